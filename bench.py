@@ -7,7 +7,11 @@ training=True (trainer.py:52), Glorot-initialised gen-0 net (seed 0), synthetic 
 One "step" = one root turn of MPGameRunner.run over all live games (mp_game_runner.py:31-68): the full
 MCTS behind every root Game.tic.  value = root env-steps of all ranks / max-over-ranks wall time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--games G | --games-total T] [--breadth B] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--games G | --games-total T] [--breadth B] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds what that figure does not need:
+HIP events around every conv launch of the timed steps (the roofline object), the untimed clock-probe turn, the engine
+kernels in isolation and the CPU baseline (each still switched off by its --no-* option).  --dump-outputs DIR writes what
+the last timed step computed as DIR/<name>.npy (float32; rank 0's games; a fixed, seeded sample where an output is large).
 N > 1: one rank per GPU, either under torch.distributed.run (RANK / WORLD_SIZE in the environment) or started by
 this script itself (`python bench.py --gpus N` spawns N fresh rank processes before touching the GPU and relays
 rank 0's JSON line).  Games shard across ranks (weak scaling: G games per GPU), no collective in the self-play
@@ -275,6 +279,61 @@ def conv_counters_profile(L, algo, board=11, profiles_dir=None):
     return out, os.path.relpath(path, REPO)
 
 
+def last_step_outputs(gr, alice, ids, moves, rewards, Xg, Vg, max_games=4096, max_obs=1024):
+    """What the last timed step computed, as float32 host arrays (--dump-outputs): what MPGameRunner.run returned
+    (rewards) and what Agent.make_moves returned (moves), the root values the agent recorded for training, the board of
+    every game after the step, a sample of the observations recorded in the step and of the rows of the iteration-end
+    exchange.  `asked` [game, snake] is 1 where the agent was asked to move that snake; elsewhere the move is -1 and the
+    root values are 0.  A reward is 0 where the game has none yet (the engine's own encoding).  Games beyond max_games and
+    observations beyond max_obs are a fixed, seeded sample (the same rows for the same arguments)."""
+    from snake_engine.engine import compact_from_state
+
+    def sample(n, cap, seed):
+        return np.arange(n) if n <= cap else np.sort(np.random.RandomState(seed).choice(n, cap, replace=False))
+    G, S = gr.game_cnt, gr.snake_cnt
+    games = sample(G, max_games, 0)
+    ids = np.asarray(ids, np.int64).reshape(-1, 2)        # (game, snake) of every move, in the order the records were made
+    out = {}
+    rw = np.zeros((G, S), np.float32)
+    for g, r in enumerate(rewards):
+        if r is not None:
+            rw[g] = [0.0 if v is None else v for v in r]
+    out["rewards"] = rw[games]
+    asked = np.zeros((G, S), np.float32)
+    asked[ids[:, 0], ids[:, 1]] = 1.0
+    out["asked"] = asked[games]
+    mv = np.full((G, S), -1.0, np.float32)
+    mv[ids[:, 0], ids[:, 1]] = moves
+    out["moves"] = mv[games]
+    vals = np.zeros((G, S, 3), np.float32)
+    vals[ids[:, 0], ids[:, 1]] = alice._rec_values[-1]      # the step's records: one per move, same order
+    out["root_values"] = vals[games]
+    st = [compact_from_state(s) for s in gr.engine.export(slots=games.astype(np.int32))]
+    for k in ("alive", "health", "length", "dir", "food", "rewards", "counters"):
+        out["state_" + k] = np.stack([s[k] for s in st]).astype(np.float32)
+    rec = sample(len(ids), max_obs, 1)
+    out["observations"] = alice.records.fetch_device(len(alice.records) - len(ids) + rec).cpu().numpy().astype(np.float32)
+    out["observation_ids"] = ids[rec].astype(np.float32)
+    rows = sample(Xg.shape[0], max_obs, 2)
+    out["exchange_rows"] = rows.astype(np.float32)
+    out["exchange_observations"] = Xg[torch.as_tensor(rows, device=Xg.device)].cpu().numpy().astype(np.float32)
+    out["exchange_values"] = Vg.cpu().numpy().astype(np.float32)
+    return out
+
+
+def write_outputs(path, outputs, limit=64 << 20):
+    bad = [name for name, a in outputs.items() if not np.isfinite(a).all()]
+    if bad:
+        raise RuntimeError(f"--dump-outputs: non-finite values in {', '.join(bad)}")
+    total = sum(a.nbytes for a in outputs.values())
+    if total > limit:
+        raise RuntimeError(f"--dump-outputs: {total} bytes of outputs, more than the {limit} allowed")
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"[rank 0] {len(outputs)} outputs of the last timed step ({total / 1e6:.1f} MB) written to {path}")
+
+
 def workload_label(board, snakes, blocks, games, breadth, world):
     """which BASELINE.json config a run is (shape AND size), or 'custom'"""
     if (board, snakes, blocks) == (11, 4, 4):
@@ -361,16 +420,25 @@ def main():
     ap.add_argument("--board", type=int, default=11, choices=[7, 11, 19], help="board side; 19 with --snakes 8 --blocks 10 = BASELINE configs[4]")
     ap.add_argument("--snakes", type=int, default=4)
     ap.add_argument("--blocks", type=int, default=4, help="residual blocks of the Q-net")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: conv-launch timing (roofline), the clock-probe turn, "
+                         "the engine kernels in isolation, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--no-conv-timing", action="store_true",
-                    help="no HIP events around the conv launches (roofline.achieved is then null): for small, launch-bound runs")
-    ap.add_argument("--no-kernel-rooflines", action="store_true")
+                    help="with --full: no HIP events around the conv launches (roofline.achieved is then null): for small, launch-bound runs")
+    ap.add_argument("--no-kernel-rooflines", action="store_true", help="with --full: no engine kernels in isolation")
     ap.add_argument("--trace-markers", action="store_true",
                     help="launch the one-wavefront k_clock_probe kernel (1 us) at the start and at the end of the timed self-play steps: "
                          "tools/gpu_busy.py finds the timed region in a rocprofv3 kernel trace by these two launches")
     ap.add_argument("--no-clock-probe", action="store_true",
-                    help="skip the untimed extra root turn that samples the shader clock beside the forward chunks (roofline.clock_mhz)")
+                    help="with --full: skip the untimed extra root turn that samples the shader clock beside the forward chunks (roofline.clock_mhz)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:            # a plain run measures the headline figure only
+        args.no_cpu_baseline = args.no_conv_timing = args.no_kernel_rooflines = args.no_clock_probe = True
 
     if args.games_total is not None:
         if args.games_total % args.gpus:
@@ -428,6 +496,14 @@ def main():
     MPGameRunner.init = "device"
     alice = Agent(nnet, 2, True, 8, args.breadth, seed=1234 + rank)
     gr = MPGameRunner(B, B, args.snakes, 1, args.games, seed=1234 + rank)
+    last_moves = [None, None]
+    if args.dump_outputs and rank == 0:
+        make_moves = alice.make_moves
+
+        def make_moves_kept(games, ids):           # the ids and moves of the latest root turn, for --dump-outputs
+            last_moves[:] = ids, make_moves(games, ids)
+            return last_moves[1]
+        alice.make_moves = make_moves_kept
 
     def barrier():
         torch.cuda.synchronize()
@@ -463,7 +539,7 @@ def main():
     env_steps = 0
     mark(0)
     for k in range(args.steps):                # one root turn per call: the same launches, plus a progress line per step
-        gr.run(alice, max_turns=1)
+        rewards = gr.run(alice, max_turns=1)
         env_steps += gr.env_steps
         if rank == 0:
             log(f"[rank 0] step {k + 1}/{args.steps}: {gr.env_steps} env-steps, {time.time() - t0:.1f} s since the start of the timed region")
@@ -497,6 +573,8 @@ def main():
     nnet._qnet.conv_timing = None
     conv_s = sum(a.elapsed_time(b) for a, b, _ in tm) * 1e-3
     rect_tiles, nnet._qnet.rect_tiles = nnet._qnet.rect_tiles, None
+    if args.dump_outputs and rank == 0:        # before anything else runs on these games (--full's clock-probe turn)
+        write_outputs(args.dump_outputs, last_step_outputs(gr, alice, *last_moves, rewards, Xg, Vg))
     # the clock the chip holds under this loop, sampled OUTSIDE the timed region (one more root turn of the same games with a
     # one-wavefront probe kernel on its own stream beside every forward chunk): nothing extra runs while the metric is timed
     clk = np.zeros(0)
@@ -525,41 +603,7 @@ def main():
     env_steps = float(per_rank[:, 0].sum())
 
     if rank == 0:
-        conv_flops = sum(f for _, _, f in tm)
-        achieved = conv_flops / conv_s / 1e12 if conv_s > 0 else None      # None: --no-conv-timing
         algo = nnet._qnet.conv_algo
-        peak = 2500.0 if algo in ("bf16", "f16s", "f16", "f16a") else 157.3      # dense MFMA peaks (bf16 / f16, f32), MI355X_MICROARCH.md
-        # MFMA flops the kernel executes per algorithmic (direct-convolution) flop: MFMAs per product x GEMM rows per pixel
-        T_full = (OBS * OBS + 31) // 32
-        per_product = 3.0 if algo == "f16s" else 1.0           # hi*hi + hi*lo + lo*hi; the reduced-precision forms issue one
-        executed = {"f16s": per_product * T_full * 32 / (OBS * OBS), "f16": T_full * 32 / (OBS * OBS), "f16a": T_full * 32 / (OBS * OBS),
-                    "bf16": T_full * 32 / (OBS * OBS), "winograd": 16 * 121 / (441 * 9.0)}.get(algo, 1.0)
-        qn = nnet._qnet
-        rect = None
-        qn.rect_tiles = rect_tiles
-        if qn.rect_tiles:
-            # sub-rectangle form: the first n_rect layers convolve the board window grown by one pixel per layer only; what
-            # the launches executed = the 32-row GEMM tiles the device-side plans counted + the full layers' tiles
-            n_layers = 2 * qn.blocks
-            imgs = sum(mm for mm, _ in qn.rect_tiles)
-            per_layer = torch.stack([c[:, 1] for _, c in qn.rect_tiles]).to(torch.float64).sum(dim=0).cpu().numpy()
-            tiles = float(per_layer.sum()) + float(imgs) * T_full * (n_layers - qn.n_rect)
-            executed = per_product * tiles * 32 / (float(imgs) * n_layers * OBS * OBS)
-            rect = {"layers": qn.n_rect, "of": n_layers,
-                    "tiles_executed_vs_full_per_layer": [float(v) / (imgs * T_full) for v in per_layer],
-                    "tiles_executed_vs_full": tiles / (float(imgs) * T_full * n_layers),
-                    "what": "tower layer i < layers convolves only the bounding box of an observation's non-background pixels (the "
-                            "board window, game.py:215-257) grown by i + 2 pixels; the rest of its output is a per-layer constant "
-                            "(bit-identical to the full convolution, tests/test_rect_conv_gpu.py); `achieved` still counts the "
-                            "reference's full direct convolution"}
-            qn.rect_tiles = None
-        # HBM bytes per average launch, from the committed rocprofv3 --pmc passes (profiles/, made by tools/conv_traffic.py).  A
-        # profile is quoted only for the kernel it was measured on: it names the sha-256 of csrc/conv_split.hip + common.h and the
-        # form (algorithm, sub-rectangle layers), and the LOADED library reports the hashes of the sources it was built from
-        traffic, traffic_src = None, None
-        if tm:
-            traffic, traffic_src = conv_traffic_profile(se.lib(), algo, qn.n_rect, conv_flops / len(tm), board=B)
-        counters, counters_src = conv_counters_profile(se.lib(), algo, board=B)
         res = {
             "metric": "self-play env-steps/sec (11x11, 4 snakes, 50 MCTS sims)",
             "value": env_steps / dt, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -580,29 +624,6 @@ def main():
                        "net_evals_per_env_step": evals / max(1, env_steps_rank0), "sim_steps_per_env_step": sims / max(1, env_steps_rank0),
                        "net_evals_per_s_rank0": evals / dt, "rollout_ticks_per_step": rollout_ticks / max(1, args.steps),
                        "net_evals_per_rollout_tick": evals / max(1, rollout_ticks), "sample_rows_gathered": int(Xg.shape[0])},
-            "roofline": {"bound": "mfma",
-                         "kernel": {"winograd": "k_conv3x3_wino_f32", "bf16": "k_conv3x3_f16s<SPLIT = false, IO16, BF = true>" + (" + its sub-rectangle form" if rect else ""),
-                                    "f16s": "k_conv3x3_f16s" + (" + k_conv3x3_f16s_rect (the same body on sub-rectangles)" if rect else ""),
-                                    "f16": "k_conv3x3_f16s<SPLIT = false>",
-                                    "f16a": "k_conv3x3_f16s<SPLIT = false, IO16>"}.get(algo, "k_conv3x3_f32"),
-                         "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                         "frac": achieved / peak if achieved else None, "traffic": traffic, "traffic_source": traffic_src,
-                         "counters": counters, "counters_source": counters_src,
-                         "launches": len(tm),
-                         "flops_convention": "algorithmic = direct 3x3 convolution, 2*441*1152*128 per state and layer (SURVEY 8d)",
-                         "executed_frac": achieved / peak * executed if achieved else None,
-                         "algorithm": {"winograd": "Winograd F(2x2,3x3) on v_mfma_f32_32x32x2_f32: executes 16*121/(441*9) = 0.488 of the "
-                                                   "algorithmic flops, fp32 throughout",
-                                       "bf16": "implicit GEMM on v_mfma_f32_32x32x16_bf16 (the split kernel's block body), bf16 operands, bf16 activations in HBM (reduced precision)",
-                                       "f16": "implicit GEMM on v_mfma_f32_32x32x16_f16, f16-rounded operands (reduced precision)",
-                                       "f16a": "implicit GEMM on v_mfma_f32_32x32x16_f16, f16 operands, f16 activations in HBM (reduced precision)",
-                                       "f16s": "implicit GEMM on v_mfma_f32_32x32x16_f16 with split operands: 3 MFMAs (hi*hi, hi*lo, lo*hi) per "
-                                               "product over the GEMM tiles actually launched (executed_frac; the full form pads 441 rows to "
-                                               "448, the sub-rectangle form computes fewer rows, see sub_rectangles); peak = dense f16 MFMA "
-                                               "at 2.4 GHz, the chip holds less in this loop (clock_mhz)"}.get(
-                                                   algo, "implicit GEMM on v_mfma_f32_32x32x2_f32"),
-                         "avg_launch_ms": conv_s / max(1, len(tm)) * 1e3,
-                         "share_of_step_time": conv_s / dt, "sub_rectangles": rect},
             # what a non-linear scaling curve is made of: one row per rank (rank r = GPU r of the node)
             "ranks": [{"rank": r, "env_steps": int(v[0]), "self_play_s": v[1], "sample_rows_s": v[2], "all_gather_s": v[3],
                        "all_reduce_s": v[4], "wall_s": v[5], "env_steps_per_s": v[0] / v[5], "net_evals": int(v[6]),
@@ -616,6 +637,64 @@ def main():
                          "bytes_per_rank": int(share) * (OBS * OBS * 3 + 3) * 4,
                          "all_gather_s_max": float(per_rank[:, 3].max()), "all_reduce_s_max": float(per_rank[:, 4].max())},
         }
+        if args.full:
+            conv_flops = sum(f for _, _, f in tm)
+            achieved = conv_flops / conv_s / 1e12 if conv_s > 0 else None      # None: --no-conv-timing
+            peak = 2500.0 if algo in ("bf16", "f16s", "f16", "f16a") else 157.3      # dense MFMA peaks of the MI355X (bf16 / f16, f32)
+            # MFMA flops the kernel executes per algorithmic (direct-convolution) flop: MFMAs per product x GEMM rows per pixel
+            T_full = (OBS * OBS + 31) // 32
+            per_product = 3.0 if algo == "f16s" else 1.0           # hi*hi + hi*lo + lo*hi; the reduced-precision forms issue one
+            executed = {"f16s": per_product * T_full * 32 / (OBS * OBS), "f16": T_full * 32 / (OBS * OBS), "f16a": T_full * 32 / (OBS * OBS),
+                        "bf16": T_full * 32 / (OBS * OBS), "winograd": 16 * 121 / (441 * 9.0)}.get(algo, 1.0)
+            qn = nnet._qnet
+            rect = None
+            qn.rect_tiles = rect_tiles
+            if qn.rect_tiles:
+                # sub-rectangle form: the first n_rect layers convolve the board window grown by one pixel per layer only; what
+                # the launches executed = the 32-row GEMM tiles the device-side plans counted + the full layers' tiles
+                n_layers = 2 * qn.blocks
+                imgs = sum(mm for mm, _ in qn.rect_tiles)
+                per_layer = torch.stack([c[:, 1] for _, c in qn.rect_tiles]).to(torch.float64).sum(dim=0).cpu().numpy()
+                tiles = float(per_layer.sum()) + float(imgs) * T_full * (n_layers - qn.n_rect)
+                executed = per_product * tiles * 32 / (float(imgs) * n_layers * OBS * OBS)
+                rect = {"layers": qn.n_rect, "of": n_layers,
+                        "tiles_executed_vs_full_per_layer": [float(v) / (imgs * T_full) for v in per_layer],
+                        "tiles_executed_vs_full": tiles / (float(imgs) * T_full * n_layers),
+                        "what": "tower layer i < layers convolves only the bounding box of an observation's non-background pixels (the "
+                                "board window, game.py:215-257) grown by i + 2 pixels; the rest of its output is a per-layer constant "
+                                "(bit-identical to the full convolution, tests/test_rect_conv_gpu.py); `achieved` still counts the "
+                                "reference's full direct convolution"}
+                qn.rect_tiles = None
+            # HBM bytes per average launch, from the committed rocprofv3 --pmc passes (profiles/, made by tools/conv_traffic.py).  A
+            # profile is quoted only for the kernel it was measured on: it names the sha-256 of csrc/conv_split.hip + common.h and the
+            # form (algorithm, sub-rectangle layers), and the LOADED library reports the hashes of the sources it was built from
+            traffic, traffic_src = None, None
+            if tm:
+                traffic, traffic_src = conv_traffic_profile(se.lib(), algo, qn.n_rect, conv_flops / len(tm), board=B)
+            counters, counters_src = conv_counters_profile(se.lib(), algo, board=B)
+            res["roofline"] = {"bound": "mfma",
+                               "kernel": {"winograd": "k_conv3x3_wino_f32", "bf16": "k_conv3x3_f16s<SPLIT = false, IO16, BF = true>" + (" + its sub-rectangle form" if rect else ""),
+                                          "f16s": "k_conv3x3_f16s" + (" + k_conv3x3_f16s_rect (the same body on sub-rectangles)" if rect else ""),
+                                          "f16": "k_conv3x3_f16s<SPLIT = false>",
+                                          "f16a": "k_conv3x3_f16s<SPLIT = false, IO16>"}.get(algo, "k_conv3x3_f32"),
+                               "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                               "frac": achieved / peak if achieved else None, "traffic": traffic, "traffic_source": traffic_src,
+                               "counters": counters, "counters_source": counters_src,
+                               "launches": len(tm),
+                               "flops_convention": "algorithmic = direct 3x3 convolution, 2*441*1152*128 per state and layer (SURVEY 8d)",
+                               "executed_frac": achieved / peak * executed if achieved else None,
+                               "algorithm": {"winograd": "Winograd F(2x2,3x3) on v_mfma_f32_32x32x2_f32: executes 16*121/(441*9) = 0.488 of the "
+                                                         "algorithmic flops, fp32 throughout",
+                                             "bf16": "implicit GEMM on v_mfma_f32_32x32x16_bf16 (the split kernel's block body), bf16 operands, bf16 activations in HBM (reduced precision)",
+                                             "f16": "implicit GEMM on v_mfma_f32_32x32x16_f16, f16-rounded operands (reduced precision)",
+                                             "f16a": "implicit GEMM on v_mfma_f32_32x32x16_f16, f16 operands, f16 activations in HBM (reduced precision)",
+                                             "f16s": "implicit GEMM on v_mfma_f32_32x32x16_f16 with split operands: 3 MFMAs (hi*hi, hi*lo, lo*hi) per "
+                                                     "product over the GEMM tiles actually launched (executed_frac; the full form pads 441 rows to "
+                                                     "448, the sub-rectangle form computes fewer rows, see sub_rectangles); peak = dense f16 MFMA "
+                                                     "at 2.4 GHz, the chip holds less in this loop (clock_mhz)"}.get(
+                                                         algo, "implicit GEMM on v_mfma_f32_32x32x2_f32"),
+                               "avg_launch_ms": conv_s / max(1, len(tm)) * 1e3,
+                               "share_of_step_time": conv_s / dt, "sub_rectangles": rect}
         if len(clk):
             held = float(np.median(clk))
             res["roofline"]["clock_mhz"] = {"median": held, "p10": float(np.percentile(clk, 10)), "p90": float(np.percentile(clk, 90)),

@@ -1,4 +1,5 @@
-"""host logic of bench.py that needs no GPU: which committed counter profile a run may quote for roofline.traffic"""
+"""host logic of bench.py that needs no GPU: which committed counter profile a run may quote for roofline.traffic, the
+outputs --dump-outputs writes, the argument checks"""
 import json
 import os
 import sys
@@ -67,3 +68,67 @@ def test_counter_profile_is_quoted_only_for_the_sources_tower_and_board_it_was_t
     json.dump(prof19, open(tmp_path / "rY_a16_sq_counters.json", "w"))
     c, src = bench.conv_counters_profile(_Lib(have), "bf16", 19, str(tmp_path))
     assert src.endswith("rY_a16_sq_counters.json") and list(c) == ["k_conv3x3_f16s<8, 1, false, 3, true>"]
+
+
+def test_dumped_outputs_are_the_last_steps_arrays_in_float32(tmp_path):
+    """--dump-outputs: the moves, root values and rewards land at their [game, snake], all finite, the board of every game after the step, a
+    fixed sample of the step's observations and of the exchange rows; the same inputs give the same files"""
+    import numpy as np
+    import torch
+    import bench
+    from snake_engine._lib import SnkGameState
+    G, S, OBS = 10, 4, 21
+
+    class Eng:
+        def export(self, slots=None):
+            arr = (SnkGameState * len(slots))()
+            for i, s in enumerate(slots):
+                arr[i].H = arr[i].W = 11
+                arr[i].S = S
+                arr[i].health[0] = int(s)
+            return arr
+
+    class Runner:
+        game_cnt, snake_cnt, engine = G, S, Eng()
+
+    class Records:
+        def __len__(self):
+            return 30
+
+        def fetch_device(self, idx):           # record i's observation is filled with i
+            return torch.as_tensor(np.asarray(idx, np.float32))[:, None, None, None].expand(-1, OBS, OBS, 3)
+
+    class Agent:
+        records = Records()
+        _rec_values = [np.zeros((1, 3), np.float32), np.arange(36, dtype=np.float32).reshape(12, 3)]
+    ids = [(g, s) for g in range(3, 9) for s in (0, 2)]
+    rewards = [None] * G
+    rewards[1] = [1.0, None, -1.0, None]
+    Xg, Vg = torch.rand(50, OBS, OBS, 3), torch.rand(50, 3)
+    out = bench.last_step_outputs(Runner(), Agent(), ids, [1, 2] * 6, rewards, Xg, Vg, max_obs=8)
+    assert all(v.dtype == np.float32 for v in out.values())
+    assert all(np.isfinite(v).all() for v in out.values())
+    assert out["asked"].sum() == 12 and out["asked"][3].tolist() == [1, 0, 1, 0] and not out["asked"][0].any()
+    assert out["moves"][3].tolist() == [1, -1, 2, -1] and (out["moves"][0] == -1).all()
+    assert out["root_values"][8, 2].tolist() == [33, 34, 35] and not out["root_values"][0].any()
+    assert out["rewards"][1].tolist() == [1.0, 0.0, -1.0, 0.0] and not out["rewards"][0].any()
+    assert out["state_health"][:, 0].tolist() == list(range(G)) and out["state_food"].shape == (G, 121)
+    assert out["observations"].shape == (8, OBS, OBS, 3) and out["observations"][:, 0, 0, 0].min() >= 30 - 12
+    rec = out["observations"][:, 0, 0, 0].astype(int) - 18                    # which of the step's 12 records were sampled
+    assert out["observation_ids"].tolist() == [list(ids[i]) for i in rec]
+    assert np.array_equal(Xg[out["exchange_rows"].astype(np.int64)].numpy(), out["exchange_observations"]) and len(out["exchange_rows"]) == 8
+    again = bench.last_step_outputs(Runner(), Agent(), ids, [1, 2] * 6, rewards, Xg, Vg, max_obs=8)
+    assert all(np.array_equal(out[k], again[k]) for k in out)
+    bench.write_outputs(str(tmp_path / "o"), out)
+    assert sorted(os.listdir(tmp_path / "o")) == sorted(k + ".npy" for k in out)
+    import pytest
+    with pytest.raises(RuntimeError, match="more than"):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros((17 << 20,), np.float32)})
+    with pytest.raises(RuntimeError, match="non-finite values in x"):
+        bench.write_outputs(str(tmp_path / "nan"), {"x": np.array([0.0, np.nan], np.float32)})
+
+
+def test_steps_must_be_positive():
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert out.returncode != 0 and "--steps" in out.stderr

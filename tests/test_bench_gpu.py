@@ -1,4 +1,4 @@
-"""GPU test of the bench.py contract: one JSON line with the metric, the roofline object and the cpu_baseline object."""
+"""GPU test of the bench.py contract: one JSON line with the metric; with --full also the roofline object and the cpu_baseline object."""
 import json
 import os
 import subprocess
@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_fields():
     env = dict(os.environ)
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--games", "16", "--breadth", "16", "--steps", "2",
-                          "--warmup", "1"], capture_output=True, text=True, env=env, timeout=600)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -51,6 +51,34 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
         e = d["engine_kernels"][k]
         assert e["bound"] == "hbm" and e["unit"] == "GB/s" and 0 < e["frac"] < 1
 
+
+
+def test_plain_run_prints_the_headline_line_and_dumps_the_last_step(tmp_path):
+    """without --full: the headline fields and nothing that takes a measurement of its own; --dump-outputs writes what the last
+    timed step computed as float32 .npy files"""
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--games", "16", "--breadth", "16", "--steps", "2",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "ranks"):
+        assert k in d, k
+    assert d["unit"] == "env-steps/s" and d["steps"] == 2 and d["warmup"] == 1 and d["dtype"].startswith("f32")
+    assert d["value"] > 0 and abs(d["value"] - 2 * 16 / (d["ms_per_step"] * 2e-3)) / d["value"] < 0.05
+    for k in ("roofline", "cpu_baseline", "engine_kernels"):
+        assert k not in d, k
+    import numpy as np
+    a = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(np.isfinite(v).all() for v in a.values())
+    asked = a["asked"] == 1                                         # [game, snake]: the snakes the agent was asked to move
+    assert a["moves"].shape == (16, 4) and a["state_food"].shape == (16, 121) and asked.any()
+    assert set(np.unique(a["moves"][asked])) <= {0.0, 1.0, 2.0} and (a["moves"][~asked] == -1).all()
+    assert not a["root_values"][~asked].any()
+    assert a["observations"].shape == (asked.sum(), 21, 21, 3) and a["observation_ids"].shape == (asked.sum(), 2)
+    assert a["exchange_values"].shape == (d["config"]["sample_rows_gathered"], 3)
+    assert a["exchange_observations"].shape == (a["exchange_rows"].shape[0], 21, 21, 3)
 
 def test_bench_gpus_2_launches_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it: the parent spawns two fresh ranks before touching the GPU and

@@ -5,8 +5,8 @@
 #   `make variant NAME=alt EXTRA=-D...` build) or "" for the defaults.  A bench.py command is summarised from its JSON line
 #   (value, conv TFLOP/s, held clock, executed fraction of the held clock's peak); any other command by its last output line.
 # Replaces round 5's eighteen one-shot tools/r5_*.sh (same pattern, different variant names); typical commands:
-#     python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-kernel-rooflines                         (judged workload)
-#     python3 bench.py --board 19 --snakes 8 --blocks 10 --games 4096 --conv-algo bf16 --steps 25 --warmup 10 --no-cpu-baseline --no-kernel-rooflines
+#     python3 bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-kernel-rooflines                         (judged workload)
+#     python3 bench.py --board 19 --snakes 8 --blocks 10 --games 4096 --conv-algo bf16 --steps 25 --warmup 10 --full --no-cpu-baseline --no-kernel-rooflines
 #     python3 tools/a16_layers.py 19 500 5      python3 tools/rect_layers.py      python3 tools/fit_time.py 32
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 N=2; [ "$1" = "-n" ] && { N=$2; shift 2; }

@@ -6,11 +6,11 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; T=${1:-r6}
 O=$R/gpurun_out/${T}set
 mkdir -p $O; cd $R
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench.json 2> $O/${T}_bench.err && tail -2 $O/${T}_bench.err
-python bench.py --games 8 --breadth 25 --steps 40 --warmup 5 --no-conv-timing --no-cpu-baseline --no-kernel-rooflines > $O/${T}_bench_config0.json 2> $O/${T}_bench_config0.err
-python bench.py --gpus 2 --steps 3 --warmup 1 > $O/${T}_bench_2ranks_gloo_1gpu.json 2> $O/${T}_bench_2ranks.err
-python bench.py --gpus 6 --games 64 --breadth 8 --steps 2 --warmup 1 > $O/${T}_bench_6ranks_gloo_1gpu.json 2> $O/${T}_bench_6ranks.err
-python bench.py --board 19 --snakes 8 --blocks 10 --games 4096 --conv-algo bf16 --steps 40 --warmup 10 --no-cpu-baseline --no-kernel-rooflines > $O/${T}_bench_config4_shape_bf16_long.json 2> $O/${T}_bench_config4_shape_bf16_long.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${T}_bench.json 2> $O/${T}_bench.err && tail -2 $O/${T}_bench.err
+python bench.py --games 8 --breadth 25 --steps 40 --warmup 5 --no-conv-timing --no-cpu-baseline --no-kernel-rooflines --full > $O/${T}_bench_config0.json 2> $O/${T}_bench_config0.err
+python bench.py --gpus 2 --steps 3 --warmup 1 --full > $O/${T}_bench_2ranks_gloo_1gpu.json 2> $O/${T}_bench_2ranks.err
+python bench.py --gpus 6 --games 64 --breadth 8 --steps 2 --warmup 1 --full > $O/${T}_bench_6ranks_gloo_1gpu.json 2> $O/${T}_bench_6ranks.err
+python bench.py --board 19 --snakes 8 --blocks 10 --games 4096 --conv-algo bf16 --steps 40 --warmup 10 --no-cpu-baseline --no-kernel-rooflines --full > $O/${T}_bench_config4_shape_bf16_long.json 2> $O/${T}_bench_config4_shape_bf16_long.err
 python3 tools/gpu_busy.py $O/${T}_busy_ref_defaults -- --games 256 --breadth 128 --steps 6 --warmup 2 > /dev/null
 python - <<P
 import json, os

@@ -74,7 +74,7 @@ def main():
     out_dir = prefix + "_trace"
     env = dict(os.environ, TMPDIR="/tmp")
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out_dir, "--", sys.executable, os.path.join(REPO, "bench.py"),
-           *bench_args, "--trace-markers", "--no-clock-probe", "--no-cpu-baseline", "--no-kernel-rooflines"]
+           *bench_args, "--full", "--trace-markers", "--no-clock-probe", "--no-cpu-baseline", "--no-kernel-rooflines"]
     p = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=open(prefix + ".err", "w"), text=True)
     if p.returncode:
         raise SystemExit(f"gpu_busy: bench under rocprofv3 exited {p.returncode}; see {prefix}.err")

@@ -11,9 +11,9 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; T=${1:-r6}
 O=$R/gpurun_out/prof_$T
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-kernel-rooflines > $O/${T}_bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -- python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-kernel-rooflines > $O/${T}_bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 cp $(find $O/bench -name "*kernel_stats.csv" | head -1) $O/${T}_bench_kernel_stats.csv; echo "bench kernel-trace done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_c4 -- python3 $R/bench.py --board 19 --snakes 8 --blocks 10 --games 4096 --conv-algo bf16 --steps 12 --warmup 10 --no-cpu-baseline --no-kernel-rooflines > $O/${T}_bench_config4_shape_bf16_under_rocprof.json 2> $O/bench_c4_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_c4 -- python3 $R/bench.py --board 19 --snakes 8 --blocks 10 --games 4096 --conv-algo bf16 --steps 12 --warmup 10 --full --no-cpu-baseline --no-kernel-rooflines > $O/${T}_bench_config4_shape_bf16_under_rocprof.json 2> $O/bench_c4_under_rocprof.err
 cp $(find $O/bench_c4 -name "*kernel_stats.csv" | head -1) $O/${T}_bench_config4_shape_bf16_kernel_stats.csv; echo "configs[4] kernel-trace done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/fit -- python3 $R/tools/fit_time.py 8 > $O/fit_under_rocprof.log 2>&1
 cp $(find $O/fit -name "*kernel_stats.csv" | head -1) $O/${T}_fit_kernel_stats.csv; echo "fit kernel-trace done"
