@@ -38,6 +38,9 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef short s16x2 __attribute__((ext_vector_type(2)));
 
 // the 16-bit activation type of the reduced-precision towers is f16 or (BF) bf16; both travel through the kernel as 16-bit
 // patterns typed _Float16 (staging copies them untouched), only the MFMA and these two conversions know the difference
@@ -177,6 +180,50 @@ extern "C" int snk_dbg_conv_stamps(unsigned long long *h_out, int n_blocks)
 //   9 MODE 6 that also takes MODE 4's per-channel maxima (its own batch norm is deferred too: the layer above a deferred stem)
 //  10 MODE 8 whose ReLU decision for the sums is recomputed like MODE 7's (the layer below is the deferred stem: no mask bytes)
 #define hs_dpp(v, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xF, 0xF, true))
+
+// ---- MX-FP8 (the mxfp8 tower, SNK_CONV_ALGO=mxfp8): OCP e4m3fn codes with one E8M0 scale per block of 32 input channels --------
+// The rule (kernel, tests/mxfp8_ref.py and DESIGN.md section 4 state the same one):
+//   block    activations: channels 32j .. 32j + 31 of one pixel; weights: the same 32 input channels of one (output channel, tap)
+//   amax     the largest |v| of the block in float32 (bf16 activations are exact there; weights come from the float32 values)
+//   E        the smallest integer with amax * 2^-E <= 448, clamped to [-127, 127]; amax == 0 gives E = -127 (all codes zero);
+//            the scale byte is E + 127
+//   code     e4m3fn round-to-nearest-even of v * 2^-E, subnormals kept; by the choice of E nothing saturates
+// With amax = m 2^e (1 <= m < 2): E = e - 8 when m <= 1.75 (m 2^8 <= 448 < m 2^9), else e - 7 -- read off amax's float bits.
+__device__ __forceinline__ unsigned mx_scale_byte(float amax)
+{
+    const unsigned b = __builtin_bit_cast(unsigned, amax);                  // amax >= 0: exponent field = b >> 23
+    const int s = (int)(b >> 23) - 8 + ((b & 0x7FFFFFu) > 0x600000u ? 1 : 0);  // E + 127; a float32 subnormal or zero clamps to 0
+    return (unsigned)max(s, 0);
+}
+// 2^-E as a float32 (E <= 120 for any finite amax: a normal number)
+__device__ __forceinline__ float mx_inv_scale(unsigned sbyte) { return __builtin_bit_cast(float, (254u - sbyte) << 23); }
+// four values (already multiplied by 2^-E, exact: a power-of-two product) -> four e4m3fn codes, RNE (the converter's scale is 1)
+__device__ __forceinline__ unsigned mx_pack4(float a, float b, float c, float d)
+{
+    s16x2 w = {0, 0};
+    w = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w, a, b, 1.0f, false);
+    w = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w, c, d, 1.0f, true);
+    return __builtin_bit_cast(unsigned, w);
+}
+// The staging path's quantizer: eight bf16 channels (bit patterns) of one lane -> eight codes (bytes 0..7) and the block's scale
+// byte.  The block is this lane's quad (lanes 4q .. 4q + 3 hold its channels 8i .. 8i + 7): amax over the quad by two DPP steps,
+// so every lane of the wave must run it.  k_mxfp8_quantize runs the same function on a plain bf16 array.
+__device__ __forceinline__ uint2 mx_quant8(const f16x8 v, unsigned &sbyte)
+{
+    const uint4 u = __builtin_bit_cast(uint4, v);          // bf16 -> float32 by bits (exact): the pair (lo, hi) of each dword
+    const float f[8] = {__builtin_bit_cast(float, u.x << 16), __builtin_bit_cast(float, u.x & 0xFFFF0000u),
+                        __builtin_bit_cast(float, u.y << 16), __builtin_bit_cast(float, u.y & 0xFFFF0000u),
+                        __builtin_bit_cast(float, u.z << 16), __builtin_bit_cast(float, u.z & 0xFFFF0000u),
+                        __builtin_bit_cast(float, u.w << 16), __builtin_bit_cast(float, u.w & 0xFFFF0000u)};
+    float m = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(f[j]));
+    m = fmaxf(m, hs_dpp(m, 0xB1));                        // quad_perm [1, 0, 3, 2]
+    m = fmaxf(m, hs_dpp(m, 0x4E));                        // quad_perm [2, 3, 0, 1]
+    sbyte = mx_scale_byte(m);
+    const float k = mx_inv_scale(sbyte);
+    return make_uint2(mx_pack4(f[0] * k, f[1] * k, f[2] * k, f[3] * k), mx_pack4(f[4] * k, f[5] * k, f[6] * k, f[7] * k));
+}
 // SPLIT = false: the reduced-precision form for BASELINE configs[4] ("bf16 MFMA conv"): the same kernel with the hi parts
 //   only, one MFMA per product instead of three (f16 operands: 11 significand bits against bf16's 8, float32 accumulate).
 // IO16 (reduced-precision form only): bit 0 = the input and the residual are f16 arrays [n][H][W][128], bit 1 = the output
@@ -189,13 +236,23 @@ extern "C" int snk_dbg_conv_stamps(unsigned long long *h_out, int n_blocks)
 // BF (with IO16 bit 0, reduced-precision form only): the 16-bit type is bf16 -- BASELINE configs[4]'s "bf16 MFMA conv" as it is
 //   worded: bf16 activations in HBM, bf16 weights, v_mfma_f32_32x32x16_bf16, float32 accumulation and epilogue.  bf16 has
 //   float32's exponent range, so there is no scale to choose and nothing to clamp.
-template <int NI, int MODE, bool SPLIT, int IO16, bool RECT, bool BF = false>
+// MX (with BF): the mxfp8 tower -- bf16 activations in HBM as in the bf16 form, but a chunk is 64 input channels (one K step of
+//   v_mfma_scale_f32_32x32x64_f8f6f4) quantized at staging time by the rule above: the 80-byte LDS pixel holds [codes of block 0
+//   (32 bytes) | codes of block 1 | scale byte 0, scale byte 1 | 14 unused], so the frame's geometry (pitches, pixels per buffer,
+//   384 staged pixels per chunk) and with it the rectangle plan are the 16-bit frame's.  The MFMA takes bytes 16 b .. 16 b + 15 of
+//   both lane halves as k-block b and the scale of (row r, block b) from lane (b, r) (measured with exact integer data,
+//   tests/test_mxfp8_gpu.py): lane (h, r) reads channels 16 h .. 16 h + 15 of each block of pixel r -- the 16-bit frame's two
+//   ds_read_b128 at +16 h and +32 + 16 h -- and the scale byte of block h; B likewise from k_mxfp8_weights' image.  Per (tile,
+//   tap) the bf16 form issues 2 MFMAs of 32 cycles in each of 4 chunks, this form 1 MFMA of 64 cycles in each of 2 chunks: a
+//   quarter of the MFMAs, half the MFMA time, half the chunks and barriers.
+template <int NI, int MODE, bool SPLIT, int IO16, bool RECT, bool BF = false, bool MX = false>
 __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *smem, const int img, const int tile0, const int ntile,
                                          const int ry0, const int rx0, const int rh, const int rw, const unsigned bbox,
                                          const int part, const int parts)
 {
     static_assert(IO16 == 0 || !SPLIT, "f16 activations only exist in the reduced-precision form");
     static_assert(!BF || (IO16 & 1), "the bf16 form reads bf16 activations");
+    static_assert(!MX || BF, "the mxfp8 form reads bf16 activations");
     constexpr bool IN16 = (IO16 & 1) != 0, OUT16 = (IO16 & 2) != 0;
     constexpr bool STATS = MODE == 4 || MODE == 6 || MODE == 9, GSTATS = MODE == 5 || MODE == 7 || MODE == 8 || MODE == 10, BARE = STATS || GSTATS;
     constexpr bool RESMASK = MODE == 8 || MODE == 10, AMAX = MODE == 4 || MODE == 9;
@@ -204,9 +261,18 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     constexpr bool K32 = IN16;
     constexpr int RING = K32 ? HS_RING16 : HS_RING, AHEAD = K32 ? HS_AHEAD16 : HS_AHEAD;      // B-fragment register ring: slots (a divisor of 9), taps ahead
     constexpr bool TWO = SPLIT || K32;                     // two A fragments / two B fragments per (tap, M tile)
-    constexpr int KC = K32 ? 32 : HS_KC, NCHUNK = HS_C / KC;
+    constexpr int KC = MX ? 64 : K32 ? 32 : HS_KC, NCHUNK = HS_C / KC;
     constexpr int NST = K32 ? HS_NST16 : HS_NST, BUFB = K32 ? HS_BUF16 : HS_NPB * HS_LDP;
     constexpr int PIECE = K32 ? 8 : 4;                     // channels of a staging item
+    // MX: a 64-channel chunk is staged in two halves of 32 channels (one MX block per pixel each) with the 16-bit frame's items --
+    // half 0 loaded at tap 0 and written from region MXR0 on, half 1 loaded at the start of tap MXT1 into the same registers and
+    // written in the chunk's last 2 NST regions (twelve items in flight at once spill the 8-tile bodies)
+    // (half 0 is written from region MXR0 on: not before the region whose tap issued its loads, HS_XLOAD_TAP)
+    constexpr int MXR0_ = 9 * NI > 4 * NST ? (9 * NI - 4 * NST) / 2 : 0;
+    constexpr int MXR0 = MXR0_ > HS_XLOAD_TAP * NI ? MXR0_ : HS_XLOAD_TAP * NI, MXT1 = (MXR0 + 2 * NST + NI - 1) / NI;
+    constexpr int MXR1 = 9 * NI - 2 * NST > MXT1 * NI ? 9 * NI - 2 * NST : MXT1 * NI;
+    constexpr bool MXIN = MX && 9 * NI >= 4 * NST && MXT1 <= 8 && MXR1 + 2 * NST <= 9 * NI;     // else both halves at the chunk's end
+    static_assert(!MXIN || (MXR0 >= HS_XLOAD_TAP * NI && MXR0 + 2 * NST <= MXT1 * NI), "MX staging: a half is written before it is loaded");
     constexpr bool P8 = IN16 && OUT16;                     // the epilogue handles 8 channels (16 bytes in and out) per thread and row
     // (MODE 7 never takes a shortcut's gradient: it produces the gradient at a block's FIRST layer's output -- its epilogue has the
     // registers the shortcut rows would take for the g_y rows instead, requested a pass ahead)
@@ -251,7 +317,7 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     for (int k = 0; k < NST; ++k) {
         const int pix_ = min(pix0 + 64 * k, npx - 1);
         const int r_ = (int)(((float)pix_ + 0.5f) * invWs), x_ = pix_ - r_ * ws;
-        ldo[k] = (ry_lo + r_) * PB + (cx_lo + x_) * HS_LDP + (tid & 3) * (K32 ? 16 : 8);
+        ldo[k] = (ry_lo + r_) * PB + (cx_lo + x_) * HS_LDP + (tid & 3) * (MX ? 8 : K32 ? 16 : 8);     // (MX: the piece's 8 codes in half 0)
         gof[k] = (r_ * p.Wd + x_) * HS_C;
         if (RECT) {
             const int Y = ya + r_, X = xa + x_;
@@ -264,6 +330,10 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     float4 st[K32 ? 1 : NST];
     f16x4 st16[K32 ? 1 : NST];
     f16x8 st8[K32 ? NST : 1];                              // the 16-bit frame's items: eight channels, staged as they are
+    f16x8 st8b[MX ? NST : 1];                              // MX: half 1 of the first chunk, and of every chunk in the 1-2 tile bodies
+    uint2 mq_t = make_uint2(0u, 0u);                       // MX: an item's eight codes and its block's scale byte (split half A -> B)
+    unsigned ms_t = 0u;
+    const unsigned ms_off = 64 - 8 * (tid & 3);            // MX: from an item's codes (half 0) to the pixel's scale byte of half 0
     f16x4 hi_t;
     float4 d_t;
     float4 asc = make_float4(1.f, 1.f, 1.f, 1.f), ash = make_float4(0.f, 0.f, 0.f, 0.f);    // MODE 6: the producer's scale / shift of the
@@ -275,9 +345,13 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
         if (K32) st8[k_] = *(const f16x8 *)((RECT ? gp16[k_] : xrow16 + gof[k_]) + KC * (c));   \
         else if (IN16) st16[k_] = *(const f16x4 *)((RECT ? gp16[k_] : xrow16 + gof[k_]) + KC * (c)); \
         else st[k_] = *(const float4 *)((RECT ? gp[k_] : xrow + gof[k_]) + KC * (c)); }
+// MX: half 1 (channels 32-63) of chunk c
+#define HS_LOAD_H1(dst, c) _Pragma("unroll") for (int k_ = 0; k_ < NST; ++k_)                  \
+        dst[k_] = *(const f16x8 *)((RECT ? gp16[k_] : xrow16 + gof[k_]) + KC * (c) + 32);
 // split of one staged float4 in two halves that sit in different MFMA regions (a region hides about 15 VALU instructions):
 //   A: clamp to the f16 range, hi = f16(v), d = v - hi;   B: lo = f16(d), both written to LDS
 #define HS_SPLIT_A(kk)                                                                          \
+    if (MX) { mq_t = mx_quant8(st8[kk], ms_t); } else                                           \
     if (K32) { } else if (IN16) { hi_t = st16[kk]; } else                                       \
     {                                                                                           \
         float4 v_ = st[kk];                                                                     \
@@ -295,7 +369,14 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
             d_t.z = v_.z - (float)hi_t[2]; d_t.w = v_.w - (float)hi_t[3];                       \
         }                                                                                       \
     }
+// MX: an item's codes and its block's scale byte into half hf_ of the pixel (the quad's four lanes write the same byte)
+#define HS_MXB(k_, bufoff, hf_)                                                                 \
+    {                                                                                           \
+        *(uint2 *)(smem + (bufoff) + ldo[k_] + 32 * (hf_)) = mq_t;                              \
+        smem[(bufoff) + ldo[k_] + ms_off + (hf_)] = (unsigned char)ms_t;                        \
+    }
 #define HS_SPLIT_B(k_, bufoff)                                                                  \
+    if (MX) { HS_MXB(k_, bufoff, 0) } else                                                      \
     if (K32) { *(f16x8 *)(smem + (bufoff) + ldo[k_]) = st8[k_]; } else                          \
     {                                                                                           \
         unsigned char *d_ = smem + (bufoff) + ldo[k_];                                          \
@@ -311,13 +392,18 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     HS_STAMP_HWID(7)
     const f16x8 *wl = p.wS + wn * 128 + lane;              // this wave's fragments of global step g = 9 chunk + tap: wl[g * 512 + {0 hi, 64 lo}]
     f16x8 Bq[RING][2];
+    // MX: the image's codes are [step 18][wn 4][half 2][lane 64] x 16 bytes (the same strides), its scale bytes [step 18][wn 4][lane 64] behind them
+    const unsigned char *wsb = (const unsigned char *)p.wS + 9 * HS_C * HS_C + wn * 64 + lane;
+    unsigned Bs[RING];
 #define HS_LOADB(slot, g)                                                                       \
     {                                                                                           \
         const f16x8 *w_ = wl + (long)(g) * 512;                                                 \
         Bq[slot][0] = w_[0];                                                                    \
         if (TWO) Bq[slot][1] = w_[64];                                                          \
+        if (MX) Bs[slot] = wsb[(g) * 256];                                                      \
     }
     HS_LOAD(0)
+    if (MX) { HS_LOAD_H1(st8b, 0) }
 #pragma unroll
     for (int s = 0; s < AHEAD; ++s) HS_LOADB(s, s);
     if (K32) {
@@ -348,6 +434,10 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     if (AFF) HS_AFF_READ(0)
 #pragma unroll
     for (int k = 0; k < NST; ++k) { HS_SPLIT_A(k) HS_SPLIT_B(k, 0) }
+    if (MX) {
+#pragma unroll
+        for (int k = 0; k < NST; ++k) { mq_t = mx_quant8(st8b[k], ms_t); HS_MXB(k, 0, 1) }
+    }
     __syncthreads();
 
     unsigned la[NI];                                       // LDS byte address (buffer 0, centre tap) of the lane's pixel in M tile i
@@ -357,9 +447,15 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
         const int y_ = (int)(((float)m_ + 0.5f) * invW), x_ = m_ - y_ * Wr;
         la[i] = (unsigned)((y_ - (y_first - 1)) * PB + (x_ + 1) * HS_LDP) + 16 * h;
     }
+    const unsigned as_off = 64 - 15 * h;                   // MX: from the lane's first codes to the scale byte of block h of the pixel
 #define HS_LDS(off) (*(const f16x8 *)(smem + (off)))
 #define HS_MFMA(a, b, c) c = BF ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0) \
                               : __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
+// MX: A = 32 codes (two 16-byte halves) with the lane's scale byte, B the same; format 0 (e4m3) for both, scales in byte 0
+#define HS_MFMA_MX(ah, al, as, bh, bl, bs, c) c = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(                           \
+        __builtin_shufflevector(__builtin_bit_cast(i32x4, ah), __builtin_bit_cast(i32x4, al), 0, 1, 2, 3, 4, 5, 6, 7),          \
+        __builtin_shufflevector(__builtin_bit_cast(i32x4, bh), __builtin_bit_cast(i32x4, bl), 0, 1, 2, 3, 4, 5, 6, 7),          \
+        c, 0, 0, 0, (int)(as), 0, (int)(bs))
 // One tap of a chunk = NI fenced regions, each = { the ds_reads of the tile two ahead; a share of the staging work;
 // this tile's three MFMAs }.  The fences keep the A fragments two tiles ahead of their use (the compiler otherwise
 // sinks the reads to the MFMAs that consume them and the wave eats the LDS latency once per tile).  The tile sequence
@@ -371,21 +467,41 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
             _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                    \
                 const int t2_ = (s) * NI + i + 2;                                               \
                 f16x8 nh = a1h, nl = a1l;                                                       \
-                if (t2_ < 9 * NI) { nh = HS_LDS(HS_AOFF(t2_)); if (TWO) nl = HS_LDS(HS_AOFF(t2_) + 32); } \
+                unsigned ns = a1s;                                                              \
+                if (t2_ < 9 * NI) {                                                             \
+                    nh = HS_LDS(HS_AOFF(t2_)); if (TWO) nl = HS_LDS(HS_AOFF(t2_) + 32);         \
+                    if (MX) ns = smem[HS_AOFF(t2_) + as_off];                                   \
+                }                                                                               \
                 __builtin_amdgcn_sched_barrier(0);                                              \
                 if (i == 0) {                                                                   \
                     HS_TSTAMP(c, (s))                                                           \
                     if (MORE || (s) + AHEAD < 9) { HS_LOADB(((s) + AHEAD) % RING, gnext + (s)); } \
                     if ((s) == HS_XLOAD_TAP && MORE) { HS_LOAD(c + 1) }                         \
+                    if (MXIN && MORE && (s) == MXT1) { HS_LOAD_H1(st8, c + 1) }                 \
+                    if (MX && !MXIN && MORE && (s) == HS_XLOAD_TAP) { HS_LOAD_H1(st8b, c + 1) } \
+                }                                                                               \
+                if (MXIN && MORE) {                                                             \
+                    const int u0_ = (s) * NI + i - MXR0, u1_ = (s) * NI + i - MXR1;             \
+                    if (u0_ >= 0 && u0_ < 2 * NST) {                                            \
+                        if ((u0_ & 1) == 0) { HS_SPLIT_A((u0_ < 0 ? 0 : min(u0_ >> 1, NST - 1))) }            \
+                        else { HS_MXB((u0_ < 0 ? 0 : min(u0_ >> 1, NST - 1)), wb, 0) }                        \
+                    }                                                                           \
+                    if (u1_ >= 0 && u1_ < 2 * NST) {                                            \
+                        if ((u1_ & 1) == 0) { HS_SPLIT_A((u1_ < 0 ? 0 : min(u1_ >> 1, NST - 1))) }            \
+                        else { HS_MXB((u1_ < 0 ? 0 : min(u1_ >> 1, NST - 1)), wb, 1) }                        \
+                    }                                                                           \
                 }                                                                               \
                 {                                                                               \
                     const int tl_ = (s) * NI + i - (9 * NI - 2 * NST);                          \
                     if (AFF && MORE && 9 * NI >= 2 * NST && tl_ == -1) HS_AFF_READ(c + 1)       \
-                    if (MORE && 9 * NI >= 2 * NST && tl_ >= 0) {                                \
+                    if (!MX && MORE && 9 * NI >= 2 * NST && tl_ >= 0) {                         \
                         if ((tl_ & 1) == 0) { HS_SPLIT_A((tl_ < 0 ? 0 : tl_ >> 1)) }            \
                         else { HS_SPLIT_B((tl_ < 0 ? 0 : tl_ >> 1), wb) }                       \
                     }                                                                           \
                 }                                                                               \
+                if (MX) {                                /* the chunk's 64 channels in one MFMA */ \
+                    HS_MFMA_MX(a0h, a0l, a0s, Bq[(s) % RING][0], Bq[(s) % RING][1], Bs[(s) % RING], acc[i]); \
+                } else {                                                                        \
                 HS_MFMA(a0h, Bq[(s) % RING][0], acc[i]);                                     \
                 if (SPLIT) {                                                                    \
                     HS_MFMA(a0h, Bq[(s) % RING][1], acc[i]);                                 \
@@ -393,7 +509,8 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
                 } else if (K32) {                        /* the chunk's second k step: channels 16-31 */ \
                     HS_MFMA(a0l, Bq[(s) % RING][1], acc[i]);                                 \
                 }                                                                               \
-                a0h = a1h; a0l = a1l; a1h = nh; a1l = nl;                                       \
+                }                                                                               \
+                a0h = a1h; a0l = a1l; a1h = nh; a1l = nl; a0s = a1s; a1s = ns;                  \
                 __builtin_amdgcn_sched_barrier(0);                                              \
             }                                                                                   \
         }
@@ -403,12 +520,18 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
         const unsigned wb = (unsigned)((c & 1) ^ 1) * BUFB;                                     \
         const int gnext = c * 9 + AHEAD;             /* global step the first prefetch of this chunk fetches */ \
         f16x8 a0h = HS_LDS(HS_AOFF(0)), a1h = HS_LDS(HS_AOFF(1)), a0l = a0h, a1l = a1h;         \
+        unsigned a0s = 0u, a1s = 0u;                                                            \
         if (TWO) { a0l = HS_LDS(HS_AOFF(0) + 32); a1l = HS_LDS(HS_AOFF(1) + 32); }              \
+        if (MX) { a0s = smem[HS_AOFF(0) + as_off]; a1s = smem[HS_AOFF(1) + as_off]; }          \
         HS_TAP(0, MORE) HS_TAP(1, MORE) HS_TAP(2, MORE) HS_TAP(3, MORE) HS_TAP(4, MORE)         \
         HS_TAP(5, MORE) HS_TAP(6, MORE) HS_TAP(7, MORE) HS_TAP(8, MORE)                         \
-        if (MORE && 9 * NI < 2 * NST) {                 /* too few regions to spread the split over: do it here */ \
+        if (!MX && MORE && 9 * NI < 2 * NST) {          /* too few regions to spread the split over: do it here */ \
             if (AFF) HS_AFF_READ(c + 1)                                                         \
             _Pragma("unroll") for (int k = 0; k < NST; ++k) { HS_SPLIT_A(k) HS_SPLIT_B(k, wb) } \
+        }                                                                                       \
+        if (MX && MORE && !MXIN) {      /* MX, 1-2 tiles: both halves loaded at tap HS_XLOAD_TAP (registers to spare), written here */ \
+            _Pragma("unroll") for (int k = 0; k < NST; ++k) { HS_SPLIT_A(k) HS_MXB(k, wb, 0) }  \
+            _Pragma("unroll") for (int k = 0; k < NST; ++k) { mq_t = mx_quant8(st8b[k], ms_t); HS_MXB(k, wb, 1) } \
         }                                                                                       \
         __syncthreads();                                                                        \
     }
@@ -453,10 +576,13 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
 #undef HS_LOAD
 #undef HS_SPLIT_A
 #undef HS_SPLIT_B
+#undef HS_MXB
+#undef HS_LOAD_H1
 #undef HS_LOADB
 #undef HS_AFF_READ
 #undef HS_LDS
 #undef HS_MFMA
+#undef HS_MFMA_MX
 
     // ---- epilogue: 64 GEMM rows (2 M tiles) at a time through a double-buffered LDS exchange, so that every thread
     //      handles float4 pieces of whole pixel rows: thread (rr0 = tid / 32, cq = tid % 32) takes rows rr0 + 8 j of the
@@ -800,7 +926,7 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     HS_STAMP(4)
 }
 
-template <int NI, int MODE, bool SPLIT = true, int IO16 = 0, bool BF = false>
+template <int NI, int MODE, bool SPLIT = true, int IO16 = 0, bool BF = false, bool MX = false>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_f16s(ConvHsArgs p)
 {
     __shared__ __align__(16) unsigned char smem[HS_SMEM];
@@ -818,10 +944,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_f16s(ConvHsArgs p)
     // layers' MFMAs computed rows nobody stored); the choice is wave-uniform
     if constexpr (IO16 != 0 && NI > 1) {
         switch (ntile) {
-        case NI - 1: hs_block<NI - 1, MODE, SPLIT, IO16, false, BF>(p, smem, img, tile0, ntile, 0, 0, 0, 0, 0u, 0, 1); break;
-        default: hs_block<NI, MODE, SPLIT, IO16, false, BF>(p, smem, img, tile0, ntile, 0, 0, 0, 0, 0u, 0, 1); break;
+        case NI - 1: hs_block<NI - 1, MODE, SPLIT, IO16, false, BF, MX>(p, smem, img, tile0, ntile, 0, 0, 0, 0, 0u, 0, 1); break;
+        default: hs_block<NI, MODE, SPLIT, IO16, false, BF, MX>(p, smem, img, tile0, ntile, 0, 0, 0, 0, 0u, 0, 1); break;
         }
-    } else hs_block<NI, MODE, SPLIT, IO16, false, BF>(p, smem, img, tile0, ntile, 0, 0, 0, 0, 0u, 0, 1);
+    } else hs_block<NI, MODE, SPLIT, IO16, false, BF, MX>(p, smem, img, tile0, ntile, 0, 0, 0, 0, 0u, 0, 1);
 }
 
 // The sub-rectangle form.  The reference's observation (game.py:215-257) is one background pixel (0, WALL, 0) everywhere
@@ -831,7 +957,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_f16s(ConvHsArgs p)
 // per staging item and per shortcut row when the block sets up its addresses).  Blocks take (image, rectangle, tile range,
 // bounding box) from descriptors written by k_rect_plan; the M-tile count of a block selects the body at run time
 // (wave-uniform), so one launch covers every rectangle shape of the batch.
-template <int MODE, bool SPLIT = true, int IO16 = 0, bool BF = false>
+template <int MODE, bool SPLIT = true, int IO16 = 0, bool BF = false, bool MX = false>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_f16s_rect(ConvHsArgs p)
 {
     __shared__ __align__(16) unsigned char smem[HS_SMEM];
@@ -840,10 +966,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_f16s_rect(ConvHsArgs p)
     if ((int)blockIdx.x >= nd) return;
     const int img = (int)d.x, ry0 = d.y & 255, rx0 = (d.y >> 8) & 255, rh = (d.y >> 16) & 255, rw = d.y >> 24;
     const int tile0 = d.z & 255, ntile = (d.z >> 8) & 255, part = (d.z >> 16) & 255, parts = d.z >> 24;
-#define HS_RECT_CASE(NI_) case NI_: hs_block<NI_, MODE, SPLIT, IO16, true, BF>(p, smem, img, tile0, ntile, ry0, rx0, rh, rw, d.w, part, parts); break;
+#define HS_RECT_CASE(NI_) case NI_: hs_block<NI_, MODE, SPLIT, IO16, true, BF, MX>(p, smem, img, tile0, ntile, ry0, rx0, rh, rw, d.w, part, parts); break;
     switch (ntile) {
         HS_RECT_CASE(1) HS_RECT_CASE(2) HS_RECT_CASE(3) HS_RECT_CASE(4) HS_RECT_CASE(5) HS_RECT_CASE(6) HS_RECT_CASE(7)
-    default: hs_block<8, MODE, SPLIT, IO16, true, BF>(p, smem, img, tile0, ntile, ry0, rx0, rh, rw, d.w, part, parts); break;
+    default: hs_block<8, MODE, SPLIT, IO16, true, BF, MX>(p, smem, img, tile0, ntile, ry0, rx0, rh, rw, d.w, part, parts); break;
     }
 #undef HS_RECT_CASE
 }
@@ -928,6 +1054,73 @@ __global__ void k_a16_weights(const float *__restrict__ w, _Float16 *__restrict_
         const float val = w[(long)(tap * HS_C + cin) * HS_C + cout] * mul;
         wS[(long)v * 8 + j] = BF ? __builtin_bit_cast(_Float16, (__bf16)val) : (_Float16)val;
     }
+}
+
+// the mxfp8 tower's weight image (snk_conv3x3_prepare_weights_mxfp8), quantized by the MX rule (see mx_scale_byte) from the float32
+// kernel: e4m3fn codes [step 18 = (chunk of 64 input channels) x 9 + tap][wn 4][half p 2][lane 64] x 16 bytes -- lane (h, r) of wave wn
+// holds input channels 64 chunk + 32 p + 16 h + 0..15 of output channel 32 wn + r in half p: the MFMA takes bytes 16 b .. 16 b + 15 of
+// BOTH lane halves as its k-block b, whose scale comes from lane (b, r) -- then the blocks' scale bytes [step][wn][lane] (lane (h, r):
+// block h), then at the 16-bit images' tail offset {1, 1, 1, 1, flag 0, 0, guard 0}: the MFMA applies the scales, the epilogue
+// has nothing to undo.  One thread per (step, output channel): its two blocks.
+__global__ __launch_bounds__(256) void k_mxfp8_weights(const float *__restrict__ w, unsigned char *__restrict__ wS)
+{
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= 18 * 128) return;
+    const int g = v >> 7, wn = (v >> 5) & 3, r = v & 31;
+    const int c = g / 9, tap = g - 9 * c, cout = 32 * wn + r;
+    const float *src = w + (long)(tap * HS_C + 64 * c) * HS_C + cout;         // input channel 64 c + i: src[i * HS_C]
+    unsigned sb[2];
+    float k[2];
+    for (int b = 0; b < 2; ++b) {
+        float m = 0.f;
+        for (int j = 0; j < 32; ++j) m = fmaxf(m, fabsf(src[(32 * b + j) * HS_C]));
+        sb[b] = mx_scale_byte(m);
+        k[b] = mx_inv_scale(sb[b]);
+    }
+    for (int h = 0; h < 2; ++h)
+        for (int pp = 0; pp < 2; ++pp) {
+            const float *s_ = src + (32 * pp + 16 * h) * HS_C;
+            unsigned q[4];
+            for (int j = 0; j < 4; ++j)
+                q[j] = mx_pack4(s_[(4 * j) * HS_C] * k[pp], s_[(4 * j + 1) * HS_C] * k[pp], s_[(4 * j + 2) * HS_C] * k[pp],
+                                s_[(4 * j + 3) * HS_C] * k[pp]);
+            *(uint4 *)(wS + ((long)((g * 4 + wn) * 2 + pp) * 64 + 32 * h + r) * 16) = make_uint4(q[0], q[1], q[2], q[3]);
+        }
+    for (int h = 0; h < 2; ++h) wS[9 * HS_C * HS_C + (g * 4 + wn) * 64 + 32 * h + r] = (unsigned char)sb[h];
+    if (v < 8) ((float *)(wS + 2 * HS_WS_ELEMS))[v] = v < 4 ? 1.0f : 0.0f;
+}
+
+// the staging path's quantizer on a plain bf16 array, for the tests: block b = x[32 b .. 32 b + 31] -> codes[32 b ..], scales[b];
+// four lanes per block as in staging (mx_quant8); lanes past the last block repeat it (every lane runs the quad's DPP steps)
+__global__ __launch_bounds__(256) void k_mxfp8_quantize(const _Float16 *__restrict__ x, long n_blocks, unsigned char *__restrict__ codes,
+                                                        unsigned char *__restrict__ scales)
+{
+    const long t = (long)blockIdx.x * 256 + threadIdx.x, b = t >> 2, bc = b < n_blocks ? b : n_blocks - 1;
+    const int q = (int)(t & 3);
+    unsigned sb;
+    const uint2 c = mx_quant8(*(const f16x8 *)(x + bc * 32 + 8 * q), sb);
+    if (b < n_blocks) {
+        *(uint2 *)(codes + b * 32 + 8 * q) = c;
+        if (q == 0) scales[b] = (unsigned char)sb;
+    }
+}
+
+extern "C" int snk_conv3x3_prepare_weights_mxfp8(const float *d_w_hwio, void *d_wS, void *stream)
+{
+    SNK_REQUIRE(d_w_hwio && d_wS, "snk_conv3x3_prepare_weights_mxfp8: NULL argument");
+    k_mxfp8_weights<<<9, 256, 0, (hipStream_t)stream>>>(d_w_hwio, (unsigned char *)d_wS);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_mxfp8_quantize_bf16(const void *d_x, int n_blocks, void *d_codes, void *d_scales, void *stream)
+{
+    SNK_REQUIRE(d_x && d_codes && d_scales, "snk_mxfp8_quantize_bf16: NULL argument");
+    SNK_REQUIRE(n_blocks > 0 && n_blocks <= (1 << 28), "snk_mxfp8_quantize_bf16: %d blocks", n_blocks);
+    k_mxfp8_quantize<<<(int)(((long)n_blocks * 4 + 255) / 256), 256, 0, (hipStream_t)stream>>>((const _Float16 *)d_x, n_blocks,
+                                                                                             (unsigned char *)d_codes, (unsigned char *)d_scales);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 // ---- the guard word: one device int32 that every layer of a net reports clamps to ----------------------------------------------
@@ -1082,7 +1275,7 @@ static int conv_f16s_launch(const float *d_x, const void *d_wS, const float *d_s
                             const float *d_center = nullptr, float *d_stat_part = nullptr, int *grid_out = nullptr, bool bf = false,
                             const float *d_gy = nullptr, const unsigned char *d_gmask = nullptr, const float *d_ginv = nullptr,
                             const float *d_aff_scale = nullptr, const float *d_aff_shift = nullptr, float *d_amax_part = nullptr,
-                            const unsigned char *d_res_mask = nullptr)
+                            const unsigned char *d_res_mask = nullptr, bool mx = false)
 {
     SNK_REQUIRE(n_images >= 0 && height >= 1 && width >= 3, "snk_conv3x3_bn_f16s: bad shape %d x %d x %d", n_images, height, width);
     SNK_REQUIRE(d_out != d_x, "snk_conv3x3_bn_f16s: in-place convolution is not possible (blocks read their neighbours' input rows)");
@@ -1174,7 +1367,9 @@ static int conv_f16s_launch(const float *d_x, const void *d_wS, const float *d_s
     // takes the generic version
     if (!split && io16) {        // f16 activations in HBM (io16: 1 = f16 in, f32 out; 3 = f16 in and out)
 #define HS_LAUNCH_IO4(NI_, MODE_)                                                               \
-        if (bf && io16 == 3) k_conv3x3_f16s<NI_, MODE_, false, 3, true><<<grid, 256, 0, st>>>(a); \
+        if (mx && io16 == 3) k_conv3x3_f16s<NI_, MODE_, false, 3, true, true><<<grid, 256, 0, st>>>(a); \
+        else if (mx) k_conv3x3_f16s<NI_, MODE_, false, 1, true, true><<<grid, 256, 0, st>>>(a); \
+        else if (bf && io16 == 3) k_conv3x3_f16s<NI_, MODE_, false, 3, true><<<grid, 256, 0, st>>>(a); \
         else if (bf) k_conv3x3_f16s<NI_, MODE_, false, 1, true><<<grid, 256, 0, st>>>(a);       \
         else if (io16 == 3) k_conv3x3_f16s<NI_, MODE_, false, 3><<<grid, 256, 0, st>>>(a);      \
         else k_conv3x3_f16s<NI_, MODE_, false, 1><<<grid, 256, 0, st>>>(a);
@@ -1187,11 +1382,13 @@ static int conv_f16s_launch(const float *d_x, const void *d_wS, const float *d_s
         break;
         if (d_w1x1) {            // the tower's last layer with the head's 1x1 stage in its epilogue: no layer output
             SNK_REQUIRE(io16 == 1 && relu && d_residual && !d_out && d_h1, "snk_conv3x3_bn_*_act16_head: the fused head closes a residual block");
-#define HS_LAUNCH_HEAD(NI_) case NI_: if (bf) k_conv3x3_f16s<NI_, 3, false, 1, true><<<grid, 256, 0, st>>>(a); \
+#define HS_LAUNCH_HEAD(NI_) case NI_: if (mx) k_conv3x3_f16s<NI_, 3, false, 1, true, true><<<grid, 256, 0, st>>>(a); \
+                                      else if (bf) k_conv3x3_f16s<NI_, 3, false, 1, true><<<grid, 256, 0, st>>>(a); \
                                       else k_conv3x3_f16s<NI_, 3, false, 1><<<grid, 256, 0, st>>>(a); break;
             switch (n_mt) {
                 HS_LAUNCH_HEAD(1) HS_LAUNCH_HEAD(2) HS_LAUNCH_HEAD(3) HS_LAUNCH_HEAD(4) HS_LAUNCH_HEAD(5) HS_LAUNCH_HEAD(6) HS_LAUNCH_HEAD(7)
-            default: if (bf) k_conv3x3_f16s<8, 3, false, 1, true><<<grid, 256, 0, st>>>(a);
+            default: if (mx) k_conv3x3_f16s<8, 3, false, 1, true, true><<<grid, 256, 0, st>>>(a);
+                     else if (bf) k_conv3x3_f16s<8, 3, false, 1, true><<<grid, 256, 0, st>>>(a);
                      else k_conv3x3_f16s<8, 3, false, 1><<<grid, 256, 0, st>>>(a); break;
             }
 #undef HS_LAUNCH_HEAD
@@ -1418,7 +1615,7 @@ extern "C" int snk_conv_rect_plan_act16(const float *d_planes, float b0, float b
 static int conv_f16s_rect_launch(const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
                                  const float *d_residual, float *d_out, const void *d_desc, const int *d_count,
                                  const float *d_bg_in, int grow_in, const float *d_bg_res, int grow_res, const float *d_bg_out,
-                                 int n_images, int height, int width, bool act16, void *stream, bool bf = false)
+                                 int n_images, int height, int width, bool act16, void *stream, bool bf = false, bool mx = false)
 {
     SNK_REQUIRE(grow_in >= 0 && grow_in < 128 && grow_res >= 0 && grow_res < 128, "snk_conv3x3_bn_f16s_rect: grow_in %d, grow_res %d", grow_in, grow_res);
     SNK_REQUIRE(d_x && d_wS && d_scale && d_shift && d_out && d_desc && d_count, "snk_conv3x3_bn_f16s_rect: NULL argument");
@@ -1430,7 +1627,10 @@ static int conv_f16s_rect_launch(const float *d_x, const void *d_wS, const float
     ConvHsArgs a = {d_x, (const f16x8 *)d_wS, (const float *)((const _Float16 *)d_wS + HS_WS_ELEMS), d_scale, d_shift,
                     d_residual, d_out, nullptr, nullptr, 0.f, 0.f, height, width, 1, 0, 0, 1, 0, nullptr, nullptr,
                     (const uint4 *)d_desc, d_count, d_bg_out, d_bg_in, d_residual ? d_bg_res : nullptr, grow_in, grow_res, nullptr, nullptr, nullptr};
-    if (act16 && bf) {
+    if (act16 && mx) {
+        if (d_residual) k_conv3x3_f16s_rect<2, false, 3, true, true><<<(int)mb, 256, 0, (hipStream_t)stream>>>(a);
+        else k_conv3x3_f16s_rect<1, false, 3, true, true><<<(int)mb, 256, 0, (hipStream_t)stream>>>(a);
+    } else if (act16 && bf) {
         if (d_residual) k_conv3x3_f16s_rect<2, false, 3, true><<<(int)mb, 256, 0, (hipStream_t)stream>>>(a);
         else k_conv3x3_f16s_rect<1, false, 3, true><<<(int)mb, 256, 0, (hipStream_t)stream>>>(a);
     } else if (act16) {
@@ -1623,6 +1823,42 @@ extern "C" int snk_conv3x3_bn_bf16_act16_head(const void *d_x16, const void *d_w
     SNK_REQUIRE(d_x16 && d_wS && d_scale && d_shift && d_residual16 && d_w1x1 && d_h1, "snk_conv3x3_bn_bf16_act16_head: NULL argument");
     return conv_f16s_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, nullptr, d_w1x1, bn_scale,
                             bn_shift, d_h1, n_images, height, width, 1, false, stream, 1, nullptr, nullptr, nullptr, true);
+}
+
+// The mxfp8 tower (SNK_CONV_ALGO=mxfp8): the bf16 tower's arguments, activations and epilogue; the MFMA operands are MX-FP8 (the
+// rule above mx_scale_byte): every 32-channel block of a staged pixel is quantized on its way into LDS, the weights once by
+// snk_conv3x3_prepare_weights_mxfp8, and each tap's 128 input channels go through two v_mfma_scale_f32_32x32x64_f8f6f4.
+extern "C" int snk_conv3x3_bn_mxfp8_act16(const void *d_x16, const void *d_wS, const float *d_scale, const float *d_shift,
+                                          const void *d_residual16, void *d_out, int out_bf16, int n_images, int height, int width,
+                                          int relu, void *stream)
+{
+    SNK_REQUIRE(d_x16 && d_wS && d_scale && d_shift && d_out, "snk_conv3x3_bn_mxfp8_act16: NULL argument");
+    SNK_REQUIRE(n_images > 0, "snk_conv3x3_bn_mxfp8_act16: %d images", n_images);
+    return conv_f16s_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, (float *)d_out, nullptr, 0.f,
+                            0.f, nullptr, n_images, height, width, relu, false, stream, out_bf16 ? 3 : 1, nullptr, nullptr, nullptr, true,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true);
+}
+
+extern "C" int snk_conv3x3_bn_mxfp8_act16_rect(const void *d_x16, const void *d_wS, const float *d_scale, const float *d_shift,
+                                               const void *d_residual16, void *d_out16, const void *d_desc, const int *d_count,
+                                               const void *d_bg_in16, int grow_in, const void *d_bg_res16, int grow_res,
+                                               const void *d_bg_out16, int n_images, int height, int width, void *stream)
+{
+    SNK_REQUIRE(n_images > 0, "snk_conv3x3_bn_mxfp8_act16_rect: %d images", n_images);
+    return conv_f16s_rect_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, (float *)d_out16, d_desc,
+                                 d_count, (const float *)d_bg_in16, grow_in, (const float *)d_bg_res16, grow_res,
+                                 (const float *)d_bg_out16, n_images, height, width, true, stream, true, true);
+}
+
+extern "C" int snk_conv3x3_bn_mxfp8_act16_head(const void *d_x16, const void *d_wS, const float *d_scale, const float *d_shift,
+                                               const void *d_residual16, const float *d_w1x1, float bn_scale, float bn_shift,
+                                               float *d_h1, int n_images, int height, int width, void *stream)
+{
+    SNK_REQUIRE(d_x16 && d_wS && d_scale && d_shift && d_residual16 && d_w1x1 && d_h1, "snk_conv3x3_bn_mxfp8_act16_head: NULL argument");
+    SNK_REQUIRE(n_images > 0, "snk_conv3x3_bn_mxfp8_act16_head: %d images", n_images);
+    return conv_f16s_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, nullptr, d_w1x1, bn_scale,
+                            bn_shift, d_h1, n_images, height, width, 1, false, stream, 1, nullptr, nullptr, nullptr, true,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true);
 }
 
 // The training step's INPUT-GRADIENT convolution with the next batch-norm backward's sums in its epilogue: d_out = conv3x3_same(d_x,

@@ -6,7 +6,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SNK_LIB_PATH") or os.path.join(_HERE, "libsnake_engine.so")      # SNK_LIB_PATH: a variant build (A/B runs)
 
 MAX_SNAKES, MAX_CELLS, MAX_NODES = 8, 361, 384
-ABI_VERSION = 112        # SNK_ABI_VERSION of include/snake_engine.h these prototypes were written against
+ABI_VERSION = 113        # SNK_ABI_VERSION of include/snake_engine.h these prototypes were written against
 
 
 class EngineError(RuntimeError):
@@ -68,6 +68,11 @@ PROTOTYPES = {
     "snk_conv3x3_bn_bf16_act16_rect": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp]),
     "snk_stem_conv_bn_relu_bf16out": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "snk_stem_conv_bn_relu_bf16out_rect": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "snk_conv3x3_prepare_weights_mxfp8": (i32, [vp, vp, vp]),
+    "snk_conv3x3_bn_mxfp8_act16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "snk_conv3x3_bn_mxfp8_act16_rect": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp]),
+    "snk_conv3x3_bn_mxfp8_act16_head": (i32, [vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, i32, i32, i32, vp]),
+    "snk_mxfp8_quantize_bf16": (i32, [vp, i32, vp, vp, vp]),
     "snk_conv3x3_prepare_weights_winograd": (i32, [vp, vp, vp]),
     "snk_conv3x3_bn_f32_winograd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "snk_conv3x3_prepare_weights_f16s": (i32, [vp, vp, C.c_float, vp]),

@@ -140,13 +140,14 @@ class QNet:
         self.conv_algo = os.environ.get("SNK_CONV_ALGO", "f16s")
         # "f16a": "f16" with the tower's activations stored as f16 in HBM (half the traffic; the f16 form with float32
         # activations is HBM-bound); "bf16": the same block body on bf16 -- bf16 activations in HBM, bf16 weights,
-        # v_mfma_f32_32x32x16_bf16: BASELINE configs[4]'s "bf16 MFMA conv" as it is worded
-        if self.conv_algo not in ("f16s", "winograd", "direct", "bf16", "f16", "f16a"):
-            raise EngineError(f"SNK_CONV_ALGO={self.conv_algo!r}: expected f16s, winograd, direct, f16, f16a or bf16")
+        # v_mfma_f32_32x32x16_bf16: BASELINE configs[4]'s "bf16 MFMA conv" as it is worded; "mxfp8": the bf16 tower with MX-FP8
+        # MFMA operands (bf16 activations in HBM, quantized per 32-channel block on their way into LDS; v_mfma_scale_f32_32x32x64_f8f6f4)
+        if self.conv_algo not in ("f16s", "winograd", "direct", "bf16", "f16", "f16a", "mxfp8"):
+            raise EngineError(f"SNK_CONV_ALGO={self.conv_algo!r}: expected f16s, winograd, direct, f16, f16a, bf16 or mxfp8")
         # sub-rectangle form of the first tower layers (snk_conv3x3_bn_f16s_rect): SNK_CONV_RECT=0 switches it off,
         # SNK_CONV_RECT_LAYERS=n fixes the number of layers that use it
-        self.rect = self.conv_algo in ("f16s", "f16a", "bf16") and os.environ.get("SNK_CONV_RECT", "1") != "0"
-        self.act16 = {"f16a": torch.float16, "bf16": torch.bfloat16}.get(self.conv_algo)      # 16-bit activations in HBM
+        self.rect = self.conv_algo in ("f16s", "f16a", "bf16", "mxfp8") and os.environ.get("SNK_CONV_RECT", "1") != "0"
+        self.act16 = {"f16a": torch.float16, "bf16": torch.bfloat16, "mxfp8": torch.bfloat16}.get(self.conv_algo)      # 16-bit activations in HBM
         self.background = BACKGROUND_PIXEL
         self.guard_trips = 0         # batches forward_guarded evaluated again after a clamp
         self.rect_tiles = None       # set to [] to collect every chunk's (images, per-layer GEMM tiles) device tensors
@@ -179,7 +180,7 @@ class QNet:
         # the split-f16 weight images of all layers are rows of ONE buffer, so that the layers' range flags (a word in each
         # image's tail) come to the host with one strided copy (range_flags)
         self._wimg = None
-        if self.conv_algo in ("f16s", "f16", "f16a", "bf16") and self.blocks:
+        if self.conv_algo in ("f16s", "f16", "f16a", "bf16", "mxfp8") and self.blocks:
             self._wimg = torch.empty((2 * self.blocks, F16S_WEIGHT_BYTES), dtype=torch.uint8, device=dev)
             self._flags_host = torch.empty((2 * self.blocks,), dtype=torch.int32).pin_memory()
             if self._guard is None:      # ONE device word every layer of this net reports a clamp to, and its pinned host mirror
@@ -190,6 +191,10 @@ class QNet:
                 self.conv_x_scale[i] = 1.0
                 wT = self._wimg[i]
                 check(self.L.snk_conv3x3_prepare_weights_bf16(t[base].contiguous().data_ptr(), wT.data_ptr(), st))
+            elif self.conv_algo == "mxfp8":                  # codes + block scales from the float32 kernel, quantized once here
+                self.conv_x_scale[i] = 1.0
+                wT = self._wimg[i]
+                check(self.L.snk_conv3x3_prepare_weights_mxfp8(t[base].contiguous().data_ptr(), wT.data_ptr(), st))
             elif self.conv_algo == "f16a":
                 self.conv_x_scale[i] = 1.0                   # f16 activations are staged as they are
                 wT = self._wimg[i]
@@ -204,7 +209,7 @@ class QNet:
             else:
                 wT = torch.empty(9 * 128 * 128, dtype=torch.float32, device=dev)
                 check(self.L.snk_conv3x3_prepare_weights(t[base].contiguous().data_ptr(), wT.data_ptr(), st))
-            if self._wimg is not None and self.conv_algo != "bf16":
+            if self._wimg is not None and self.conv_algo not in ("bf16", "mxfp8"):
                 check(self.L.snk_conv3x3_f16s_set_guard_word(wT.data_ptr(), self._guard[0].data_ptr(), st))
             sc, sh = fold(*t[base + 1:base + 5])
             self.conv_wT.append(wT); self.conv_sc.append(sc); self.conv_sh.append(sh)
@@ -391,6 +396,9 @@ class QNet:
         if self.conv_algo == "bf16":
             return (L.snk_stem_conv_bn_relu_bf16out, L.snk_stem_conv_bn_relu_bf16out_rect, L.snk_conv3x3_bn_bf16_act16,
                     L.snk_conv3x3_bn_bf16_act16_rect, L.snk_conv3x3_bn_bf16_act16_head)
+        if self.conv_algo == "mxfp8":          # the bf16 tower's stem (bf16 activations); its layers with MX-FP8 MFMA operands
+            return (L.snk_stem_conv_bn_relu_bf16out, L.snk_stem_conv_bn_relu_bf16out_rect, L.snk_conv3x3_bn_mxfp8_act16,
+                    L.snk_conv3x3_bn_mxfp8_act16_rect, L.snk_conv3x3_bn_mxfp8_act16_head)
         return (L.snk_stem_conv_bn_relu_f16out, L.snk_stem_conv_bn_relu_f16out_rect, L.snk_conv3x3_bn_f16_act16,
                 L.snk_conv3x3_bn_f16_act16_rect, L.snk_conv3x3_bn_f16_act16_head)
 

@@ -50,10 +50,11 @@ typedef struct {
 } snk_game_state;
 
 const char *snk_last_error(void);
-#define SNK_ABI_VERSION 112 /* 100: rounds 1-3; 110: round 5 (the gate argument d_skip of the tick kernels, round 4; the 16-bit
+#define SNK_ABI_VERSION 113 /* 100: rounds 1-3; 110: round 5 (the gate argument d_skip of the tick kernels, round 4; the 16-bit
                              * towers' own weight image and rectangle plan, round 5); 111: the training step's deferred batch
                              * norm (fifteen entry points added, snk_conv3x3_stats_partials returns more); 112: round 6,
-                             * snk_engine_import_at_sync and snk_engine_observe_rows added: a caller compares it with snk_version() */
+                             * snk_engine_import_at_sync and snk_engine_observe_rows added; 113: the MX-FP8 tower's five entry
+                             * points: a caller compares it with snk_version() */
 int snk_version(void);
 
 /* ---- engine lifetime -------------------------------------------------------------------
@@ -322,6 +323,36 @@ int snk_stem_conv_bn_relu_bf16out(const float *d_x, const float *d_w, const floa
 int snk_stem_conv_bn_relu_bf16out_rect(const float *d_x, const float *d_w, const float *d_scale, const float *d_shift,
                                        void *d_out16, const void *d_bbox, int grow, int n_images, int height, int width,
                                        void *stream);
+/* The MX-FP8 tower (SNK_CONV_ALGO=mxfp8; reduced precision, never the default): the bf16 tower with block-scaled FP8 MFMA
+ * operands.  Activations stay bf16 in HBM (the same buffers, stem, shortcut and head as the bf16 tower); each tap's 128 input
+ * channels go through two v_mfma_scale_f32_32x32x64_f8f6f4; accumulation, batch norm, shortcut and ReLU are float32.
+ * THE QUANTIZATION RULE (every entry point below uses it):
+ *   block: for activations, the 32 input channels 32j .. 32j+31 of one pixel; for weights, the same 32 input channels of one
+ *          (output channel, tap);
+ *   amax:  the largest |v| of the block in float32 (bf16 values are exact there; weights are taken from their float32 values);
+ *   E:     the smallest integer with amax * 2^-E <= 448, clamped to [-127, 127]; amax == 0 gives E = -127 and all codes zero;
+ *          the stored scale byte (E8M0) is E + 127;
+ *   codes: OCP e4m3fn, round to nearest even of v * 2^-E, subnormals kept; by the choice of E nothing saturates.
+ * There is no range to guard (no activation scale, no clamp, no range flag), as for bf16.
+ * snk_conv3x3_prepare_weights_mxfp8: the float32 HWIO kernel -> codes and scale bytes in fragment order, in a
+ *   SNK_CONV_F16S_WEIGHT_BYTES buffer (the first 152 064 bytes and the tail are used).
+ * snk_conv3x3_bn_mxfp8_act16 / _rect / _head: argument for argument snk_conv3x3_bn_bf16_act16 / _rect / _head (bf16 inputs,
+ *   shortcut and background images; bf16 or float32 output; the rectangle plan is snk_conv_rect_plan_act16's -- the block
+ *   frame's geometry is the 16-bit towers').  n_images must be >= 1.
+ * snk_mxfp8_quantize_bf16: the staging path's quantizer on a bf16 array of n_blocks blocks of 32 values: d_codes gets
+ *   32 * n_blocks e4m3fn bytes, d_scales n_blocks scale bytes (for tests). */
+int snk_conv3x3_prepare_weights_mxfp8(const float *d_w_hwio, void *d_wS, void *stream);
+int snk_conv3x3_bn_mxfp8_act16(const void *d_x16, const void *d_wS, const float *d_scale, const float *d_shift,
+                               const void *d_residual16, void *d_out, int out_bf16, int n_images, int height, int width,
+                               int relu, void *stream);
+int snk_conv3x3_bn_mxfp8_act16_rect(const void *d_x16, const void *d_wS, const float *d_scale, const float *d_shift,
+                                    const void *d_residual16, void *d_out16, const void *d_desc, const int *d_count,
+                                    const void *d_bg_in16, int grow_in, const void *d_bg_res16, int grow_res,
+                                    const void *d_bg_out16, int n_images, int height, int width, void *stream);
+int snk_conv3x3_bn_mxfp8_act16_head(const void *d_x16, const void *d_wS, const float *d_scale, const float *d_shift,
+                                    const void *d_residual16, const float *d_w1x1, float bn_scale, float bn_shift,
+                                    float *d_h1, int n_images, int height, int width, void *stream);
+int snk_mxfp8_quantize_bf16(const void *d_x, int n_blocks, void *d_codes, void *d_scales, void *stream);
 int snk_head_dense_f32(const float *d_h1, const float *d_fc1_w, const float *d_fc1_b, const float *d_fc2_w,
                        const float *d_fc2_b, const uint8_t *d_mask, float *d_q, int n_images, int height, int width,
                        void *stream);

@@ -42,7 +42,7 @@ for name in ("gen-0 Glorot (bench net)", "randomised BN"):
                 k += 1
     ref = forward64(ws, states)
     line = f"{name:28s} max|Q| {np.abs(ref).max():.3f}:"
-    for algo in ("direct", "winograd", "f16s"):
+    for algo in ("direct", "winograd", "f16s") + tuple(sys.argv[1:]):      # e.g. net_accuracy.py bf16 mxfp8: the reduced-precision towers too
         os.environ["SNK_CONV_ALGO"] = algo
         q = net.QNet(ws, (21, 21, 3)).forward(torch.as_tensor(states, device="cuda")).cpu().numpy().astype(np.float64)
         line += f"  {algo} {np.abs(q - ref).max():.2e}"
