@@ -59,6 +59,8 @@ template <bool BF> __device__ __forceinline__ _Float16 hs_to16(float v)
 #define HS_KC 16                                         // input channels per chunk = one MFMA k step
 #define HS_LDP 80                                        // bytes per LDS pixel: [hi k0-15 | lo k0-15] + 16 (16 x odd: conflict-free b128)
 #define HS_NPB 352                                       // pixels per LDS buffer
+#define HS_NPB_PK 416                                    // the same in the packed sub-rectangle form (PK below): the block's LDS is the
+                                                         //   epilogue's 67 584 bytes anyway, and two strips carry four halo rows
 #define HS_MLD 132                                       // epilogue row (floats): 528 bytes = 16 x 33
 #define HS_SMEM_STAGE (2 * HS_BUF16)                     // 65 536 bytes (split form: 2 x 352 x 80 = 56 320)
 #define HS_SMEM_EPI (2 * 64 * HS_MLD * 4)                // 67 584 bytes
@@ -245,11 +247,20 @@ __device__ __forceinline__ uint2 mx_quant8(const f16x8 v, unsigned &sbyte)
 //   ds_read_b128 at +16 h and +32 + 16 h -- and the scale byte of block h; B likewise from k_mxfp8_weights' image.  Per (tile,
 //   tap) the bf16 form issues 2 MFMAs of 32 cycles in each of 4 chunks, this form 1 MFMA of 64 cycles in each of 2 chunks: a
 //   quarter of the MFMAs, half the MFMA time, half the chunks and barriers.
-template <int NI, int MODE, bool SPLIT, int IO16, bool RECT, bool BF = false, bool MX = false>
+// PK (with RECT, float32-accurate form only): the PACKED sub-rectangle form (k_rect_plan_pack below).  The images of a launch
+//   whose rectangles have the same shape share one GEMM row space, so a block's rows are up to TWO segments: pixels tile0 ..
+//   tile0 + ntile - 1 of image img's rectangle (here tile0 / ntile count ROWS, and the segment may start anywhere), then pixels
+//   0 .. nB - 1 of image imgB's rectangle (same shape, its own position ryB / rxB and bounding box).  Each segment has its own
+//   strip in LDS (A's rows first, B's behind them, same pitch); only the address set-up knows about segments -- the staging
+//   items, the lanes' pixel addresses, the epilogue's row map, the shortcut / background choice and the fill -- the chunk loop
+//   is the unpacked form's, and every GEMM row accumulates the same (chunk, tap, k) sequence whichever tile it sits in.
+template <int NI, int MODE, bool SPLIT, int IO16, bool RECT, bool BF = false, bool MX = false, bool PK = false>
 __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *smem, const int img, const int tile0, const int ntile,
                                          const int ry0, const int rx0, const int rh, const int rw, const unsigned bbox,
-                                         const int part, const int parts)
+                                         const int part, const int parts, const int imgB = 0, const int ryB = 0, const int rxB = 0,
+                                         const unsigned bboxB = 0u, const int nB = 0)
 {
+    static_assert(!PK || (RECT && SPLIT && IO16 == 0 && (MODE == 1 || MODE == 2)), "the packed form exists for the float32-accurate sub-rectangle layers only");
     static_assert(IO16 == 0 || !SPLIT, "f16 activations only exist in the reduced-precision form");
     static_assert(!BF || (IO16 & 1), "the bf16 form reads bf16 activations");
     static_assert(!MX || BF, "the mxfp8 form reads bf16 activations");
@@ -262,7 +273,7 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     constexpr int RING = K32 ? HS_RING16 : HS_RING, AHEAD = K32 ? HS_AHEAD16 : HS_AHEAD;      // B-fragment register ring: slots (a divisor of 9), taps ahead
     constexpr bool TWO = SPLIT || K32;                     // two A fragments / two B fragments per (tap, M tile)
     constexpr int KC = MX ? 64 : K32 ? 32 : HS_KC, NCHUNK = HS_C / KC;
-    constexpr int NST = K32 ? HS_NST16 : HS_NST, BUFB = K32 ? HS_BUF16 : HS_NPB * HS_LDP;
+    constexpr int NST = K32 ? HS_NST16 : HS_NST, BUFB = K32 ? HS_BUF16 : (PK ? HS_NPB_PK : HS_NPB) * HS_LDP;
     constexpr int PIECE = K32 ? 8 : 4;                     // channels of a staging item
     // MX: a 64-channel chunk is staged in two halves of 32 channels (one MX block per pixel each) with the 16-bit frame's items --
     // half 0 loaded at tap 0 and written from region MXR0 on, half 1 loaded at the start of tap MXT1 into the same registers and
@@ -287,7 +298,7 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     const int cy0 = RECT ? ry0 : 0, cx0 = RECT ? rx0 : 0;  // its origin on the canvas
     const int HW = RECT ? rh * rw : p.Hd * p.Wd;           // its pixels = GEMM rows
     const int HWc = p.Hd * p.Wd;                           // the canvas: what the tensors in HBM are pitched by
-    const int m0 = 32 * tile0, m1 = min(32 * (tile0 + ntile), HW);      // the block's GEMM rows = pixels m0 .. m1 - 1 of the image
+    const int m0 = PK ? tile0 : 32 * tile0, m1 = PK ? tile0 + ntile : min(32 * (tile0 + ntile), HW);   // the block's GEMM rows = pixels m0 .. m1 - 1 of the image (PK: its first segment's)
     const int P = RECT ? Wr + 2 : Wr + 1;                  // padded pitch (pixels)
     const int PB = K32 ? (RECT ? (Wr + 2) * HS_LDP + HS_GAP16_RECT : Wr * HS_LDP + HS_GAP16_FULL) : P * HS_LDP;   // LDS row pitch (bytes)
     const float invW = 1.0f / (float)Wr;
@@ -312,7 +323,34 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     const _Float16 *gp16[NST];                             //   (bounding box grown by grow_in), else in that layer's background image
     const int by0 = bbox & 255, bx0 = (bbox >> 8) & 255, by1 = (bbox >> 16) & 255, bx1 = bbox >> 24;
     const bool sel_in = RECT && p.bg_in != nullptr;
+    (void)imgB; (void)ryB; (void)rxB; (void)bboxB; (void)nB;
+    // PK: the second segment's strip (image rows -1 .. its last row + 1) sits behind the first one's RA rows
+    const int nA = m1 - m0, RA = y_last - y_first + 3;
+    const int yB_last = (int)(((float)max(nB - 1, 0) + 0.5f) * invW);
+    const int yaB = max(ryB - 1, 0), ybB = min(ryB + yB_last + 1, p.Hd - 1), xaB = max(rxB - 1, 0), xbB = min(rxB + Wr, p.Wd - 1);
+    const int ry_loB = RA + yaB - (ryB - 1), cx_loB = xaB - (rxB - 1), wsB = xbB - xaB + 1, npxB = nB > 0 ? (ybB - yaB + 1) * wsB : 0;
+    const int byB0 = bboxB & 255, bxB0 = (bboxB >> 8) & 255, byB1 = (bboxB >> 16) & 255, bxB1 = bboxB >> 24;
+    (void)nA; (void)RA; (void)ry_loB; (void)cx_loB; (void)npxB; (void)byB0; (void)bxB0; (void)byB1; (void)bxB1;
     // items past the strip's last pixel repeat it (same value to the same LDS address): no predication, no branches
+    if constexpr (PK) {
+        const float invWsB = 1.0f / (float)wsB;
+#pragma unroll
+        for (int k = 0; k < NST; ++k) {
+            const int pq_ = pix0 + 64 * k;
+            const bool sb_ = npxB > 0 && pq_ >= npx;          // the item belongs to the second strip
+            const int pix_ = sb_ ? min(pq_ - npx, npxB - 1) : min(pq_, npx - 1);
+            const int w_ = sb_ ? wsB : ws;
+            const int r_ = (int)(((float)pix_ + 0.5f) * (sb_ ? invWsB : invWs)), x_ = pix_ - r_ * w_;
+            ldo[k] = ((sb_ ? ry_loB : ry_lo) + r_) * PB + ((sb_ ? cx_loB : cx_lo) + x_) * HS_LDP + (tid & 3) * 8;
+            gof[k] = 0u;
+            const int Y = (sb_ ? yaB : ya) + r_, X = (sb_ ? xaB : xa) + x_;
+            const int y0_ = sb_ ? byB0 : by0, x0_ = sb_ ? bxB0 : bx0, y1_ = sb_ ? byB1 : by1, x1_ = sb_ ? bxB1 : bx1;
+            const bool stale = sel_in && (Y < y0_ - p.grow_in || Y > y1_ + p.grow_in || X < x0_ - p.grow_in || X > x1_ + p.grow_in);
+            const long o_ = (long)(Y * p.Wd + X) * HS_C + PIECE * (tid & 3);
+            gp[k] = (stale ? p.bg_in : p.x + (long)(sb_ ? imgB : img) * HWc * HS_C) + o_;
+            gp16[k] = nullptr;
+        }
+    } else
 #pragma unroll
     for (int k = 0; k < NST; ++k) {
         const int pix_ = min(pix0 + 64 * k, npx - 1);
@@ -443,6 +481,14 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     unsigned la[NI];                                       // LDS byte address (buffer 0, centre tap) of the lane's pixel in M tile i
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
+        if constexpr (PK) {                                // rows past the block's last pixel repeat it
+            const int r_ = 32 * i + l31;
+            const bool sb_ = nB > 0 && r_ >= nA;
+            const int m_ = sb_ ? min(r_ - nA, nB - 1) : min(m0 + r_, m1 - 1);
+            const int y_ = (int)(((float)m_ + 0.5f) * invW), x_ = m_ - y_ * Wr;
+            la[i] = (unsigned)((sb_ ? RA + y_ + 1 : y_ - (y_first - 1)) * PB + (x_ + 1) * HS_LDP) + 16 * h;
+            continue;
+        }
         const int m_ = min(m0 + 32 * i + l31, HW - 1);     // rows past the image repeat its last pixel (computed, never stored)
         const int y_ = (int)(((float)m_ + 0.5f) * invW), x_ = m_ - y_ * Wr;
         la[i] = (unsigned)((y_ - (y_first - 1)) * PB + (x_ + 1) * HS_LDP) + 16 * h;
@@ -800,7 +846,7 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     if (BARE && p.center) cen4 = *(const float4 *)(p.center + 4 * cq);
     float4 st_m = cen4;
     float *Ms = (float *)smem;                                      // [2][64 rows][HS_MLD]
-    const long obase = (long)img * HWc * HS_C + 4 * cq;
+    const long obase = (PK ? 0l : (long)img * HWc * HS_C) + 4 * cq;     // (PK: a row's offset carries its image)
     float4 wh = make_float4(0.f, 0.f, 0.f, 0.f);
     if (has_head) wh = *(const float4 *)(p.w1x1 + 4 * cq);
     constexpr int NPASS = (NI + 1) / 2;
@@ -813,7 +859,16 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     {                                                                                           \
         _Pragma("unroll") for (int j = 0; j < HS_ROWS(pass) / 8; ++j) {                         \
             const int m_ = m0 + 64 * (pass) + rr0 + 8 * j;                                      \
-            if (RECT) {                                                                         \
+            if (PK) {                         /* row -> (segment, pixel) -> address in the segment's image */ \
+                const int r_ = 64 * (pass) + rr0 + 8 * j;                                       \
+                const bool sb_ = r_ >= nA;                                                      \
+                const int mm_ = sb_ ? r_ - nA : m_;                                             \
+                const int y_ = (int)(((float)mm_ + 0.5f) * invW), x_ = mm_ - y_ * Wr;           \
+                const int Y_ = (sb_ ? ryB : cy0) + y_, X_ = (sb_ ? rxB : cx0) + x_;             \
+                off[(pass) & 1][j] = r_ < nA + nB ? (((sb_ ? imgB : img) * p.Hd + Y_) * p.Wd + X_) * HS_C : -1; \
+                res_stale[j] = r_ < nA + nB && sel_res && (Y_ < (sb_ ? byB0 : by0) - p.grow_res || Y_ > (sb_ ? byB1 : by1) + p.grow_res || \
+                                           X_ < (sb_ ? bxB0 : bx0) - p.grow_res || X_ > (sb_ ? bxB1 : bx1) + p.grow_res); \
+            } else if (RECT) {                                                                  \
                 const int y_ = (int)(((float)m_ + 0.5f) * invW), x_ = m_ - y_ * Wr;             \
                 off[(pass) & 1][j] = m_ < m1 ? ((cy0 + y_) * p.Wd + cx0 + x_) * HS_C : -1;      \
                 res_stale[j] = sel_res && (cy0 + y_ < by0 - p.grow_res || cy0 + y_ > by1 + p.grow_res || \
@@ -827,8 +882,10 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
                     const f16x4 r16_ = *(const f16x4 *)(rb_ + max(off[(pass) & 1][j], 0));      \
                     rv[(pass) & 1][j] = make_float4(hs_from16<BF>(r16_[0]), hs_from16<BF>(r16_[1]), hs_from16<BF>(r16_[2]), hs_from16<BF>(r16_[3])); \
                 } else {                                                                        \
+                    /* (PK: the row's offset carries its image, the background image is one canvas) */ \
+                    const int bgo_ = (PK && res_stale[j]) ? (64 * (pass) + rr0 + 8 * j >= nA ? imgB : img) * HWc * HS_C : 0; \
                     const float *rb_ = (RECT && res_stale[j]) ? p.bg_res + 4 * cq : p.res + obase; \
-                    rv[(pass) & 1][j] = *(const float4 *)(rb_ + max(off[(pass) & 1][j], 0));    \
+                    rv[(pass) & 1][j] = *(const float4 *)(rb_ + (max(off[(pass) & 1][j], 0) - bgo_));    \
                 }                                                                               \
             }                                                                                   \
         }                                                                                       \
@@ -910,7 +967,24 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
             *(float4 *)(p.stat_part + (size_t)blockIdx.x * 256 + rr0 * 128 + 4 * cq) = t;
         }
     }
-    if (RECT && p.bg_out) {
+    if (PK && p.bg_out) {
+        // the packed form: a segment with pixels m .. m + n - 1 of the HW of its rectangle fills the same share of its image's canvas,
+        // pixels ceil(m HWc / HW) .. ceil((m + n) HWc / HW) - 1: an image's segments tile its canvas, each does work in step with its rows
+        const float invF = 1.0f / (float)p.Wd;
+        for (int s = 0; s < 2; ++s) {
+            const int sm = s ? 0 : m0, sn = s ? nB : nA;
+            if (sn == 0) continue;
+            const int q_lo = (sm * HWc + HW - 1) / HW, q_hi = ((sm + sn) * HWc + HW - 1) / HW;
+            const int fy = s ? ryB : cy0, fx = s ? rxB : cx0;
+            float *ob = p.out + (long)(s ? imgB : img) * HWc * HS_C;
+            for (int q = q_lo + rr0; q < q_hi; q += 8) {
+                const int y_ = (int)(((float)q + 0.5f) * invF), x_ = q - y_ * p.Wd;
+                if (y_ >= fy && y_ < fy + rh && x_ >= fx && x_ < fx + rw) continue;
+                const int o_ = (y_ * p.Wd + x_) * HS_C + 4 * cq;
+                *(float4 *)(ob + o_) = *(const float4 *)(p.bg_out + o_);
+            }
+        }
+    } else if (RECT && p.bg_out) {
         // the layers that read this output are full layers: every pixel of the canvas outside the rectangle takes the layer's
         // state-independent background value; the image's parts share the pixels, 32 lanes per pixel
         const float invF = 1.0f / (float)p.Wd;
@@ -970,6 +1044,29 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_f16s_rect(ConvHsArgs p)
     switch (ntile) {
         HS_RECT_CASE(1) HS_RECT_CASE(2) HS_RECT_CASE(3) HS_RECT_CASE(4) HS_RECT_CASE(5) HS_RECT_CASE(6) HS_RECT_CASE(7)
     default: hs_block<8, MODE, SPLIT, IO16, true, BF, MX>(p, smem, img, tile0, ntile, ry0, rx0, rh, rw, d.w, part, parts); break;
+    }
+#undef HS_RECT_CASE
+}
+
+// The packed sub-rectangle form (float32-accurate tower): a block's descriptor is two uint4, one per segment --
+//   { image, y0 | x0 << 8 | h << 16 | w << 24, first pixel | pixels << 16, bounding box } and
+//   { image B, the same with B's position, pixels of B (0: one segment) | M tiles << 16, B's bounding box }
+// (a one-segment block repeats its image in the second word group, so that every 16-byte entry names an image and its rectangle);
+// *n_desc counts 16-byte entries.  Written by k_rect_plan_pack / k_rect_pack_resolve.
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void k_conv3x3_f16s_rectp(ConvHsArgs p)
+{
+    __shared__ __align__(16) unsigned char smem[HS_SMEM];
+    const int nd = *p.n_desc;
+    const uint4 dA = p.desc[2 * blockIdx.x], dB = p.desc[2 * blockIdx.x + 1];      // the grid never exceeds the array
+    if (2 * (int)blockIdx.x >= nd) return;
+    const int img = (int)dA.x, ry0 = dA.y & 255, rx0 = (dA.y >> 8) & 255, rh = (dA.y >> 16) & 255, rw = dA.y >> 24;
+    const int mA = dA.z & 0xFFFF, nA = dA.z >> 16, nB = dB.z & 0xFFFF, ntile = (dB.z >> 16) & 15;
+    const int imgB = (int)dB.x, ryB = dB.y & 255, rxB = (dB.y >> 8) & 255;
+#define HS_RECT_CASE(NI_) case NI_: hs_block<NI_, MODE, true, 0, true, false, false, true>(p, smem, img, mA, nA, ry0, rx0, rh, rw, dA.w, 0, 1, imgB, ryB, rxB, dB.w, nB); break;
+    switch (ntile) {
+        HS_RECT_CASE(1) HS_RECT_CASE(2) HS_RECT_CASE(3) HS_RECT_CASE(4) HS_RECT_CASE(5) HS_RECT_CASE(6) HS_RECT_CASE(7)
+    default: hs_block<8, MODE, true, 0, true, false, false, true>(p, smem, img, mA, nA, ry0, rx0, rh, rw, dA.w, 0, 1, imgB, ryB, rxB, dB.w, nB); break;
     }
 #undef HS_RECT_CASE
 }
@@ -1612,6 +1709,308 @@ extern "C" int snk_conv_rect_plan_act16(const float *d_planes, float b0, float b
     return rect_plan(d_planes, b0, b1, b2, n_images, height, width, n_layers, grow, d_bbox, d_desc, d_counts, stream, true);
 }
 
+
+// ---- the packed plan (float32-accurate tower) -------------------------------------------------------------------------
+// A rectangle of h x w pixels alone pads its rows to whole M tiles: 15 x 15 = 225 = 7 x 32 + 1 runs an eighth tile for one pixel.
+// Which pixels share a tile changes no result bit, so the images of a launch whose rectangles have the same SHAPE (the shape
+// fixes the LDS pitch and the tap offsets; the position may differ) are given one concatenated row space, and only its end is
+// padded.  The rule, stated once here for the device (k_rect_plan_pack), the host (snk_conv_rect_plan_pack_host) and the tests:
+//   bin      the images of a layer by (h, w), in any order;
+//   group    P = min(8, 32 / gcd(h w, 32)) consecutive images of a bin, the bin's last group whatever is left: groups are cut
+//            independently of each other, so equal groups are cut alike (one thread cuts a group: short groups keep the plan kernel
+//            short; 32 / gcd images would be a whole number of tiles, 8 images leave less than one tile of padding in 8 images);
+//   block    hs_pack_walk: a group of one image is cut like the unpacked plan cuts a rectangle (hs_rect_parts); otherwise from the group's first unassigned pixel, the longest run of 8, 7, .. 1 tiles (or up to the group's end)
+//            that touches at most two images and whose strips -- per segment its pixel rows, one above, one below, halo columns --
+//            fit the LDS buffer (HS_NPB_PK pixels together) and the staging items (64 HS_NST canvas pixels together); when not even
+//            one tile does (a tile would touch three images, or two strips are too wide), the block is the current image's next
+//            32 pixels or its rest alone, padded: what the unpacked plan does with a tile.
+// Blocks are ordered largest first over the whole layer, as in the unpacked plan.
+#define HS_PACK_BINS 4096                                // (h, w) bins of a canvas the packed plan takes: up to 64 x 64
+__host__ __device__ static inline bool hs_pack_fits(int wr, int Hd, int Wd, float inv, int m, int nA, int nB)
+{
+    const int yf = (int)(((float)m + 0.5f) * inv), yl = (int)(((float)(m + nA - 1) + 0.5f) * inv);
+    const int cols_in = wr + 2 < Wd ? wr + 2 : Wd;
+    int R = yl - yf + 3;
+    int st = (R < Hd ? R : Hd) * cols_in;
+    if (nB > 0) {
+        const int RB = (int)(((float)(nB - 1) + 0.5f) * inv) + 3;
+        R += RB;
+        st += (RB < Hd ? RB : Hd) * cols_in;
+    }
+    return R * (wr + 2) <= HS_NPB_PK && st <= 64 * HS_NST;
+}
+// images per group of shape (hr, wr)
+__host__ __device__ static inline int hs_pack_period(int S) { const int t = S | 32, P = 32 / (t & -t); return P < 8 ? P : 8; }
+// emit(i, m, nA, nB, ntile): a block = pixels m .. m + nA - 1 of the group's image i, then pixels 0 .. nB - 1 of image i + 1
+template <class F> __host__ __device__ static inline void hs_pack_walk(int hr, int wr, int Hd, int Wd, int q, F &&emit)
+{
+    const int S = hr * wr;
+    if (q == 1) {                             // nothing to share tiles with: the unpacked plan's equal parts
+        int tm;
+        const int parts = hs_rect_parts(hr, wr, Hd, Wd, &tm), T = (S + 31) / 32, base = T / parts, rem = T % parts;
+        for (int k = 0; k < parts; ++k) {
+            const int tile0 = k * base + (k < rem ? k : rem), ntile = base + (k < rem ? 1 : 0);
+            emit(0, 32 * tile0, 32 * (tile0 + ntile) < S ? 32 * ntile : S - 32 * tile0, 0, ntile);
+        }
+        return;
+    }
+    const float inv = 1.0f / (float)wr;
+    int i = 0, m = 0;
+    while (i < q) {
+        const int left = (q - i) * S - m;
+        const int rest = S - m;
+        int nA = rest < 32 ? rest : 32, nB = 0;
+        for (int n = 8; n >= 1; --n) {
+            const int rows = 32 * n < left ? 32 * n : left;
+            const int a_ = rows < rest ? rows : rest, b_ = rows - a_;
+            if (b_ <= S && hs_pack_fits(wr, Hd, Wd, inv, m, a_, b_)) { nA = a_; nB = b_; break; }
+        }
+        emit(i, m, nA, nB, (nA + nB + 31) / 32);
+        m += nA;
+        if (m == S) { ++i; m = nB; if (m == S) { ++i; m = 0; } }
+    }
+}
+
+// One workgroup per layer.  Images -> bins (shared-memory histogram, block scan, counting sort into d_order), then every group
+// is walked twice by one thread: once to count the blocks of each size (the descriptor array is ordered by size), once to write
+// them -- with the images still named by their place in d_order, which k_rect_pack_resolve (all layers, one thread per block)
+// turns into image, rectangle and bounding box: the walk itself waits for no load.
+__global__ __launch_bounds__(1024) void k_rect_plan_pack(const unsigned *__restrict__ bbox, int n, int Hd, int Wd, RectPlanArgs a,
+                                                         int *__restrict__ order_all)
+{
+    __shared__ int cnt[HS_PACK_BINS], cur[HS_PACK_BINS], gb[HS_PACK_BINS + 1];
+    __shared__ unsigned long long sc[1024];
+    __shared__ int cls[9], clscur[9], tiles_sum;
+    const int L = blockIdx.x, g = a.grow[L], tid = threadIdx.x, nb = Hd * Wd;
+    int *order = order_all + (long)L * n;
+    for (int b = tid; b < nb; b += 1024) cnt[b] = 0;
+    if (tid < 9) cls[tid] = 0;
+    if (tid == 0) tiles_sum = 0;
+    __syncthreads();
+#define HS_PACK_SHAPE(b_)                                                                       \
+        const int y0 = max((int)((b_) & 255) - g, 0), x0 = max((int)(((b_) >> 8) & 255) - g, 0); \
+        const int y1 = min((int)(((b_) >> 16) & 255) + g, Hd - 1), x1 = min((int)((b_) >> 24) + g, Wd - 1); \
+        const int hr = y1 - y0 + 1, wr = x1 - x0 + 1, bin = (hr - 1) * Wd + wr - 1;
+    for (int img = tid; img < n; img += 1024) {
+        const unsigned b = bbox[img];
+        HS_PACK_SHAPE(b)
+        (void)y0; (void)x0;
+        atomicAdd(&cnt[bin], 1);
+    }
+    __syncthreads();
+    // exclusive scan over the bins of (images, groups): K consecutive bins per thread
+    const int K = (nb + 1023) / 1024;
+    unsigned long long mine = 0;
+    for (int j = 0; j < K; ++j) {
+        const int b = tid * K + j;
+        if (b < nb && cnt[b] > 0) {
+            const int P = hs_pack_period((b / Wd + 1) * (b % Wd + 1));
+            mine += (unsigned long long)cnt[b] << 32 | (unsigned)((cnt[b] + P - 1) / P);
+        }
+    }
+    sc[tid] = mine;
+    __syncthreads();
+    for (int s = 1; s < 1024; s <<= 1) {
+        const unsigned long long v = tid >= s ? sc[tid - s] : 0ull;
+        __syncthreads();
+        sc[tid] += v;
+        __syncthreads();
+    }
+    {
+        unsigned long long e = sc[tid] - mine;
+        for (int j = 0; j < K; ++j) {
+            const int b = tid * K + j;
+            if (b < nb) {
+                cur[b] = (int)(e >> 32); gb[b] = (int)(e & 0xFFFFFFFFu);
+                if (cnt[b] > 0) {
+                    const int P = hs_pack_period((b / Wd + 1) * (b % Wd + 1));
+                    e += (unsigned long long)cnt[b] << 32 | (unsigned)((cnt[b] + P - 1) / P);
+                }
+            }
+        }
+    }
+    const int n_groups = (int)(sc[1023] & 0xFFFFFFFFu);
+    if (tid == 0) gb[nb] = n_groups;
+    __syncthreads();
+    for (int img = tid; img < n; img += 1024) {           // counting sort: the bin's images side by side (in the atomics' order)
+        const unsigned b = bbox[img];
+        HS_PACK_SHAPE(b)
+        (void)y0; (void)x0;
+        order[atomicAdd(&cur[bin], 1)] = img;
+    }
+#undef HS_PACK_SHAPE
+    // group gi -> its bin (the last b with gb[b] <= gi: empty bins share the value of the bin after them), place and size
+#define HS_PACK_GROUP(gi)                                                                       \
+        int lo_ = 0, hi_ = nb;                /* first index whose gb exceeds gi */                \
+        while (lo_ < hi_) { const int mid_ = (lo_ + hi_) >> 1; if (gb[mid_ + 1] > (gi)) hi_ = mid_; else lo_ = mid_ + 1; } \
+        const int bin = lo_, hr = bin / Wd + 1, wr = bin % Wd + 1, P = hs_pack_period(hr * wr);  \
+        const int rank0 = ((gi) - gb[bin]) * P, q = min(P, cnt[bin] - rank0);
+    int tiles = 0;
+    for (int gi = tid; gi < n_groups; gi += 1024) {
+        HS_PACK_GROUP(gi)
+        hs_pack_walk(hr, wr, Hd, Wd, q, [&](int, int, int, int, int nt) { atomicAdd(&cls[nt], 1); tiles += nt; });
+    }
+    atomicAdd(&tiles_sum, tiles);
+    __syncthreads();
+    if (tid == 0) {
+        int o = 0;
+        for (int nt = 8; nt >= 1; --nt) { clscur[nt] = o; o += cls[nt]; }
+        a.counts[2 * L] = 2 * o;
+        a.counts[2 * L + 1] = tiles_sum;
+    }
+    __syncthreads();
+    uint4 *desc = a.desc + (long)L * a.max_blocks;
+    for (int gi = tid; gi < n_groups; gi += 1024) {
+        HS_PACK_GROUP(gi)
+        const int first = cur[bin] - cnt[bin] + rank0;     // (the sort left cur at the bin's end)
+        hs_pack_walk(hr, wr, Hd, Wd, q, [&](int i, int m, int nA, int nB, int nt) {
+            const int slot = atomicAdd(&clscur[nt], 1);
+            desc[2 * slot] = make_uint4((unsigned)(first + i), 0u, (unsigned)m | (unsigned)nA << 16, 0u);
+            desc[2 * slot + 1] = make_uint4((unsigned)(first + i + (nB > 0 ? 1 : 0)), 0u, (unsigned)nB | (unsigned)nt << 16, 0u);
+        });
+    }
+#undef HS_PACK_GROUP
+}
+
+// places in d_order -> image, rectangle, bounding box: one thread per 16-byte entry of every layer
+__global__ __launch_bounds__(256) void k_rect_pack_resolve(const unsigned *__restrict__ bbox, int n, int Hd, int Wd, RectPlanArgs a,
+                                                           const int *__restrict__ order_all)
+{
+    const int L = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x, g = a.grow[L];
+    if (e >= a.counts[2 * L]) return;
+    uint4 *d = a.desc + (long)L * a.max_blocks + e;
+    const int img = order_all[(long)L * n + (int)d->x];
+    const unsigned b = bbox[img];
+    const int y0 = max((int)(b & 255) - g, 0), x0 = max((int)((b >> 8) & 255) - g, 0);
+    const int y1 = min((int)((b >> 16) & 255) + g, Hd - 1), x1 = min((int)(b >> 24) + g, Wd - 1);
+    d->x = (unsigned)img;
+    d->y = (unsigned)y0 | (unsigned)x0 << 8 | (unsigned)(y1 - y0 + 1) << 16 | (unsigned)(x1 - x0 + 1) << 24;
+    d->w = b;
+}
+
+// 16-byte descriptor entries per layer the packed plan may write for n_images observations: two per block, blocks per image at
+// most the worst ratio over every shape and group size (each bin's groups are cut alike, its last group is one of the sizes)
+static long rect_pack_max_desc(int n_images, int height, int width)
+{
+    if (n_images < 0 || height < 3 || width < 3 || height * width > HS_PACK_BINS) return -1;
+    if (rect_max_parts(height, width, false) < 0) return -1;
+    static int cache_h = 0, cache_w = 0;
+    static double cache_r = 0.0;
+    if (cache_h != height || cache_w != width) {
+        double worst = 1.0;
+        for (int hr = 1; hr <= height; ++hr)
+            for (int wr = 1; wr <= width; ++wr) {
+                const int P = hs_pack_period(hr * wr);
+                int tm;
+                const int alone = hs_rect_parts(hr, wr, height, width, &tm);       // a group of one image
+                if ((double)alone > worst) worst = (double)alone;
+                if (P == 1) continue;
+                // a group of q images is cut like the first q of P images, except that its last block stops at the group's end
+                // (a shorter second segment always fits): it has at most the blocks of the P-walk up to the one that ends image q - 1
+                int blocks = 0, done = 0;
+                const int S = hr * wr;
+                hs_pack_walk(hr, wr, height, width, P, [&](int i, int m, int nA, int nB, int) {
+                    ++blocks;
+                    const int upto = m + nA == S ? i + (nB == S ? 1 : 0) : -1;      // the last image this block ends
+                    for (; done <= upto && done < P; ++done) {       // a group of done + 1 >= 2 images has at most this many blocks
+                        const double r = (double)blocks / (double)(done + 1);
+                        if (r > worst) worst = r;
+                    }
+                });
+            }
+        cache_h = height; cache_w = width; cache_r = worst;
+    }
+    return 2 * ((long)((double)n_images * cache_r) + 1);
+}
+
+extern "C" long snk_conv_rect_pack_max_desc(int n_images, int height, int width) { return rect_pack_max_desc(n_images, height, width); }
+
+extern "C" int snk_conv_rect_plan_pack(const float *d_planes, float b0, float b1, float b2, int n_images, int height, int width,
+                                       int n_layers, const int *grow, void *d_bbox, void *d_desc, int *d_counts, void *d_order, void *stream)
+{
+    SNK_REQUIRE(d_planes && grow && d_bbox && d_desc && d_counts && d_order, "snk_conv_rect_plan_pack: NULL argument");
+    SNK_REQUIRE(n_layers >= 1 && n_layers <= HS_RECT_MAX_LAYERS, "snk_conv_rect_plan_pack: %d layers (at most %d)", n_layers, HS_RECT_MAX_LAYERS);
+    const long md = rect_pack_max_desc(n_images, height, width);
+    SNK_REQUIRE(md >= 0 && md < (1l << 31), "snk_conv_rect_plan_pack: bad shape %d x %d x %d", n_images, height, width);
+    if (n_images == 0) return 0;
+    RectPlanArgs a;
+    a.n_layers = n_layers;
+    for (int i = 0; i < n_layers; ++i) {
+        SNK_REQUIRE(grow[i] >= 0 && grow[i] < 128, "snk_conv_rect_plan_pack: grow[%d] = %d", i, grow[i]);
+        a.grow[i] = grow[i];
+    }
+    a.desc = (uint4 *)d_desc; a.max_blocks = md; a.counts = d_counts;
+    a.a16 = false;
+    hipStream_t st = (hipStream_t)stream;
+    k_obs_bbox<<<(n_images + 3) / 4, 256, 0, st>>>(d_planes, n_images, height, width, b0, b1, b2, (unsigned *)d_bbox);
+    k_rect_plan_pack<<<n_layers, 1024, 0, st>>>((const unsigned *)d_bbox, n_images, height, width, a, (int *)d_order);
+    k_rect_pack_resolve<<<dim3((unsigned)((md + 255) / 256), n_layers), 256, 0, st>>>((const unsigned *)d_bbox, n_images, height, width, a, (const int *)d_order);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// The same rule on the host, one layer, from given bounding boxes (y0 | x0 << 8 | y1 << 16 | x1 << 24): descriptors in the
+// device format (bins in shape order, a bin's images in index order; largest blocks first, otherwise in that order), h_counts =
+// { 16-byte entries, M tiles }.  h_desc: snk_conv_rect_pack_max_desc(n_images, height, width) entries.  No GPU involved.
+extern "C" int snk_conv_rect_plan_pack_host(const unsigned *h_bbox, int n_images, int height, int width, int grow,
+                                            unsigned *h_desc, int *h_counts)
+{
+    SNK_REQUIRE(h_bbox && h_desc && h_counts, "snk_conv_rect_plan_pack_host: NULL argument");
+    SNK_REQUIRE(grow >= 0 && grow < 128, "snk_conv_rect_plan_pack_host: grow = %d", grow);
+    const long md = rect_pack_max_desc(n_images, height, width);
+    SNK_REQUIRE(md >= 0 && md < (1l << 31), "snk_conv_rect_plan_pack_host: bad shape %d x %d x %d", n_images, height, width);
+    const int nb = height * width;
+    int *binof = (int *)malloc(sizeof(int) * (size_t)(n_images + 1)), *start = (int *)calloc((size_t)nb + 2, sizeof(int));
+    int *order = (int *)malloc(sizeof(int) * (size_t)(n_images + 1));
+    unsigned *rect = (unsigned *)malloc(sizeof(unsigned) * (size_t)(n_images + 1));
+    unsigned *tmp = (unsigned *)malloc(16 * (size_t)(md + 2));
+    long n_blk = 0, tiles = 0;
+    bool ok = binof && start && order && rect && tmp;
+    if (ok) {
+        for (int i = 0; i < n_images; ++i) {
+            const unsigned b = h_bbox[i];
+            const int y0 = (int)(b & 255) - grow > 0 ? (int)(b & 255) - grow : 0, x0 = (int)((b >> 8) & 255) - grow > 0 ? (int)((b >> 8) & 255) - grow : 0;
+            const int y1 = (int)((b >> 16) & 255) + grow < height - 1 ? (int)((b >> 16) & 255) + grow : height - 1;
+            const int x1 = (int)(b >> 24) + grow < width - 1 ? (int)(b >> 24) + grow : width - 1;
+            if (y1 < y0 || x1 < x0) { ok = false; break; }
+            binof[i] = (y1 - y0) * width + x1 - x0;
+            rect[i] = (unsigned)y0 | (unsigned)x0 << 8 | (unsigned)(y1 - y0 + 1) << 16 | (unsigned)(x1 - x0 + 1) << 24;
+            ++start[binof[i] + 1];
+        }
+    }
+    if (ok) {
+        for (int b = 0; b < nb; ++b) start[b + 1] += start[b];
+        for (int i = 0; i < n_images; ++i) order[start[binof[i]]++] = i;      // (start[b] is now the bin's end)
+        int at = 0;
+        for (int b = 0; b < nb && ok; ++b) {
+            const int cntb = start[b] - at, hr = b / width + 1, wr = b % width + 1, P = hs_pack_period(hr * wr);
+            for (int r0 = 0; r0 < cntb; r0 += P) {
+                const int first = at + r0;
+                hs_pack_walk(hr, wr, height, width, cntb - r0 < P ? cntb - r0 : P, [&](int i, int m, int nA, int nB, int nt) {
+                    if (2 * (n_blk + 1) > md) { ok = false; return; }
+                    const int ia = order[first + i], ib = order[first + i + (nB > 0 ? 1 : 0)];
+                    unsigned *d = tmp + 8 * n_blk++;
+                    d[0] = (unsigned)ia; d[1] = rect[ia]; d[2] = (unsigned)m | (unsigned)nA << 16; d[3] = h_bbox[ia];
+                    d[4] = (unsigned)ib; d[5] = rect[ib]; d[6] = (unsigned)nB | (unsigned)nt << 16; d[7] = h_bbox[ib];
+                    tiles += nt;
+                });
+            }
+            at = start[b];
+        }
+    }
+    if (ok) {
+        long o = 0;
+        for (int nt = 8; nt >= 1; --nt)
+            for (long k = 0; k < n_blk; ++k)
+                if ((int)((tmp[8 * k + 6] >> 16) & 15) == nt) { for (int j = 0; j < 8; ++j) h_desc[8 * o + j] = tmp[8 * k + j]; ++o; }
+        h_counts[0] = (int)(2 * n_blk);
+        h_counts[1] = (int)tiles;
+    }
+    free(binof); free(start); free(order); free(rect); free(tmp);
+    SNK_REQUIRE(ok, "snk_conv_rect_plan_pack_host: bad bounding box, out of memory or more blocks than snk_conv_rect_pack_max_desc allows");
+    return 0;
+}
+
 static int conv_f16s_rect_launch(const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
                                  const float *d_residual, float *d_out, const void *d_desc, const int *d_count,
                                  const float *d_bg_in, int grow_in, const float *d_bg_res, int grow_res, const float *d_bg_out,
@@ -1649,6 +2048,29 @@ extern "C" int snk_conv3x3_bn_f16s_rect(const float *d_x, const void *d_wS, cons
 {
     return conv_f16s_rect_launch(d_x, d_wS, d_scale, d_shift, d_residual, d_out, d_desc, d_count, d_bg_in, grow_in, d_bg_res, grow_res,
                                  d_bg_out, n_images, height, width, false, stream);
+}
+
+// snk_conv3x3_bn_f16s_rect on the packed plan's descriptors (snk_conv_rect_plan_pack)
+extern "C" int snk_conv3x3_bn_f16s_rect_pack(const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
+                                             const float *d_residual, float *d_out, const void *d_desc, const int *d_count,
+                                             const float *d_bg_in, int grow_in, const float *d_bg_res, int grow_res,
+                                             const float *d_bg_out, int n_images, int height, int width, void *stream)
+{
+    SNK_REQUIRE(grow_in >= 0 && grow_in < 128 && grow_res >= 0 && grow_res < 128, "snk_conv3x3_bn_f16s_rect_pack: grow_in %d, grow_res %d", grow_in, grow_res);
+    SNK_REQUIRE(d_x && d_wS && d_scale && d_shift && d_out && d_desc && d_count, "snk_conv3x3_bn_f16s_rect_pack: NULL argument");
+    SNK_REQUIRE(d_out != d_x, "snk_conv3x3_bn_f16s_rect_pack: in-place convolution is not possible");
+    const long md = rect_pack_max_desc(n_images, height, width);
+    // (a row's offset into the tensors carries its image: the whole batch must stay below 2^31 elements)
+    SNK_REQUIRE(md >= 0 && md < (1l << 31) && (long)n_images * height * width * HS_C < (1l << 31), "snk_conv3x3_bn_f16s_rect_pack: bad shape %d x %d x %d",
+                n_images, height, width);
+    if (n_images == 0) return 0;
+    ConvHsArgs a = {d_x, (const f16x8 *)d_wS, (const float *)((const _Float16 *)d_wS + HS_WS_ELEMS), d_scale, d_shift,
+                    d_residual, d_out, nullptr, nullptr, 0.f, 0.f, height, width, 1, 0, 0, 1, 0, nullptr, nullptr,
+                    (const uint4 *)d_desc, d_count, d_bg_out, d_bg_in, d_residual ? d_bg_res : nullptr, grow_in, grow_res, nullptr, nullptr, nullptr};
+    if (d_residual) k_conv3x3_f16s_rectp<2><<<(int)(md / 2), 256, 0, (hipStream_t)stream>>>(a);
+    else k_conv3x3_f16s_rectp<1><<<(int)(md / 2), 256, 0, (hipStream_t)stream>>>(a);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 // the sub-rectangle form of snk_conv3x3_bn_f16_act16 (f16 activations in and out, relu = 1; the background images are f16

@@ -156,6 +156,7 @@ class QNet:
         # full form then cuts the images into one-tile blocks, conv_split.hip `fine_max`), and the plan's two launches
         # cost as much as a layer (BASELINE configs[0]: 8 games)
         self.rect_min = int(os.environ.get("SNK_CONV_RECT_MIN", "48"))
+        self.rect_pack = os.environ.get("SNK_CONV_RECT_PACK", "1") != "0"
         self.n_streams = int(os.environ.get("SNK_NET_STREAMS", "1"))   # 2: chunks alternate between two streams (+0.8 % end to end,
         #    but per-launch HIP-event timings then overlap, so bench.py keeps the single-stream default)
         self._side = None
@@ -565,7 +566,13 @@ class QNet:
         """descriptors of this chunk's sub-rectangle layers: (descriptor tensor [n_rect][max_blocks][4], counts [n_rect][2])"""
         bg = self.backgrounds()
         a16 = self.act16 is not None          # the 16-bit towers cut rectangles for their own block frame
-        mb = int((self.L.snk_conv_rect_max_blocks_act16 if a16 else self.L.snk_conv_rect_max_blocks)(m, self.h, self.w))
+        # the float32-accurate tower packs the rows of same-shaped rectangles into shared GEMM tiles (SNK_CONV_RECT_PACK=0: every
+        # rectangle pads its own last tile); the descriptor array then holds two 16-byte entries per block
+        pack = not a16 and self.rect_pack and m * self.h * self.w * 128 < 2 ** 31
+        mb = int(self.L.snk_conv_rect_pack_max_desc(m, self.h, self.w)) if pack else -1
+        if mb < 0:
+            pack = False
+            mb = int((self.L.snk_conv_rect_max_blocks_act16 if a16 else self.L.snk_conv_rect_max_blocks)(m, self.h, self.w))
         if mb < 0:
             raise EngineError(f"sub-rectangle convolution: shape {m} x {self.h} x {self.w} not supported")
         key = ("rect", k)
@@ -573,11 +580,12 @@ class QNet:
         if ws is None or ws[0].shape[0] != self.n_rect or ws[0].shape[1] < mb or ws[2].shape[0] < m:
             ws = (torch.empty((self.n_rect, mb, 4), dtype=torch.int32, device=self.device),
                   torch.zeros((self.n_rect, 2), dtype=torch.int32, device=self.device),
-                  torch.empty((m,), dtype=torch.int32, device=self.device))
+                  torch.empty((m,), dtype=torch.int32, device=self.device),
+                  torch.empty((self.n_rect, m), dtype=torch.int32, device=self.device))      # the packed plan's image order
             if self._ws is None:
                 self._ws = {}
             self._ws[key] = ws
-        desc, counts, bbox = ws
+        desc, counts, bbox, order = ws
         if self.rect_tiles is not None:          # bench.py: what the launches really executed
             counts = torch.zeros((self.n_rect, 2), dtype=torch.int32, device=self.device)
             self.rect_tiles.append((m, counts))
@@ -585,9 +593,13 @@ class QNet:
         # the descriptor array of layer l starts at l * max_blocks(m): the tensor may be wider (an earlier, larger chunk)
         desc_m = desc if desc.shape[1] == mb else desc.view(-1)[:self.n_rect * mb * 4].view(self.n_rect, mb, 4)
         b0, b1, b2 = self.background
+        if pack:
+            check(self.L.snk_conv_rect_plan_pack(x.data_ptr(), b0, b1, b2, m, self.h, self.w, self.n_rect, grow, bbox.data_ptr(),
+                                                 desc_m.data_ptr(), counts.data_ptr(), order.data_ptr(), st))
+            return desc_m, counts, bg, bbox, True
         check((self.L.snk_conv_rect_plan_act16 if a16 else self.L.snk_conv_rect_plan)(
             x.data_ptr(), b0, b1, b2, m, self.h, self.w, self.n_rect, grow, bbox.data_ptr(), desc_m.data_ptr(), counts.data_ptr(), st))
-        return desc_m, counts, bg, bbox
+        return desc_m, counts, bg, bbox, False
 
     def _conv(self, i, x, res, out, m, st, h1=None, plan=None):
         tm = self.conv_timing
@@ -595,9 +607,10 @@ class QNet:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(torch.cuda.current_stream())
         if plan is not None and i < self.n_rect and h1 is None:
-            check(self.L.snk_conv3x3_bn_f16s_rect(x.data_ptr(), self.conv_wT[i].data_ptr(), self.conv_sc[i].data_ptr(),
-                                                  self.conv_sh[i].data_ptr(), None if res is None else res.data_ptr(),
-                                                  out.data_ptr(), *self._rect_args(i, plan, res), m, self.h, self.w, st))
+            conv_rect = self.L.snk_conv3x3_bn_f16s_rect_pack if plan[4] else self.L.snk_conv3x3_bn_f16s_rect
+            check(conv_rect(x.data_ptr(), self.conv_wT[i].data_ptr(), self.conv_sc[i].data_ptr(),
+                            self.conv_sh[i].data_ptr(), None if res is None else res.data_ptr(),
+                            out.data_ptr(), *self._rect_args(i, plan, res), m, self.h, self.w, st))
             if tm is not None:
                 e1.record(torch.cuda.current_stream())
                 tm.append((e0, e1, 2.0 * m * self.h * self.w * 9 * 128 * 128))

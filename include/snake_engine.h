@@ -272,6 +272,28 @@ int snk_conv3x3_bn_f16s_rect(const float *d_x, const void *d_wS, const float *d_
                              const float *d_residual, float *d_out, const void *d_desc, const int *d_count,
                              const float *d_bg_in, int grow_in, const float *d_bg_res, int grow_res,
                              const float *d_bg_out, int n_images, int height, int width, void *stream);
+/* The PACKED plan of the float32-accurate sub-rectangle layers.  A rectangle alone pads its pixels to whole 32-row GEMM tiles
+ * (15 x 15 = 225 pixels run an eighth tile for one pixel); which pixels share a tile changes no result bit, so the observations
+ * of a launch whose rectangles have the same shape get one concatenated row space, cut into blocks of at most 8 tiles that
+ * touch at most two observations (csrc/conv_split.hip, hs_pack_walk).  Results are bit-identical to snk_conv3x3_bn_f16s_rect.
+ * snk_conv_rect_pack_max_desc: 16-byte descriptor entries per layer (two per block) for n_images observations, or -1 when the
+ *   canvas is not supported (more than 4096 pixels; use the unpacked plan).
+ * snk_conv_rect_plan_pack: snk_conv_rect_plan's arguments; d_desc = n_layers * snk_conv_rect_pack_max_desc entries, d_counts[2 l] =
+ *   entries written for layer l, d_counts[2 l + 1] = M tiles its launch executes; d_order: n_layers * n_images int32 of scratch.
+ *   A block's two entries are { observation, y0 | x0 << 8 | h << 16 | w << 24, first pixel | pixels << 16, bounding box } and the
+ *   same for its second segment with { pixels (0: none, the entry then repeats the first observation) | tiles << 16 } third.
+ * snk_conv3x3_bn_f16s_rect_pack: snk_conv3x3_bn_f16s_rect on such descriptors; n_images * height * width * 128 < 2^31.
+ * snk_conv_rect_plan_pack_host: the same rule on the host for one layer, from given bounding boxes (no GPU): h_desc takes
+ *   snk_conv_rect_pack_max_desc entries in the device format, h_counts = { entries, tiles }. */
+long snk_conv_rect_pack_max_desc(int n_images, int height, int width);
+int snk_conv_rect_plan_pack(const float *d_planes, float b0, float b1, float b2, int n_images, int height, int width,
+                            int n_layers, const int *grow, void *d_bbox, void *d_desc, int *d_counts, void *d_order, void *stream);
+int snk_conv_rect_plan_pack_host(const unsigned *h_bbox, int n_images, int height, int width, int grow,
+                                 unsigned *h_desc, int *h_counts);
+int snk_conv3x3_bn_f16s_rect_pack(const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
+                                  const float *d_residual, float *d_out, const void *d_desc, const int *d_count,
+                                  const float *d_bg_in, int grow_in, const float *d_bg_res, int grow_res,
+                                  const float *d_bg_out, int n_images, int height, int width, void *stream);
 /* The tower's LAST layer with the head's 1x1 stage fused into its epilogue (alpha_nnet.py:46-50): besides (or, with
  * d_out NULL, instead of) the layer output it writes d_h1[n][height*width] = relu(dot(out[pixel][:], w1x1) * bn_scale
  * + bn_shift); snk_head_dense_f32 finishes AlphaNNet.v from d_h1 (Flatten, Dense(128) + ReLU, Dense(3) + tanh,
