@@ -268,7 +268,7 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     constexpr bool STATS = MODE == 4 || MODE == 6 || MODE == 9, GSTATS = MODE == 5 || MODE == 7 || MODE == 8 || MODE == 10, BARE = STATS || GSTATS;
     constexpr bool RESMASK = MODE == 8 || MODE == 10, AMAX = MODE == 4 || MODE == 9;
     constexpr bool AFF = MODE == 6 || MODE == 9, GAFF = MODE == 7 || MODE == 10, NORES = MODE == 7;
-    static_assert(!(AFF || GAFF || RESMASK) || (SPLIT && IO16 == 0 && !RECT), "the deferred batch norm exists in the training step's float32 form only");
+    static_assert(!(AFF || GAFF || RESMASK) || (IO16 == 0 && !RECT), "the deferred batch norm exists in the training step's forms (float32 tensors, whole images) only");
     constexpr bool K32 = IN16;
     constexpr int RING = K32 ? HS_RING16 : HS_RING, AHEAD = K32 ? HS_AHEAD16 : HS_AHEAD;      // B-fragment register ring: slots (a divisor of 9), taps ahead
     constexpr bool TWO = SPLIT || K32;                     // two A fragments / two B fragments per (tap, M tile)
@@ -1411,16 +1411,21 @@ static int conv_f16s_launch(const float *d_x, const void *d_wS, const float *d_s
     const int n_mt = tiles_max, grid = n_images * n_blk;
     hipStream_t st = (hipStream_t)stream;
     if (grid_out) *grid_out = grid;
+// (split == false: the training step's single-pass f16 form -- the same frames with the hi halves only, SPLIT = false)
+#define HS_LAUNCH_TRAIN_NI(NI_, MODE_)                                                          \
+        if (split) k_conv3x3_f16s<NI_, MODE_><<<grid, 256, 0, st>>>(a);                         \
+        else k_conv3x3_f16s<NI_, MODE_, false><<<grid, 256, 0, st>>>(a);                        \
+        break;
 #define HS_LAUNCH_TRAIN(MODE_)                                                                   \
         switch (n_mt) {                                                                         \
-        case 1: k_conv3x3_f16s<1, MODE_><<<grid, 256, 0, st>>>(a); break;                       \
-        case 2: k_conv3x3_f16s<2, MODE_><<<grid, 256, 0, st>>>(a); break;                       \
-        case 3: k_conv3x3_f16s<3, MODE_><<<grid, 256, 0, st>>>(a); break;                       \
-        case 4: k_conv3x3_f16s<4, MODE_><<<grid, 256, 0, st>>>(a); break;                       \
-        case 5: k_conv3x3_f16s<5, MODE_><<<grid, 256, 0, st>>>(a); break;                       \
-        case 6: k_conv3x3_f16s<6, MODE_><<<grid, 256, 0, st>>>(a); break;                       \
-        case 7: k_conv3x3_f16s<7, MODE_><<<grid, 256, 0, st>>>(a); break;                       \
-        default: k_conv3x3_f16s<8, MODE_><<<grid, 256, 0, st>>>(a); break;                      \
+        case 1: HS_LAUNCH_TRAIN_NI(1, MODE_)                                                    \
+        case 2: HS_LAUNCH_TRAIN_NI(2, MODE_)                                                    \
+        case 3: HS_LAUNCH_TRAIN_NI(3, MODE_)                                                    \
+        case 4: HS_LAUNCH_TRAIN_NI(4, MODE_)                                                    \
+        case 5: HS_LAUNCH_TRAIN_NI(5, MODE_)                                                    \
+        case 6: HS_LAUNCH_TRAIN_NI(6, MODE_)                                                    \
+        case 7: HS_LAUNCH_TRAIN_NI(7, MODE_)                                                    \
+        default: HS_LAUNCH_TRAIN_NI(8, MODE_)                                                   \
         }                                                                                       \
         SNK_CHECK_HIP(hipGetLastError());                                                       \
         return 0;
@@ -1431,35 +1436,10 @@ static int conv_f16s_launch(const float *d_x, const void *d_wS, const float *d_s
     if (d_stat_part && a.g_y && d_aff_scale) { HS_LAUNCH_TRAIN(7) }    // ... of a layer whose ReLU decision is recomputed from its scale / shift
     if (d_stat_part && d_aff_scale && d_amax_part) { HS_LAUNCH_TRAIN(9) }
     if (d_stat_part && d_aff_scale) { HS_LAUNCH_TRAIN(6) }             // forward pass, the producer's batch norm + ReLU applied on the way in
+    if (d_stat_part && a.g_y) { HS_LAUNCH_TRAIN(5) }                   // the training step's input gradient + the previous layer's batch-norm backward sums
+    if (d_stat_part) { HS_LAUNCH_TRAIN(4) }                            // the training step's forward pass: bare convolution + batch-norm sums
 #undef HS_LAUNCH_TRAIN
-    if (d_stat_part && a.g_y) {          // the training step's input gradient + the previous layer's batch-norm backward sums
-        switch (n_mt) {
-        case 1: k_conv3x3_f16s<1, 5><<<grid, 256, 0, st>>>(a); break;
-        case 2: k_conv3x3_f16s<2, 5><<<grid, 256, 0, st>>>(a); break;
-        case 3: k_conv3x3_f16s<3, 5><<<grid, 256, 0, st>>>(a); break;
-        case 4: k_conv3x3_f16s<4, 5><<<grid, 256, 0, st>>>(a); break;
-        case 5: k_conv3x3_f16s<5, 5><<<grid, 256, 0, st>>>(a); break;
-        case 6: k_conv3x3_f16s<6, 5><<<grid, 256, 0, st>>>(a); break;
-        case 7: k_conv3x3_f16s<7, 5><<<grid, 256, 0, st>>>(a); break;
-        default: k_conv3x3_f16s<8, 5><<<grid, 256, 0, st>>>(a); break;
-        }
-        SNK_CHECK_HIP(hipGetLastError());
-        return 0;
-    }
-    if (d_stat_part) {                   // the training step's forward pass: bare convolution + batch-norm sums
-        switch (n_mt) {
-        case 1: k_conv3x3_f16s<1, 4><<<grid, 256, 0, st>>>(a); break;
-        case 2: k_conv3x3_f16s<2, 4><<<grid, 256, 0, st>>>(a); break;
-        case 3: k_conv3x3_f16s<3, 4><<<grid, 256, 0, st>>>(a); break;
-        case 4: k_conv3x3_f16s<4, 4><<<grid, 256, 0, st>>>(a); break;
-        case 5: k_conv3x3_f16s<5, 4><<<grid, 256, 0, st>>>(a); break;
-        case 6: k_conv3x3_f16s<6, 4><<<grid, 256, 0, st>>>(a); break;
-        case 7: k_conv3x3_f16s<7, 4><<<grid, 256, 0, st>>>(a); break;
-        default: k_conv3x3_f16s<8, 4><<<grid, 256, 0, st>>>(a); break;
-        }
-        SNK_CHECK_HIP(hipGetLastError());
-        return 0;
-    }
+#undef HS_LAUNCH_TRAIN_NI
     // the three epilogue shapes the net wrapper uses get compile-time versions at the 21x21 tile count; everything else
     // takes the generic version
     if (!split && io16) {        // f16 activations in HBM (io16: 1 = f16 in, f32 out; 3 = f16 in and out)
@@ -2156,17 +2136,37 @@ __global__ __launch_bounds__(256) void k_amax_fold128(const float *__restrict__ 
     }
 }
 
-extern "C" int snk_conv3x3_f16s_stats(const float *d_x, const void *d_wS, float *d_out, const float *d_center, float *d_partials,
-                                      double *d_sums, int n_images, int height, int width, void *stream)
+static int conv_stats(bool split, const float *d_x, const void *d_wS, float *d_out, const float *d_center, float *d_partials,
+                      double *d_sums, int n_images, int height, int width, void *stream)
 {
-    SNK_REQUIRE(d_x && d_wS && d_out && d_partials && d_sums && n_images > 0, "snk_conv3x3_f16s_stats: bad argument");
+    SNK_REQUIRE(d_x && d_wS && d_out && d_partials && d_sums && n_images > 0, "snk_conv3x3_%s_stats: bad argument", split ? "f16s" : "f16");
     int grid = 0;
     const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, nullptr, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
-                                    true, stream, 0, d_center, d_partials, &grid);
+                                    split, stream, 0, d_center, d_partials, &grid);
     if (rc) return rc;
     tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int snk_conv3x3_f16s_stats(const float *d_x, const void *d_wS, float *d_out, const float *d_center, float *d_partials,
+                                      double *d_sums, int n_images, int height, int width, void *stream)
+{
+    return conv_stats(true, d_x, d_wS, d_out, d_center, d_partials, d_sums, n_images, height, width, stream);
+}
+
+// ---- the training step's single-pass f16 mode (TrainStep(conv="f16"), SNK_TRAIN_CONV=f16) -------------------------------------------
+// The snk_conv3x3_f16_* entry points take the argument lists, weight images and scale tails of their snk_conv3x3_f16s_* namesakes
+// and run the same block frames with SPLIT = false: one MFMA per product.  The arithmetic rule (include/snake_engine.h, DESIGN.md
+// section 4, tests/test_train_f16_gpu.py state the same one): an operand v enters the MFMA as f16(v * s), round to nearest even, s
+// the power of two the split form uses for that tensor (the image's tail); beyond +-65504 after scaling it is clamped and the
+// layer's range flag raised, as in the split form; products are exact in float32, sums are float32, the result is multiplied by
+// the inverse scales.  Nothing else is rounded to 16 bits: every tensor in HBM stays float32.  The weight image is the split
+// image: its hi fragments are 1 KB runs of their own, so a wave that skips the lo runs streams exactly a hi-only image's bytes.
+extern "C" int snk_conv3x3_f16_stats(const float *d_x, const void *d_wS, float *d_out, const float *d_center, float *d_partials,
+                                     double *d_sums, int n_images, int height, int width, void *stream)
+{
+    return conv_stats(false, d_x, d_wS, d_out, d_center, d_partials, d_sums, n_images, height, width, stream);
 }
 
 // The same with the two options of the deferred batch norm (snake_engine/train_step.py: the activation between the two convolutions
@@ -2176,18 +2176,18 @@ extern "C" int snk_conv3x3_f16s_stats(const float *d_x, const void *d_wS, float 
 //     would have written; the input scale in d_wS's tail must cover that range (snk_bn_train_finalize_range);
 //   d_amax (or NULL; with either input form): 128 floats, the largest |out - center| per channel -- what snk_bn_train_finalize_range turns into the
 //     range of this layer's own batch norm + ReLU output without a pass over it.
-extern "C" int snk_conv3x3_f16s_stats_deferred(const float *d_x, const void *d_wS, float *d_out, const float *d_center,
-                                               const float *d_in_scale, const float *d_in_shift, float *d_amax, float *d_partials,
-                                               double *d_sums, int n_images, int height, int width, void *stream)
+static int conv_stats_deferred(bool split, const float *d_x, const void *d_wS, float *d_out, const float *d_center,
+                               const float *d_in_scale, const float *d_in_shift, float *d_amax, float *d_partials,
+                               double *d_sums, int n_images, int height, int width, void *stream)
 {
     SNK_REQUIRE(d_x && d_wS && d_out && d_partials && d_sums && n_images > 0 && !d_in_scale == !d_in_shift,
-                "snk_conv3x3_f16s_stats_deferred: bad argument");
+                "snk_conv3x3_%s_stats_deferred: bad argument", split ? "f16s" : "f16");
     // the launch's grid is known only inside: the maxima sit behind the largest sums + fold scratch the buffer is sized for
     const long T = ((long)height * width + 31) / 32;
     float *amax_part = d_amax ? d_partials + (long)n_images * T * 256 + TF_SCRATCH_FLOATS(256) : nullptr;
     int grid = 0;
     const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, nullptr, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
-                                    true, stream, 0, d_center, d_partials, &grid, false, nullptr, nullptr, nullptr, d_in_scale, d_in_shift,
+                                    split, stream, 0, d_center, d_partials, &grid, false, nullptr, nullptr, nullptr, d_in_scale, d_in_shift,
                                     amax_part);
     if (rc) return rc;
     tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
@@ -2198,6 +2198,22 @@ extern "C" int snk_conv3x3_f16s_stats_deferred(const float *d_x, const void *d_w
     }
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int snk_conv3x3_f16s_stats_deferred(const float *d_x, const void *d_wS, float *d_out, const float *d_center,
+                                               const float *d_in_scale, const float *d_in_shift, float *d_amax, float *d_partials,
+                                               double *d_sums, int n_images, int height, int width, void *stream)
+{
+    return conv_stats_deferred(true, d_x, d_wS, d_out, d_center, d_in_scale, d_in_shift, d_amax, d_partials, d_sums, n_images, height,
+                               width, stream);
+}
+
+extern "C" int snk_conv3x3_f16_stats_deferred(const float *d_x, const void *d_wS, float *d_out, const float *d_center,
+                                              const float *d_in_scale, const float *d_in_shift, float *d_amax, float *d_partials,
+                                              double *d_sums, int n_images, int height, int width, void *stream)
+{
+    return conv_stats_deferred(false, d_x, d_wS, d_out, d_center, d_in_scale, d_in_shift, d_amax, d_partials, d_sums, n_images, height,
+                               width, stream);
 }
 
 // reduced precision with f16 activations in HBM (BASELINE configs[4]): d_x16 / d_residual16 are f16 [n][H][W][128]; the output
@@ -2288,52 +2304,85 @@ extern "C" int snk_conv3x3_bn_mxfp8_act16_head(const void *d_x16, const void *d_
 // on their way out d_sums[0..127] = sum(g), d_sums[128..255] = sum(g * (y - mean) * inv) with g = d_out where that layer's ReLU bit
 // is set (d_mask: one byte per quad of channels, as snk_bn_train_apply writes them; d_y: its pre-batch-norm output) -- what
 // snk_bn_train_grad_sums_f64 computes from d_out in a pass of its own.  d_partials: snk_conv3x3_stats_partials floats.
-extern "C" int snk_conv3x3_f16s_igrad_stats(const float *d_x, const void *d_wS, const float *d_residual, float *d_out, const float *d_y,
-                                            const uint8_t *d_mask, const float *d_mean, const float *d_inv, float *d_partials,
-                                            double *d_sums, int n_images, int height, int width, void *stream)
+static int conv_igrad_stats(bool split, const float *d_x, const void *d_wS, const float *d_residual, float *d_out, const float *d_y,
+                            const uint8_t *d_mask, const float *d_mean, const float *d_inv, float *d_partials, double *d_sums,
+                            int n_images, int height, int width, void *stream)
 {
     SNK_REQUIRE(d_x && d_wS && d_out && d_y && d_mask && d_mean && d_inv && d_partials && d_sums && n_images > 0,
-                "snk_conv3x3_f16s_igrad_stats: bad argument");
+                "snk_conv3x3_%s_igrad_stats: bad argument", split ? "f16s" : "f16");
     int grid = 0;
     const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, d_residual, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
-                                    true, stream, 0, d_mean, d_partials, &grid, false, d_y, d_mask, d_inv);
+                                    split, stream, 0, d_mean, d_partials, &grid, false, d_y, d_mask, d_inv);
     if (rc) return rc;
     tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
+extern "C" int snk_conv3x3_f16s_igrad_stats(const float *d_x, const void *d_wS, const float *d_residual, float *d_out,
+                                            const float *d_y, const uint8_t *d_mask, const float *d_mean, const float *d_inv, float *d_partials,
+                                            double *d_sums, int n_images, int height, int width, void *stream)
+{
+    return conv_igrad_stats(true, d_x, d_wS, d_residual, d_out, d_y, d_mask, d_mean, d_inv, d_partials, d_sums, n_images, height,
+                            width, stream);
+}
+
+extern "C" int snk_conv3x3_f16_igrad_stats(const float *d_x, const void *d_wS, const float *d_residual, float *d_out,
+                                           const float *d_y, const uint8_t *d_mask, const float *d_mean, const float *d_inv, float *d_partials,
+                                           double *d_sums, int n_images, int height, int width, void *stream)
+{
+    return conv_igrad_stats(false, d_x, d_wS, d_residual, d_out, d_y, d_mask, d_mean, d_inv, d_partials, d_sums, n_images, height,
+                            width, stream);
+}
+
 // The same for a layer below whose batch norm + ReLU output was never written (deferred): its ReLU decision is
 // d_y * d_scale[c] + d_shift[c] > 0 -- the sign of what snk_bn_train_apply would have written -- instead of mask bytes.
-extern "C" int snk_conv3x3_f16s_igrad_stats_deferred(const float *d_x, const void *d_wS, const float *d_residual, float *d_out,
-                                                     const float *d_y, const float *d_scale, const float *d_shift, const float *d_mean,
-                                                     const float *d_inv, float *d_partials, double *d_sums, int n_images, int height,
-                                                     int width, void *stream)
+static int conv_igrad_stats_deferred(bool split, const float *d_x, const void *d_wS, const float *d_residual, float *d_out,
+                                     const float *d_y, const float *d_scale, const float *d_shift, const float *d_mean,
+                                     const float *d_inv, float *d_partials, double *d_sums, int n_images, int height, int width, void *stream)
 {
     SNK_REQUIRE(d_x && d_wS && d_out && d_y && d_scale && d_shift && d_mean && d_inv && d_partials && d_sums && n_images > 0,
-                "snk_conv3x3_f16s_igrad_stats_deferred: bad argument");
+                "snk_conv3x3_%s_igrad_stats_deferred: bad argument", split ? "f16s" : "f16");
     int grid = 0;
     const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, d_residual, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
-                                    true, stream, 0, d_mean, d_partials, &grid, false, d_y, nullptr, d_inv, d_scale, d_shift);
+                                    split, stream, 0, d_mean, d_partials, &grid, false, d_y, nullptr, d_inv, d_scale, d_shift);
     if (rc) return rc;
     tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int snk_conv3x3_f16s_igrad_stats_deferred(const float *d_x, const void *d_wS, const float *d_residual, float *d_out,
+                                                     const float *d_y, const float *d_scale, const float *d_shift,
+                                                     const float *d_mean, const float *d_inv, float *d_partials, double *d_sums, int n_images,
+                                                     int height, int width, void *stream)
+{
+    return conv_igrad_stats_deferred(true, d_x, d_wS, d_residual, d_out, d_y, d_scale, d_shift, d_mean, d_inv, d_partials, d_sums,
+                                     n_images, height, width, stream);
+}
+
+extern "C" int snk_conv3x3_f16_igrad_stats_deferred(const float *d_x, const void *d_wS, const float *d_residual, float *d_out,
+                                                    const float *d_y, const float *d_scale, const float *d_shift, const float *d_mean,
+                                                    const float *d_inv, float *d_partials, double *d_sums, int n_images, int height,
+                                                    int width, void *stream)
+{
+    return conv_igrad_stats_deferred(false, d_x, d_wS, d_residual, d_out, d_y, d_scale, d_shift, d_mean, d_inv, d_partials, d_sums,
+                                     n_images, height, width, stream);
 }
 
 // snk_conv3x3_f16s_igrad_stats whose shortcut gradient is d_residual WHERE d_residual_mask's bit is set: d_residual = the gradient
 // at the residual block's output (before that output's ReLU), d_residual_mask = that output's ReLU bits (snk_bn_train_apply's
 // bytes) -- the masked copy snk_bn_train_grad_apply(d_g) writes is not needed.  d_out may be d_residual (in place).
-extern "C" int snk_conv3x3_f16s_igrad_stats_masked_res(const float *d_x, const void *d_wS, const float *d_residual,
-                                                       const uint8_t *d_residual_mask, float *d_out, const float *d_y,
-                                                       const uint8_t *d_mask, const float *d_mean, const float *d_inv, float *d_partials,
-                                                       double *d_sums, int n_images, int height, int width, void *stream)
+static int conv_igrad_stats_masked_res(bool split, const float *d_x, const void *d_wS, const float *d_residual,
+                                       const uint8_t *d_residual_mask, float *d_out, const float *d_y, const uint8_t *d_mask, const float *d_mean,
+                                       const float *d_inv, float *d_partials, double *d_sums, int n_images, int height, int width,
+                                       void *stream)
 {
     SNK_REQUIRE(d_x && d_wS && d_residual && d_residual_mask && d_out && d_y && d_mask && d_mean && d_inv && d_partials && d_sums &&
-                n_images > 0, "snk_conv3x3_f16s_igrad_stats_masked_res: bad argument");
+                n_images > 0, "snk_conv3x3_%s_igrad_stats_masked_res: bad argument", split ? "f16s" : "f16");
     int grid = 0;
     const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, d_residual, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
-                                    true, stream, 0, d_mean, d_partials, &grid, false, d_y, d_mask, d_inv, nullptr, nullptr, nullptr,
+                                    split, stream, 0, d_mean, d_partials, &grid, false, d_y, d_mask, d_inv, nullptr, nullptr, nullptr,
                                     d_residual_mask);
     if (rc) return rc;
     tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
@@ -2341,22 +2390,59 @@ extern "C" int snk_conv3x3_f16s_igrad_stats_masked_res(const float *d_x, const v
     return 0;
 }
 
+extern "C" int snk_conv3x3_f16s_igrad_stats_masked_res(const float *d_x, const void *d_wS, const float *d_residual,
+                                                       const uint8_t *d_residual_mask, float *d_out, const float *d_y, const uint8_t *d_mask,
+                                                       const float *d_mean, const float *d_inv, float *d_partials, double *d_sums,
+                                                       int n_images, int height, int width, void *stream)
+{
+    return conv_igrad_stats_masked_res(true, d_x, d_wS, d_residual, d_residual_mask, d_out, d_y, d_mask, d_mean, d_inv, d_partials,
+                                       d_sums, n_images, height, width, stream);
+}
+
+extern "C" int snk_conv3x3_f16_igrad_stats_masked_res(const float *d_x, const void *d_wS, const float *d_residual,
+                                                      const uint8_t *d_residual_mask, float *d_out, const float *d_y, const uint8_t *d_mask,
+                                                      const float *d_mean, const float *d_inv, float *d_partials, double *d_sums,
+                                                      int n_images, int height, int width, void *stream)
+{
+    return conv_igrad_stats_masked_res(false, d_x, d_wS, d_residual, d_residual_mask, d_out, d_y, d_mask, d_mean, d_inv, d_partials,
+                                       d_sums, n_images, height, width, stream);
+}
+
 // snk_conv3x3_f16s_igrad_stats_masked_res for a layer below whose batch norm + ReLU output was never written (the deferred stem):
 // the ReLU decision of the SUMS is d_y * d_scale[c] + d_shift[c] > 0 instead of mask bytes
+static int conv_igrad_stats_masked_res_deferred(bool split, const float *d_x, const void *d_wS, const float *d_residual,
+                                                const uint8_t *d_residual_mask, float *d_out, const float *d_y, const float *d_scale,
+                                                const float *d_shift, const float *d_mean, const float *d_inv, float *d_partials,
+                                                double *d_sums, int n_images, int height, int width, void *stream)
+{
+    SNK_REQUIRE(d_x && d_wS && d_residual && d_residual_mask && d_out && d_y && d_scale && d_shift && d_mean && d_inv && d_partials &&
+                d_sums && n_images > 0, "snk_conv3x3_%s_igrad_stats_masked_res_deferred: bad argument", split ? "f16s" : "f16");
+    int grid = 0;
+    const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, d_residual, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
+                                    split, stream, 0, d_mean, d_partials, &grid, false, d_y, nullptr, d_inv, d_scale, d_shift, nullptr,
+                                    d_residual_mask);
+    if (rc) return rc;
+    tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 extern "C" int snk_conv3x3_f16s_igrad_stats_masked_res_deferred(const float *d_x, const void *d_wS, const float *d_residual,
                                                                 const uint8_t *d_residual_mask, float *d_out, const float *d_y,
                                                                 const float *d_scale, const float *d_shift, const float *d_mean,
                                                                 const float *d_inv, float *d_partials, double *d_sums, int n_images,
                                                                 int height, int width, void *stream)
 {
-    SNK_REQUIRE(d_x && d_wS && d_residual && d_residual_mask && d_out && d_y && d_scale && d_shift && d_mean && d_inv && d_partials &&
-                d_sums && n_images > 0, "snk_conv3x3_f16s_igrad_stats_masked_res_deferred: bad argument");
-    int grid = 0;
-    const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, d_residual, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
-                                    true, stream, 0, d_mean, d_partials, &grid, false, d_y, nullptr, d_inv, d_scale, d_shift, nullptr,
-                                    d_residual_mask);
-    if (rc) return rc;
-    tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
-    SNK_CHECK_HIP(hipGetLastError());
-    return 0;
+    return conv_igrad_stats_masked_res_deferred(true, d_x, d_wS, d_residual, d_residual_mask, d_out, d_y, d_scale, d_shift, d_mean,
+                                                d_inv, d_partials, d_sums, n_images, height, width, stream);
+}
+
+extern "C" int snk_conv3x3_f16_igrad_stats_masked_res_deferred(const float *d_x, const void *d_wS, const float *d_residual,
+                                                               const uint8_t *d_residual_mask, float *d_out, const float *d_y,
+                                                               const float *d_scale, const float *d_shift, const float *d_mean,
+                                                               const float *d_inv, float *d_partials, double *d_sums, int n_images, int height,
+                                                               int width, void *stream)
+{
+    return conv_igrad_stats_masked_res_deferred(false, d_x, d_wS, d_residual, d_residual_mask, d_out, d_y, d_scale, d_shift, d_mean,
+                                                d_inv, d_partials, d_sums, n_images, height, width, stream);
 }

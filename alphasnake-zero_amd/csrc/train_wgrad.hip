@@ -301,7 +301,10 @@ struct Wg2Args {
 // AFF: the deferred batch norm (snake_engine/train_step.py): X is the pre-batch-norm output of the layer below, its batch norm + ReLU
 //   -- k_bn_apply's expression, csrc/train.hip -- is applied when an item is laid into LDS; the stream's padding slots, which the
 //   buffer descriptor answers with zeros, must stay zeros (they are the padding of the ACTIVATION): one bit per item remembers it
-template <int NK, int MAXX, int WT, bool AFF = false>
+// HI: the training step's single-pass f16 mode (snk_conv3x3_wgrad_f16): only the hi planes of X and dY exist -- no lo planes, none of
+//   their ds_writes and transposing reads, one MFMA per tap and k-step instead of three; a buffer is XH0 XH1 | YH0..3, half the bytes.
+//   The window (NK) and the staging items are the split form's: the frame is not re-tuned.
+template <int NK, int MAXX, int WT, bool AFF = false, bool HI = false>
 __global__ __launch_bounds__(512) void k_wgrad2_f16s(Wg2Args p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -314,7 +317,8 @@ __global__ __launch_bounds__(512) void k_wgrad2_f16s(Wg2Args p)
     const int S = nimg * SR * P;                                          // slots of this group's stream
     const int T = (S + 16 * NK - 1) / (16 * NK);                          // windows
     const int plane_x = (WT ? 16 * NK + WG_GX + 2 * (WT + 1) + 8 : p.rows_x) * 64, plane_y = 16 * NK * 64;
-    const int buf_bytes = 4 * plane_x + 8 * plane_y;                      // XH0 XH1 XL0 XL1 | YH0..3 YL0..3
+    const int x_bytes = (HI ? 2 : 4) * plane_x;                          // the X planes of a buffer
+    const int buf_bytes = x_bytes + (HI ? 4 : 8) * plane_y;               // XH0 XH1 XL0 XL1 | YH0..3 YL0..3 (HI: XH0 XH1 | YH0..3)
     for (int o = tid * 16; o < 2 * buf_bytes; o += 512 * 16) *(uint4 *)(smem + o) = make_uint4(0u, 0u, 0u, 0u);
 
     // ---- staging: item j of this thread = (slot, four channels) of the window; X first, then dY
@@ -374,15 +378,17 @@ __global__ __launch_bounds__(512) void k_wgrad2_f16s(Wg2Args p)
             v.z = fmaxf(v.z * xsc.z + xsh.z, 0.f); v.w = fmaxf(v.w * xsc.w + xsh.w, 0.f);
             xv[j] = make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
         }
-        wg_split4(xv[j], sx, hi, lo);
+        wg_split4(xv[j], sx, hi, lo);                                     // (HI: lo is never used and its two instructions per element go)
         unsigned char *d = B + xl0 + min(xr0 + 32 * j, nxs - 1) * 64;
-        *(uint2 *)d = hi; *(uint2 *)(d + 2 * plane_x) = lo;
+        *(uint2 *)d = hi;
+        if (!HI) *(uint2 *)(d + 2 * plane_x) = lo;
     };
     auto store_y = [&](int j, unsigned char *B) {
         uint2 hi, lo;
         wg_split4(yv[j], sy, hi, lo);
-        unsigned char *d = B + 4 * plane_x + yl0 + (yr0 + 16 * j) * 64;
-        *(uint2 *)d = hi; *(uint2 *)(d + 4 * plane_y) = lo;
+        unsigned char *d = B + x_bytes + yl0 + (yr0 + 16 * j) * 64;
+        *(uint2 *)d = hi;
+        if (!HI) *(uint2 *)(d + 4 * plane_y) = lo;
     };
 
     // ---- MFMA side (addressing as in k_wgrad_f16s): a transposing read of rows R .. R + 3
@@ -416,7 +422,8 @@ __global__ __launch_bounds__(512) void k_wgrad2_f16s(Wg2Args p)
 #endif
         unsigned char *B = smem + (t & 1) * buf_bytes, *Bn = smem + ((t + 1) & 1) * buf_bytes;
         const unsigned char *XH = B + wa * plane_x, *XL = XH + 2 * plane_x;
-        const unsigned char *YH = B + 4 * plane_x + wb * plane_y, *YL = YH + 4 * plane_y;
+        const unsigned char *YH = B + x_bytes + wb * plane_y, *YL = YH + 4 * plane_y;
+        (void)XL; (void)YL;
         // the registers hold window t + 1: group g lays item g into the other buffer and requests the same item of window t + 2 into the
         // registers that just became free (a whole window ahead of its use; its address arithmetic sits in the shadow of the MFMAs)
 
@@ -431,13 +438,13 @@ __global__ __launch_bounds__(512) void k_wgrad2_f16s(Wg2Args p)
         {                                                                                       \
             const int Rx = 16 * (ks_) + 8 * h + xoff + ((dyi_) - 1) * P + ((dxi) - 1);          \
             ah[dxi] = wg_cat(WG_TR(XH + Rx * 64 + lane_off), WG_TR(XH + (Rx + 4) * 64 + lane_off)); \
-            al[dxi] = wg_cat(WG_TR(XL + Rx * 64 + lane_off), WG_TR(XL + (Rx + 4) * 64 + lane_off)); \
+            if (!HI) al[dxi] = wg_cat(WG_TR(XL + Rx * 64 + lane_off), WG_TR(XL + (Rx + 4) * 64 + lane_off)); \
         }
 #define WG2_LOADB(ks_)                                                                          \
         {                                                                                       \
             const int R = 16 * (ks_) + 8 * h;                                                   \
             bh = wg_cat(WG_TR(YH + R * 64 + lane_off), WG_TR(YH + (R + 4) * 64 + lane_off));    \
-            bl = wg_cat(WG_TR(YL + R * 64 + lane_off), WG_TR(YL + (R + 4) * 64 + lane_off));    \
+            if (!HI) bl = wg_cat(WG_TR(YL + R * 64 + lane_off), WG_TR(YL + (R + 4) * 64 + lane_off)); \
         }
         WG2_LOADB(0)
         WG2_LOADA(0, 0, 0) WG2_LOADA(1, 0, 0) WG2_LOADA(2, 0, 0)
@@ -459,8 +466,10 @@ __global__ __launch_bounds__(512) void k_wgrad2_f16s(Wg2Args p)
             for (int dxi = 0; dxi < 3; ++dxi) {
                 const int tp = 3 * dyi + dxi;
                 acc[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[dxi], bh, acc[tp], 0, 0, 0);
-                acc[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[dxi], bl, acc[tp], 0, 0, 0);
-                acc[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[dxi], bh, acc[tp], 0, 0, 0);
+                if (!HI) {
+                    acc[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[dxi], bl, acc[tp], 0, 0, 0);
+                    acc[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[dxi], bh, acc[tp], 0, 0, 0);
+                }
                 if (gn < 3 * NK) {
                     if (dxi == 2 && dyn == 0) WG2_LOADB(ksn)             // the k-step's last MFMA has been issued: its dY fragments may go
                     WG2_LOADA(dxi, ksn, dyn)
@@ -542,9 +551,12 @@ extern "C" long snk_conv3x3_wgrad_partials(int height, int width)
 
 static int wgrad_launch(const float *d_x, const float *d_dy, const float *d_x_tail, const float *d_dy_tail, float *d_partials,
                         float *d_dw, int n_images, int height, int width, void *stream, const float *d_x_scale,
-                        const float *d_x_shift)
+                        const float *d_x_shift, bool hi_only = false)
 {
     SNK_REQUIRE((long)n_images * height * width * 128 < (1l << 40), "snk_conv3x3_wgrad_f16s: batch too large");
+    // the single-pass f16 mode exists in the window form only
+    SNK_REQUIRE(!hi_only || wg_use_windows(height, width), "snk_conv3x3_wgrad_f16: the slab form of the weight gradient (SNK_WGRAD=slabs, "
+                "or a shape the window form does not take: %d x %d) has no single-pass f16 variant", height, width);
     if (wg_use_windows(height, width)) {
         Wg2Shape s2;
         wg2_shape(height, width, s2);
@@ -560,9 +572,13 @@ static int wgrad_launch(const float *d_x, const float *d_dy, const float *d_x_ta
             if (!attr_) {                                                                       \
                 SNK_CHECK_HIP(hipFuncSetAttribute((const void *)k_wgrad2_f16s<NK_, MX_, WT_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
                 SNK_CHECK_HIP(hipFuncSetAttribute((const void *)k_wgrad2_f16s<NK_, MX_, WT_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+                SNK_CHECK_HIP(hipFuncSetAttribute((const void *)k_wgrad2_f16s<NK_, MX_, WT_, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)); \
+                SNK_CHECK_HIP(hipFuncSetAttribute((const void *)k_wgrad2_f16s<NK_, MX_, WT_, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)); \
                 attr_ = true;                                                                   \
             }                                                                                   \
-            if (d_x_scale) k_wgrad2_f16s<NK_, MX_, WT_, true><<<g2, 512, s2.lds + 512, (hipStream_t)stream>>>(a2); \
+            if (hi_only && d_x_scale) k_wgrad2_f16s<NK_, MX_, WT_, true, true><<<g2, 512, s2.lds / 2 + 512, (hipStream_t)stream>>>(a2); \
+            else if (hi_only) k_wgrad2_f16s<NK_, MX_, WT_, false, true><<<g2, 512, s2.lds / 2, (hipStream_t)stream>>>(a2); \
+            else if (d_x_scale) k_wgrad2_f16s<NK_, MX_, WT_, true><<<g2, 512, s2.lds + 512, (hipStream_t)stream>>>(a2); \
             else k_wgrad2_f16s<NK_, MX_, WT_, false><<<g2, 512, s2.lds, (hipStream_t)stream>>>(a2); \
         }
         if (wt == 21 && s2.nk == 5 && s2.maxx <= 4) WG2_LAUNCH(5, 4, 21)
@@ -607,6 +623,25 @@ extern "C" int snk_conv3x3_wgrad_f16s_deferred(const float *d_y_below, const flo
     SNK_REQUIRE(d_y_below && d_scale && d_shift && d_dy && d_x_tail && d_dy_tail && d_partials && d_dw && n_images > 0,
                 "snk_conv3x3_wgrad_f16s_deferred: bad argument");
     return wgrad_launch(d_y_below, d_dy, d_x_tail, d_dy_tail, d_partials, d_dw, n_images, height, width, stream, d_scale, d_shift);
+}
+
+// The single-pass f16 mode of the two entry points above (TrainStep(conv="f16")): X and dY enter the MFMA as f16(v * s) with the
+// scales of d_x_tail / d_dy_tail and nothing else -- one MFMA per tap and k-step (the rule: include/snake_engine.h).  Same arguments,
+// same partials.  Window form only: with SNK_WGRAD=slabs, or for a shape only the slab form takes, the call fails with a message.
+extern "C" int snk_conv3x3_wgrad_f16(const float *d_x, const float *d_dy, const float *d_x_tail, const float *d_dy_tail,
+                                     float *d_partials, float *d_dw, int n_images, int height, int width, void *stream)
+{
+    SNK_REQUIRE(d_x && d_dy && d_x_tail && d_dy_tail && d_partials && d_dw && n_images > 0, "snk_conv3x3_wgrad_f16: bad argument");
+    return wgrad_launch(d_x, d_dy, d_x_tail, d_dy_tail, d_partials, d_dw, n_images, height, width, stream, nullptr, nullptr, true);
+}
+
+extern "C" int snk_conv3x3_wgrad_f16_deferred(const float *d_y_below, const float *d_scale, const float *d_shift, const float *d_dy,
+                                              const float *d_x_tail, const float *d_dy_tail, float *d_partials, float *d_dw,
+                                              int n_images, int height, int width, void *stream)
+{
+    SNK_REQUIRE(d_y_below && d_scale && d_shift && d_dy && d_x_tail && d_dy_tail && d_partials && d_dw && n_images > 0,
+                "snk_conv3x3_wgrad_f16_deferred: bad argument");
+    return wgrad_launch(d_y_below, d_dy, d_x_tail, d_dy_tail, d_partials, d_dw, n_images, height, width, stream, d_scale, d_shift, true);
 }
 
 // 1 when the training step may defer the batch norm + ReLU of a residual block's first layer into the kernels that read it

@@ -137,6 +137,15 @@ PROTOTYPES = {
     "snk_bn_train_grad_sums_f64_deferred": (i32, [vp, vp, vp, vp, vp, vp, C.c_long, vp, vp, vp]),
     "snk_bn_train_grad_apply_deferred": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_long, vp, vp, vp]),
     "snk_conv3x3_f16s_igrad_stats_masked_res": (i32, [vp] * 11 + [i32, i32, i32, vp]),
+    # the training step's single-pass f16 mode: the argument lists of the snk_conv3x3_f16s_* / snk_conv3x3_wgrad_f16s* namesakes
+    "snk_conv3x3_f16_stats": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "snk_conv3x3_f16_stats_deferred": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "snk_conv3x3_f16_igrad_stats": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "snk_conv3x3_f16_igrad_stats_deferred": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "snk_conv3x3_f16_igrad_stats_masked_res": (i32, [vp] * 11 + [i32, i32, i32, vp]),
+    "snk_conv3x3_f16_igrad_stats_masked_res_deferred": (i32, [vp] * 12 + [i32, i32, i32, vp]),
+    "snk_conv3x3_wgrad_f16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "snk_conv3x3_wgrad_f16_deferred": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "snk_stem_wgrad_partials": (C.c_long, [i32, i32, i32]),
     "snk_stem_wgrad_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "snk_bn_train_sums_f64": (i32, [vp, C.c_long, vp, vp, vp, vp]),

@@ -43,6 +43,13 @@ Weight images (round 5; ``SNK_TRAIN_BATCH_PREP=0`` turns it off): all tower laye
 two launches per optimizer step (snk_conv3x3_prepare_weights_f16s_train_batch) and kept while the weights stay -- the
 forward-only steps make none.  An image's input scale is written straight into its tail by the kernel that writes the
 convolution's input (``tail_out[l]`` is a view of layer l + 1's forward image, ``tail_dy[l]`` of layer l's input-gradient image).
+
+The single-pass f16 mode (``TrainStep(..., conv="f16")``; ``SNK_TRAIN_CONV=f16`` for ``fit``): every tower convolution pass --
+forward, input gradient, weight gradient -- multiplies only the hi halves, one MFMA per product instead of three
+(snk_conv3x3_f16_*, snk_conv3x3_wgrad_f16*).  An operand v enters the MFMA as f16(v * s), s the power of two the split form uses
+for that tensor; products and sums are float32; every tensor in HBM, the scales taken from the data, the float64 batch-norm
+sums, the deferred batch norm, the mask bytes, the stem, the head and Adam are untouched (include/snake_engine.h states the rule).
+The weight images are the split form's (the kernels read their hi fragments only).  Opt-in; ``conv="f16s"`` is the default.
 """
 import ctypes
 import os
@@ -60,6 +67,8 @@ _RES_MASK = os.environ.get("SNK_TRAIN_RES_MASK", "1") != "0"          # 0: the s
 _HEAD_FUSED = os.environ.get("SNK_TRAIN_HEAD_FUSED", "1") != "0"      # 0: the head's 1x1 convolution in a pass of its own (A/B runs)
 _DEFER_STEM = os.environ.get("SNK_TRAIN_DEFER_STEM", "1") != "0"      # 0: the stem's batch norm + ReLU output is written (A/B runs)
 _DEFER_BN = os.environ.get("SNK_TRAIN_DEFER_BN", "1") != "0"          # 0: every layer's batch norm + ReLU output is written (A/B runs)
+F16_SLABS_ERROR = ("the single-pass f16 training mode (conv=\"f16\", SNK_TRAIN_CONV=f16) and SNK_WGRAD=slabs do not combine: "
+                   "the slab form of the weight gradient has no f16 variant")
 BN_EPS, BN_MOMENTUM, L2_C = 1e-3, 0.99, 1e-5
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-7
 C = 128
@@ -79,8 +88,22 @@ def supported(input_shape, blocks=1):
 
 
 class TrainStep:
-    def __init__(self, weights, input_shape, max_rows, device, dist=None):
+    def __init__(self, weights, input_shape, max_rows, device, dist=None, conv="f16s"):
         self.L = lib()
+        if conv not in ("f16s", "f16"):
+            raise ValueError(f"TrainStep: conv={conv!r} (\"f16s\": float32-accurate split products, \"f16\": one f16 MFMA per product)")
+        if conv == "f16":
+            if os.environ.get("SNK_WGRAD") == "slabs":
+                raise ValueError(F16_SLABS_ERROR)
+        self.conv = conv
+        # the tower's entry points: the split form's, or their single-pass f16 namesakes (same argument lists)
+        fn = lambda name: getattr(self.L, name.replace("f16s", "f16") if conv == "f16" else name)
+        self.c_stats, self.c_stats_deferred = fn("snk_conv3x3_f16s_stats"), fn("snk_conv3x3_f16s_stats_deferred")
+        self.c_igrad, self.c_igrad_deferred = fn("snk_conv3x3_f16s_igrad_stats"), fn("snk_conv3x3_f16s_igrad_stats_deferred")
+        self.c_igrad_masked = fn("snk_conv3x3_f16s_igrad_stats_masked_res")
+        self.c_igrad_masked_deferred = fn("snk_conv3x3_f16s_igrad_stats_masked_res_deferred")
+        self.c_wgrad, self.c_wgrad_deferred = fn("snk_conv3x3_wgrad_f16s"), fn("snk_conv3x3_wgrad_f16s_deferred")
+        self.c_bare = fn("snk_conv3x3_bn_f16s")                 # (the bare convolution without sums: A/B switches, imposed masks)
         self.dev = torch.device(device)
         self.dist = dist
         self.h, self.w = int(input_shape[0]), int(input_shape[1])
@@ -232,7 +255,7 @@ class TrainStep:
                                    _p(self.partials), _p(tail), _p(self.relu_mask[l]), st))
 
     def _conv(self, x, image, res, out, n):
-        check(self.L.snk_conv3x3_bn_f16s(_p(x), _p(image), _p(self.ones), _p(self.zeros), _p(res), _p(out), n, self.h, self.w, 0, self._st()))
+        check(self.c_bare(_p(x), _p(image), _p(self.ones), _p(self.zeros), _p(res), _p(out), n, self.h, self.w, 0, self._st()))
 
     # ---- forward ---------------------------------------------------------------------------------------------------
     def forward(self, x, target, n_global, want_bwd=False):
@@ -258,16 +281,16 @@ class TrainStep:
             if not self.batch_prep:
                 check(L.snk_conv3x3_prepare_weights_f16s_train(_p(self.view[k]), _p(self.img_f[l]), _p(self.tail_out[l - 1]), 0, None, st))
             if self._deferred(l - 1):                             # reads y_{l-1} through layer l - 1's batch norm + ReLU
-                check(L.snk_conv3x3_f16s_stats_deferred(_p(self.y[l - 1]), _p(self.img_f[l]), _p(self.y[l]), _p(self.moving[k + 3]),
+                check(self.c_stats_deferred(_p(self.y[l - 1]), _p(self.img_f[l]), _p(self.y[l]), _p(self.moving[k + 3]),
                                                         _p(self.scale[l - 1]), _p(self.shift[l - 1]),
                                                         _p(self.amax) if self._deferred(l) else None, _p(self.cv_partials),
                                                         _p(self.sums), n, self.h, self.w, st))
             elif self._deferred(l):                               # also takes the maxima its own deferred batch norm is ranged by
-                check(L.snk_conv3x3_f16s_stats_deferred(_p(self.out[l - 1]), _p(self.img_f[l]), _p(self.y[l]), _p(self.moving[k + 3]),
+                check(self.c_stats_deferred(_p(self.out[l - 1]), _p(self.img_f[l]), _p(self.y[l]), _p(self.moving[k + 3]),
                                                         None, None, _p(self.amax), _p(self.cv_partials), _p(self.sums), n, self.h,
                                                         self.w, st))
             elif _CONV_STATS:
-                check(L.snk_conv3x3_f16s_stats(_p(self.out[l - 1]), _p(self.img_f[l]), _p(self.y[l]), _p(self.moving[k + 3]),
+                check(self.c_stats(_p(self.out[l - 1]), _p(self.img_f[l]), _p(self.y[l]), _p(self.moving[k + 3]),
                                                _p(self.cv_partials), _p(self.sums), n, self.h, self.w, st))
             else:
                 self._conv(self.out[l - 1], self.img_f[l], None, self.y[l], n)
@@ -359,11 +382,11 @@ class TrainStep:
             src = B if (masked and not second) else A
             self._bn_backward(l, n, count, want_res=second and not masked, tail=self.tail_dy, have_sums=have_sums, src=src)   # -> dY (+ gres)
             if self._deferred(l - 1):
-                check(L.snk_conv3x3_wgrad_f16s_deferred(_p(self.y[l - 1]), _p(self.scale[l - 1]), _p(self.shift[l - 1]), _p(self.dY),
+                check(self.c_wgrad_deferred(_p(self.y[l - 1]), _p(self.scale[l - 1]), _p(self.shift[l - 1]), _p(self.dY),
                                                         _p(self.tail_out[l - 1]), _p(self.tail_dy), _p(self.wg_partials),
                                                         _p(self.gview[k]), n, self.h, self.w, st))
             else:
-                check(L.snk_conv3x3_wgrad_f16s(_p(self.out[l - 1]), _p(self.dY), _p(self.tail_out[l - 1]), _p(self.tail_dy),
+                check(self.c_wgrad(_p(self.out[l - 1]), _p(self.dY), _p(self.tail_out[l - 1]), _p(self.tail_dy),
                                                _p(self.wg_partials), _p(self.gview[k]), n, self.h, self.w, st))
             if not self.batch_prep:
                 check(L.snk_conv3x3_prepare_weights_f16s_train(_p(self.view[k]), _p(self.img_b), _p(self.tail_dy), 1, _p(self.img_f[l]), st))
@@ -374,22 +397,22 @@ class TrainStep:
             if have_sums and not second and not masked and self._deferred(l - 1):
                 have_sums = False                                 # (deferred stem below, shortcut as a masked copy: no launch takes both)
             if masked and not second and self._deferred(l - 1):
-                check(L.snk_conv3x3_f16s_igrad_stats_masked_res_deferred(_p(self.dY), _p(self.img_b), _p(A), _p(self.relu_mask[l + 1]), _p(A),
+                check(self.c_igrad_masked_deferred(_p(self.dY), _p(self.img_b), _p(A), _p(self.relu_mask[l + 1]), _p(A),
                                                                          _p(self.y[l - 1]), _p(self.scale[l - 1]), _p(self.shift[l - 1]),
                                                                          _p(self.mean[l - 1]), _p(self.inv[l - 1]), _p(self.cv_partials),
                                                                          _p(self.sums), n, self.h, self.w, st))
             elif masked and not second:
-                check(L.snk_conv3x3_f16s_igrad_stats_masked_res(_p(self.dY), _p(self.img_b), _p(A), _p(self.relu_mask[l + 1]), _p(A),
+                check(self.c_igrad_masked(_p(self.dY), _p(self.img_b), _p(A), _p(self.relu_mask[l + 1]), _p(A),
                                                                 _p(self.y[l - 1]), _p(self.relu_mask[l - 1]), _p(self.mean[l - 1]),
                                                                 _p(self.inv[l - 1]), _p(self.cv_partials), _p(self.sums), n, self.h,
                                                                 self.w, st))
             elif have_sums and self._deferred(l - 1):
-                check(L.snk_conv3x3_f16s_igrad_stats_deferred(_p(self.dY), _p(self.img_b), _p(res), _p(dst),
+                check(self.c_igrad_deferred(_p(self.dY), _p(self.img_b), _p(res), _p(dst),
                                                               _p(self.y[l - 1]), _p(self.scale[l - 1]), _p(self.shift[l - 1]),
                                                               _p(self.mean[l - 1]), _p(self.inv[l - 1]), _p(self.cv_partials),
                                                               _p(self.sums), n, self.h, self.w, st))
             elif have_sums:
-                check(L.snk_conv3x3_f16s_igrad_stats(_p(self.dY), _p(self.img_b), _p(res), _p(dst),
+                check(self.c_igrad(_p(self.dY), _p(self.img_b), _p(res), _p(dst),
                                                      _p(self.y[l - 1]), _p(self.relu_mask[l - 1]), _p(self.mean[l - 1]), _p(self.inv[l - 1]),
                                                      _p(self.cv_partials), _p(self.sums), n, self.h, self.w, st))
             else:

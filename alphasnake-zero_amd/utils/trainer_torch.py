@@ -2,7 +2,8 @@
 SURVEY.md section 8 row f-1.  On the GPU a step is sequenced by hand on this library's kernels
 (snake_engine/train_step.py: convolutions, batch norms, head, Adam -- no autograd graph, no library convolution);
 the autograd restatement `_Net` below is the float64 / CPU cross-check of the same formulas (tests/test_trainer_cpu.py)
-and the `SNK_TRAIN_CONV=torch` A/B arm (every operator from PyTorch / MIOpen).
+and the `SNK_TRAIN_CONV=torch` A/B arm (every operator from PyTorch / MIOpen).  `SNK_TRAIN_CONV=f16` runs the hand-sequenced step
+with one f16 MFMA per product in every tower convolution pass (snake_engine/train_step.py, conv="f16"): an option, off by default.
 
 Keras 2.x / TF 2.1 semantics restated (the formulas, not the code; tests/test_trainer_cpu.py cross-checks them against
 an independent float64 NumPy restatement with a hand-written backward pass):
@@ -31,6 +32,7 @@ import torch
 import torch.nn.functional as F
 
 _NATIVE = os.environ.get("SNK_TRAIN_CONV", "native") != "torch"           # `torch`: every operator through PyTorch / MIOpen (A/B runs)
+_CONV_F16 = os.environ.get("SNK_TRAIN_CONV") == "f16"                     # `f16`: the kernels' single-pass f16 mode (unset: the split form)
 # steps at learning rate 0 (alpha_nnet.py:79-84: all after the 100th) cannot move a weight; Adam's moments die with the
 # optimizer (copy_and_compile re-creates it): only the forward half -- the batch-norm moving averages -- is run for them.
 # `full` runs the dead backward passes anyway (the equivalence test, A/B timing)
@@ -184,6 +186,9 @@ def fit(weights, input_shape, X, Y, epochs=32, batch_size=2048, lr_schedule=None
         shuffle=True, dtype=torch.float32):
     """Returns the trained weights (Keras order).  X: (N, h, w, 3) float32, Y: (N, 3) float32 -- on every rank the SAME
     arrays (and the same seed) when torch.distributed is initialised; rank r then works on rows r::world of every batch."""
+    if _CONV_F16 and os.environ.get("SNK_WGRAD") == "slabs":
+        from snake_engine.train_step import F16_SLABS_ERROR
+        raise ValueError(F16_SLABS_ERROR)
     dist = _dist()
     world = dist.get_world_size() if dist is not None else 1
     rank = dist.get_rank() if dist is not None else 0
@@ -204,7 +209,8 @@ def fit(weights, input_shape, X, Y, epochs=32, batch_size=2048, lr_schedule=None
     if _NATIVE and device.type == "cuda" and dtype == torch.float32:
         from snake_engine import train_step
         if train_step.supported(input_shape, (len(weights) - 14) // 10):
-            native = train_step.TrainStep(weights, input_shape, -(-min(batch_size, n) // world), device, dist)
+            native = train_step.TrainStep(weights, input_shape, -(-min(batch_size, n) // world), device, dist,
+                                          conv="f16" if _CONV_F16 else "f16s")
         else:
             import warnings
             warnings.warn(f"fit: no weight-gradient kernel for {tuple(input_shape)} observations (square, width 3 .. 96, at least one "
@@ -215,7 +221,7 @@ def fit(weights, input_shape, X, Y, epochs=32, batch_size=2048, lr_schedule=None
         opt = KerasAdam(params)
     step = 0
     history = []
-    fit.last_mode = "kernels" if native is not None else "autograd"
+    fit.last_mode = ("kernels-f16" if native.conv == "f16" else "kernels") if native is not None else "autograd"
     for ep in range(epochs):
         perm = (torch.randperm(n, generator=gen) if shuffle else torch.arange(n)).to(device)
         tot = torch.zeros((), dtype=torch.float64, device=device)      # the epoch's loss stays on the device: one read per epoch

@@ -625,6 +625,44 @@ int snk_conv3x3_f16s_igrad_stats_masked_res(const float *d_x, const void *d_wS, 
                                             const uint8_t *d_residual_mask, float *d_out, const float *d_y, const uint8_t *d_mask,
                                             const float *d_mean, const float *d_inv, float *d_partials, double *d_sums,
                                             int n_images, int height, int width, void *stream);
+/* ---- the single-pass f16 mode of the training step (alpha_nnet.py:58-59: Keras fit; TrainStep(conv="f16"), SNK_TRAIN_CONV=f16) ----
+ * Mixed-precision training as accelerator stacks offer it: float32 tensors and master weights in HBM, float32 accumulation, ONE
+ * f16 MFMA per product where the float32-accurate forms above issue three (hi*hi + hi*lo + lo*hi).  Opt-in; the default stays the
+ * split form.  The arithmetic rule, stated here, in DESIGN.md section 4 and in tests/test_train_f16_gpu.py:
+ *   - an operand v of a pass enters the MFMA as f16(v * s), round to nearest even; s is the power of two the split form uses for
+ *     that tensor (tail words of the weight image; d_x_tail / d_dy_tail of the weight gradient);
+ *   - a convolution input beyond +-65504 after scaling is clamped and raises the layer's range flag, exactly as in the split form;
+ *   - products are exact in float32, sums are float32, the result is multiplied by the inverse scales as in the split form;
+ *   - nothing else is rounded to 16 bits: activations and gradients written to HBM stay float32, and the batch-norm sums, the
+ *     deferred batch norm, the shortcut mask bytes, the stem, the head and Adam are those of the split form.
+ * Each entry point takes the argument list, the weight image (snk_conv3x3_prepare_weights_f16s_train[_batch]: the kernels read only
+ * its hi fragments) and the partials of its snk_conv3x3_f16s_* / snk_conv3x3_wgrad_f16s* namesake above.  The weight gradient
+ * exists in the window form only: with SNK_WGRAD=slabs, or a shape only the slab form takes, the call fails with a message. */
+int snk_conv3x3_f16_stats(const float *d_x, const void *d_wS, float *d_out, const float *d_center, float *d_partials,
+                          double *d_sums, int n_images, int height, int width, void *stream);
+int snk_conv3x3_f16_stats_deferred(const float *d_x, const void *d_wS, float *d_out, const float *d_center, const float *d_in_scale,
+                                   const float *d_in_shift, float *d_amax, float *d_partials, double *d_sums, int n_images,
+                                   int height, int width, void *stream);
+int snk_conv3x3_f16_igrad_stats(const float *d_x, const void *d_wS, const float *d_residual, float *d_out, const float *d_y,
+                                const uint8_t *d_mask, const float *d_mean, const float *d_inv, float *d_partials,
+                                double *d_sums, int n_images, int height, int width, void *stream);
+int snk_conv3x3_f16_igrad_stats_deferred(const float *d_x, const void *d_wS, const float *d_residual, float *d_out, const float *d_y,
+                                         const float *d_scale, const float *d_shift, const float *d_mean, const float *d_inv,
+                                         float *d_partials, double *d_sums, int n_images, int height, int width, void *stream);
+int snk_conv3x3_f16_igrad_stats_masked_res(const float *d_x, const void *d_wS, const float *d_residual,
+                                           const uint8_t *d_residual_mask, float *d_out, const float *d_y, const uint8_t *d_mask,
+                                           const float *d_mean, const float *d_inv, float *d_partials, double *d_sums,
+                                           int n_images, int height, int width, void *stream);
+int snk_conv3x3_f16_igrad_stats_masked_res_deferred(const float *d_x, const void *d_wS, const float *d_residual,
+                                                    const uint8_t *d_residual_mask, float *d_out, const float *d_y,
+                                                    const float *d_scale, const float *d_shift, const float *d_mean,
+                                                    const float *d_inv, float *d_partials, double *d_sums, int n_images, int height,
+                                                    int width, void *stream);
+int snk_conv3x3_wgrad_f16(const float *d_x, const float *d_dy, const float *d_x_tail, const float *d_dy_tail, float *d_partials,
+                          float *d_dw, int n_images, int height, int width, void *stream);
+int snk_conv3x3_wgrad_f16_deferred(const float *d_y_below, const float *d_scale, const float *d_shift, const float *d_dy,
+                                   const float *d_x_tail, const float *d_dy_tail, float *d_partials, float *d_dw, int n_images,
+                                   int height, int width, void *stream);
 long snk_stem_wgrad_partials(int n_images, int height, int width);
 int snk_stem_wgrad_f32(const float *d_x, const float *d_dy, float *d_partials, float *d_dw, int n_images, int height, int width,
                        void *stream);
