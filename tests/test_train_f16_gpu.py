@@ -94,7 +94,8 @@ def _three_passes(torch, n, hw, xmag, gmag):
     return _PASSES[key]
 
 
-@pytest.mark.parametrize("n,hw,xmag,gmag", [(64, 21, 1.0, 1.0), (48, 21, 30.0, 1e-6), (5, 13, 1e-3, 50.0), (3, 37, 1.0, 1e-4)])
+@pytest.mark.parametrize("n,hw,xmag,gmag", [(64, 21, 1.0, 1.0), (48, 21, 30.0, 1e-6), (5, 13, 1e-3, 50.0), (3, 37, 1.0, 1e-4),
+                                           (41, 37, 1.0, 1.0)])      # the 19x19 batched plan: 9 blocks of 5 / 4 tiles (tests/conv_plan_ref.py)
 def test_three_passes_match_float64_on_the_rounded_operands(torch_gpu, n, hw, xmag, gmag):
     """forward and input gradient on k_conv3x3_f16s<SPLIT = false>, weight gradient on k_wgrad2_f16s<HI> (the two compile-time-width
     forms and the generic one; image counts that leave most of the 128 image groups empty; both ends of the scale range)"""

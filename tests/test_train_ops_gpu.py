@@ -31,7 +31,8 @@ def _tail_of(torch, L, x):
     return image[F16S_TAIL_OFFSET:F16S_TAIL_OFFSET + 16].view(torch.float32).clone()
 
 
-@pytest.mark.parametrize("n,hw,xmag,gmag", [(64, 21, 1.0, 1.0), (48, 21, 30.0, 1e-6), (5, 13, 1e-3, 50.0), (3, 37, 1.0, 1e-4)])
+@pytest.mark.parametrize("n,hw,xmag,gmag", [(64, 21, 1.0, 1.0), (48, 21, 30.0, 1e-6), (5, 13, 1e-3, 50.0), (3, 37, 1.0, 1e-4),
+                                           (41, 37, 1.0, 1.0)])      # the 19x19 batched plan: 9 blocks of 5 / 4 tiles (tests/conv_plan_ref.py)
 def test_tower_convolution_three_passes_match_float64(torch_gpu, n, hw, xmag, gmag):
     """forward and input gradient on k_conv3x3_f16s (snk_conv3x3_prepare_weights_f16s_train: the mirrored kernel is laid out by
     the library), weight gradient on k_wgrad_f16s, with the power-of-two scales taken from the data on the device"""
@@ -222,10 +223,11 @@ def _net64(torch, ws, X, Y):
     return float(loss), dict(zip(pidx, grads)), pre, q.detach(), n_conv
 
 
-@pytest.mark.parametrize("n,blocks,hw", [(40, 2, 21), (23, 4, 21), (5, 1, 37), (9, 1, 13), (3, 10, 37)])
+@pytest.mark.parametrize("n,blocks,hw", [(40, 2, 21), (23, 4, 21), (5, 1, 37), (9, 1, 13), (3, 10, 37), (41, 1, 37)])
 def test_one_whole_step_matches_float64_with_the_same_relu_masks(torch_gpu, n, blocks, hw):
-    """hw = 37: BASELINE configs[4]'s 19 x 19 board (its weight gradient runs in slabs of five image rows; the last case is that
-    config's 10-block net), 13: a 7 x 7 board"""
+    """hw = 37: BASELINE configs[4]'s 19 x 19 board (its weight gradient runs in slabs of five image rows; (3, 10, 37) is that
+    config's 10-block net; n = 41 is the smallest batch whose convolutions run that canvas's batched plan, nine blocks of 5 or 4
+    M tiles per image -- tests/conv_plan_ref.py), 13: a 7 x 7 board"""
     torch = torch_gpu
     from snake_engine import net
     from snake_engine.train_step import TrainStep
@@ -337,7 +339,8 @@ def test_a_net_without_residual_blocks_is_fitted_off_the_kernels_and_says_so(tor
         train_step.TrainStep(ws, (21, 21, 3), 8, "cuda")
 
 
-@pytest.mark.parametrize("n,blocks,hw", [(24, 2, 21), (6, 1, 37), (10, 2, 13)])
+@pytest.mark.parametrize("n,blocks,hw", [(24, 2, 21), (6, 1, 37), (10, 2, 13),
+                                         (41, 1, 37)])     # MODE 5 in the 5-tile body, blocks 7 and 8 of an image with 4 tiles
 def test_batch_norm_backward_sums_in_the_input_gradient_epilogue_change_nothing_but_rounding(torch_gpu, monkeypatch, n, blocks, hw):
     """round 5: the input-gradient convolution of layer l also takes the two sums layer l - 1's batch-norm backward starts with
     (snk_conv3x3_f16s_igrad_stats) instead of snk_bn_train_grad_sums_f64 reading the gradient, the pre-batch-norm tensor and the
@@ -379,7 +382,7 @@ def test_batch_norm_backward_sums_in_the_input_gradient_epilogue_change_nothing_
         assert err <= 1e-5 * max(ref.abs().max().item(), 1e-12), (err, ref.abs().max().item())
 
 
-@pytest.mark.parametrize("n,hw", [(5, 21), (3, 13), (2, 37)])
+@pytest.mark.parametrize("n,hw", [(5, 21), (3, 13), (2, 37), (41, 37)])      # (41, 37): the 5-tile body, its last block 4 tiles + 25 rows
 def test_input_gradient_epilogue_reads_nothing_behind_the_last_image(torch_gpu, monkeypatch, n, hw):
     """ADVICE round 5, finding 1.  The input-gradient epilogue (conv_split.hip, MODE 5 / 8) steps from row to row through the buffer
     instructions' SGPR soffset and relies on the image's descriptor to return zero for rows past the image (hw * hw is no multiple
