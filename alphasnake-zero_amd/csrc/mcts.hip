@@ -324,16 +324,19 @@ __global__ void k_tt_rebuild(snk_tt Old, snk_tt New, int now, int max_age)
         const int t = __float_as_int(so[6]);
         if (now - t > max_age) continue;
         uint64_t slot = klo & New.mask;
+        bool placed = false;
         for (uint64_t probes = 0; probes <= New.cap; ++probes) {
             if (atomicCAS(&New.key_lo[slot], 0ull, klo) == 0ull) {
                 New.key_hi[slot] = Old.key_hi[s];
                 float *sn = &New.stat[slot * 8];
                 for (int k = 0; k < 8; ++k) sn[k] = so[k];
                 atomicAdd(&New.d_ctrl[0], 1);
+                placed = true;
                 break;
             }
             slot = (slot + 1) & New.mask;
         }
+        if (!placed) atomicExch(&New.d_ctrl[1], 1);      // more survivors than slots: the new table reports itself full
     }
 }
 

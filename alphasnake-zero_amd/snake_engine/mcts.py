@@ -126,7 +126,9 @@ class DeviceMCTS:
             self.moves = torch.empty((m,), dtype=torch.uint8, device=dev)
             self.est = torch.empty((m,), dtype=torch.float32, device=dev)
             self.pmf = torch.empty((m, 3), dtype=torch.float32, device=dev)
-            self.path_entry = torch.empty((m, D), dtype=torch.int32, device=dev)
+            # -1 = none: on a first turn a root row whose lookup overflowed is never written by select and reads as none in
+            # snk_tt_read_q (on later turns it reads the previous turn's index: in bounds, capacities only grow; end_of_turn raises)
+            self.path_entry = torch.full((m, D), -1, dtype=torch.int32, device=dev)
             self.path_move = torch.empty((m, D), dtype=torch.uint8, device=dev)
             self.path_len = torch.zeros((m,), dtype=torch.int32, device=dev)
             self.alive_rows = torch.empty((B, S), dtype=torch.uint8, device=dev)

@@ -395,7 +395,9 @@ int snk_tt_destroy(snk_tt *t);
 int snk_tt_clear(snk_tt *t, void *stream);                              /* Agent.clear, agent.py:140-147 */
 int snk_tt_status_sync(snk_tt *t, int64_t *capacity, int64_t *occupied, int *overflowed);
 /* eviction (agent.py:101-110): keeps entries with now_turn - last_touch <= max_age, re-hashed into a
- * table of new_capacity.  Entry indices change: call between root turns only.                    */
+ * table of new_capacity.  Entry indices change: call between root turns only.  A survivor that
+ * finds no free slot (new_capacity below the number of survivors) is dropped and sets the new
+ * table's overflow flag, which snk_tt_status_sync reports.                                       */
 int snk_tt_rebuild_sync(snk_tt *t, uint64_t new_capacity, int now_turn, int max_age);
 /* MCTSAgent.make_moves "get states without duplicates" (agent.py:170-186): find-or-insert m keys.
  * d_active (optional) uint8[m]: 0 rows are skipped (entry = none).  d_is_new[i] = 1 for exactly one
