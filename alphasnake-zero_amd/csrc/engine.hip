@@ -705,8 +705,11 @@ __global__ __launch_bounds__(WPB * 64) void k_observe(const uint8_t *__restrict_
                                                           float *__restrict__ planes, uint8_t *__restrict__ mask_out,
                                                           uint64_t *__restrict__ key_out, int legacy_mask, int reps,
                                                           const int32_t *__restrict__ index, const uint8_t *__restrict__ sub_active,
-                                                          uint8_t *__restrict__ row_active)
+                                                          uint8_t *__restrict__ row_active, const uint8_t *__restrict__ mirror)
 {
+    // mirror (optional): mirror[i] != 0 writes row i's planes flipped on the W axis, numpy.flip(states, axis=2) of the trainer's
+    // augmentation (trainer.py:93-97): the board cells go to column N-1-j AFTER the rot90 map; the wall background and the centre
+    // pixel are symmetric.  Planes only: mask and key of a mirrored row are not defined (snk_engine_observe_mirror passes neither).
     // index (optional): output row i observes pairs[index[i]] (the rollout tick's rows to evaluate: no gathered copy of the pairs);
     // row_active (optional, with sub_active): row_active[i] = the observing snake is alive AND sub_active[its slot] -- the tick's
     // "which rows are live" (mp_game_runner.py:99-103) taken where the record is in hand instead of by two launches of its own
@@ -742,6 +745,7 @@ __global__ __launch_bounds__(WPB * 64) void k_observe(const uint8_t *__restrict_
     for (int rep = 0; rep < reps; ++rep) {
     const int pi = pi0 + rep;
     const bool valid = pi < m;
+    const bool mir = mirror && valid && mirror[pi];
     uint8_t *g = smem + (wv * GPW + gq) * (!planes ? lds_per_obs(L) : layout == SNK_NHWC_F32 ? lds_per_wave_win(L) : lds_per_wave_obs(L));
     float *v1 = (float *)(g + obs_rec_bytes(L));            // channel 1 per board cell: 0.02 x the largest tail-distance of a node on it
     float *v0 = v1 + L.nc_pad;                              // channel 0 per board cell: the head value of the snake whose head is here
@@ -885,6 +889,7 @@ __global__ __launch_bounds__(WPB * 64) void k_observe(const uint8_t *__restrict_
                 else if (k == 1) { i = N - 1 - sj; j = si; }
                 else if (k == 2) { i = N - 1 - si; j = N - 1 - sj; }
                 else { i = sj; j = N - 1 - si; }
+                if (mir) j = N - 1 - j;                // (the window rows qa..qb depend on i alone and hold all N columns)
                 float *px = cvs + (3 * (i * N + j) + base);
                 px[0] = v0[c]; px[1] = v1[c]; px[2] = food_bit(food, c) ? fval : 0.0f;
             }
@@ -951,6 +956,7 @@ __global__ __launch_bounds__(WPB * 64) void k_observe(const uint8_t *__restrict_
                 else if (k == 1) { i = N - 1 - sj; j = si; }
                 else if (k == 2) { i = N - 1 - si; j = N - 1 - sj; }
                 else { i = sj; j = N - 1 - si; }
+                if (mir) j = N - 1 - j;
                 const int pp = i * N + j;
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch)
@@ -1280,7 +1286,7 @@ extern "C" int snk_engine_alive(const snk_engine *e, const int32_t *d_slots, int
 
 static int engine_observe(const snk_engine *e, const int32_t *d_pairs, const int32_t *d_index, int m, int layout, float *d_planes,
                           uint8_t *d_mask, uint64_t *d_key, int legacy_mask, const uint8_t *d_sub_active, uint8_t *d_row_active,
-                          void *stream);
+                          void *stream, const uint8_t *d_mirror = nullptr);
 extern "C" int snk_engine_observe(const snk_engine *e, const int32_t *d_pairs, int m, int layout,
                                   float *d_planes, uint8_t *d_mask, uint64_t *d_key, int legacy_mask, void *stream)
 {
@@ -1293,9 +1299,16 @@ extern "C" int snk_engine_observe_rows(const snk_engine *e, const int32_t *d_pai
     SNK_REQUIRE((d_row_active == nullptr) == (d_sub_active == nullptr), "snk_engine_observe_rows: d_row_active needs d_sub_active (and the other way round)");
     return engine_observe(e, d_pairs, d_index, m, layout, d_planes, d_mask, d_key, legacy_mask, d_sub_active, d_row_active, stream);
 }
+// the trainer's mirror augmentation (trainer.py:93-97) taken where the observation is encoded: flagged rows come out W-flipped
+extern "C" int snk_engine_observe_mirror(const snk_engine *e, const int32_t *d_pairs, const int32_t *d_index, const uint8_t *d_mirror,
+                                         int m, int layout, float *d_planes, void *stream)
+{
+    SNK_REQUIRE(m <= 0 || d_planes != nullptr, "snk_engine_observe_mirror: d_planes is NULL");
+    return engine_observe(e, d_pairs, d_index, m, layout, d_planes, nullptr, nullptr, 0, nullptr, nullptr, stream, d_mirror);
+}
 static int engine_observe(const snk_engine *e, const int32_t *d_pairs, const int32_t *d_index, int m, int layout, float *d_planes,
                           uint8_t *d_mask, uint64_t *d_key, int legacy_mask, const uint8_t *d_sub_active, uint8_t *d_row_active,
-                          void *stream)
+                          void *stream, const uint8_t *d_mirror)
 {
     SNK_REQUIRE(e != nullptr, "snk_engine_observe: engine is NULL");
     SNK_REQUIRE(layout == SNK_NHWC_F32 || layout == SNK_NCHW_F32 || layout == SNK_NCHW_BF16, "snk_engine_observe: unknown layout %d", layout);
@@ -1309,16 +1322,16 @@ static int engine_observe(const snk_engine *e, const int32_t *d_pairs, const int
         constexpr int WPB = 4;
         const size_t lds = (size_t)WPB * 4 * lds_per_obs(L);
         const int grid = (m + WPB * 4 - 1) / (WPB * 4);
-        if (L.H == 11) k_observe<11, 11, 16, WPB><<<grid, WPB * 64, lds, (hipStream_t)stream>>>(e->d_state, L, d_pairs, m, layout, d_planes, d_mask, d_key, legacy_mask, 1, d_index, d_sub_active, d_row_active);
-        else if (L.H == 7) k_observe<7, 7, 16, WPB><<<grid, WPB * 64, lds, (hipStream_t)stream>>>(e->d_state, L, d_pairs, m, layout, d_planes, d_mask, d_key, legacy_mask, 1, d_index, d_sub_active, d_row_active);
-        else k_observe<0, 0, 16, WPB><<<grid, WPB * 64, lds, (hipStream_t)stream>>>(e->d_state, L, d_pairs, m, layout, d_planes, d_mask, d_key, legacy_mask, 1, d_index, d_sub_active, d_row_active);
+        if (L.H == 11) k_observe<11, 11, 16, WPB><<<grid, WPB * 64, lds, (hipStream_t)stream>>>(e->d_state, L, d_pairs, m, layout, d_planes, d_mask, d_key, legacy_mask, 1, d_index, d_sub_active, d_row_active, d_mirror);
+        else if (L.H == 7) k_observe<7, 7, 16, WPB><<<grid, WPB * 64, lds, (hipStream_t)stream>>>(e->d_state, L, d_pairs, m, layout, d_planes, d_mask, d_key, legacy_mask, 1, d_index, d_sub_active, d_row_active, d_mirror);
+        else k_observe<0, 0, 16, WPB><<<grid, WPB * 64, lds, (hipStream_t)stream>>>(e->d_state, L, d_pairs, m, layout, d_planes, d_mask, d_key, legacy_mask, 1, d_index, d_sub_active, d_row_active, d_mirror);
     } else {
         const size_t lds = (size_t)WAVES_PER_BLOCK * (!d_planes ? lds_per_obs(L) : layout == SNK_NHWC_F32 ? lds_per_wave_win(L) : lds_per_wave_obs(L));
         // several observations per wavefront once the request fills the chip's wave slots (256 CUs x 32) a few times over
         static const int reps_env = getenv("SNK_OBS_REPS") ? atoi(getenv("SNK_OBS_REPS")) : 0;
         const int reps = reps_env > 0 ? reps_env : (d_planes && m >= 4 * 8192) ? 2 : 1;
         DISPATCH_BOARD(L, (k_observe<BH, BW, 64, WAVES_PER_BLOCK><<<wave_grid((m + reps - 1) / reps), BLOCK_THREADS, lds, (hipStream_t)stream>>>(
-            e->d_state, L, d_pairs, m, layout, d_planes, d_mask, d_key, legacy_mask, reps, d_index, d_sub_active, d_row_active)));
+            e->d_state, L, d_pairs, m, layout, d_planes, d_mask, d_key, legacy_mask, reps, d_index, d_sub_active, d_row_active, d_mirror)));
     }
     SNK_CHECK_HIP(hipGetLastError());
     return 0;

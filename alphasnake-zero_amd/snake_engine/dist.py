@@ -18,6 +18,14 @@ def shard_range(total, rank, world):
 # global NumPy / random state exactly where a one-rank run leaves it (the reference draws nothing here, trainer.py:63-75)
 _seed_stream = np.random.Generator(np.random.PCG64())
 
+
+def seed(n):
+    """re-seed the stream the ranks' shared seed is drawn from (gather_counts).  The default is OS entropy, so the hypergeometric
+    top-up of share_counts -- which rank gives how many extra rows when one is short of its share -- differs from run to run; it
+    is repeatable only after dist.seed(n), called on rank 0 at least (rank 0's draw is the one all ranks use)."""
+    global _seed_stream
+    _seed_stream = np.random.Generator(np.random.PCG64(int(n)))
+
 BATCH_ROWS = 2048          # trainer.py:63
 MAX_BATCHES = 5            # trainer.py:65
 

@@ -138,11 +138,21 @@ class Engine:
 
     # ---- Game.get_states + obstacle mask + transposition key ----------------------------------
     def observe(self, pairs, m=None, planes=None, mask=None, key=None, layout=NHWC_F32, legacy_mask=False, index=None,
-                sub_active=None, row_active=None):
+                sub_active=None, row_active=None, mirror=None):
         """index: int32[m], row i observes pairs[index[i]]; sub_active uint8[n_slots] + row_active uint8[m]: row_active[i] = the
-        observing snake is alive and its slot is active (snk_engine_observe_rows: the rollout tick's forms)"""
+        observing snake is alive and its slot is active (snk_engine_observe_rows: the rollout tick's forms);
+        mirror: uint8[m], rows with mirror[i] != 0 are written flipped on the W axis (snk_engine_observe_mirror: planes only)"""
         pairs = self._i32(pairs)
         m = pairs.shape[0] if m is None else m
+        if mirror is not None:
+            if mask is not None or key is not None or row_active is not None or sub_active is not None:
+                raise ValueError("observe: mirror writes planes only -- the mask, key and row_active of a mirrored row are not defined")
+            if planes is None:
+                raise ValueError("observe: mirror needs planes")
+            assert mirror.dtype == torch.uint8 and mirror.is_cuda and mirror.is_contiguous() and mirror.numel() >= m
+            assert index is None or (index.dtype == torch.int32 and index.is_cuda and index.is_contiguous() and index.numel() >= m)
+            check(self.L.snk_engine_observe_mirror(self.h, _ptr(pairs), _ptr(index), _ptr(mirror), m, layout, _ptr(planes), _stream()))
+            return
         if index is None and row_active is None:
             check(self.L.snk_engine_observe(self.h, _ptr(pairs), m, layout, _ptr(planes), _ptr(mask), _ptr(key),
                                             int(legacy_mask), _stream()))

@@ -113,13 +113,23 @@ class _Records(Sequence):
     def __len__(self):
         return self._a._n_records
 
-    def fetch_device(self, indices):
+    def fetch_device(self, indices, mirror=None):
         """the observations of the given records as one device tensor [k, 2H-1, 2W-1, 3] (no host round trip: what the
-        iteration-end all-gather sends)"""
+        iteration-end all-gather sends).  mirror (optional): one bool per index; those rows come out flipped on the W axis
+        (the trainer's augmentation, trainer.py:93-97, written by the launch that encodes them)"""
         a = self._a
         idx = np.asarray(indices, np.int64)
         pairs = a._rec_pairs_host()[idx]
-        planes, _, _ = a._rec_engine.observe_all(pairs.astype(np.int32), want_mask=False, want_key=False)
+        eng = a._rec_engine
+        if mirror is None:
+            planes, _, _ = eng.observe_all(pairs.astype(np.int32), want_mask=False, want_key=False)
+            return planes
+        flags = np.ascontiguousarray(np.asarray(mirror, bool).reshape(-1), np.uint8)
+        if len(flags) != len(idx):
+            raise ValueError(f"fetch_device: {len(flags)} mirror flags for {len(idx)} indices")
+        planes = eng.new((len(idx),) + tuple(eng.obs_shape), torch.float32)
+        if len(idx):
+            eng.observe(pairs.astype(np.int32), len(idx), planes, mirror=torch.as_tensor(flags, device=planes.device))
         return planes
 
     def fetch(self, indices):

@@ -105,8 +105,12 @@ class AlphaNNet:
     # ---- training half --------------------------------------------------------------
     def train(self, X, Y, epochs=32, batch_size=2048):
         from utils import trainer_torch
-        ws = trainer_torch.fit(self._qnet.get_weights(), self.input_shape, np.array(X, np.float32), np.array(Y, np.float32),
-                               epochs, batch_size, self.lr_schedule)
+        # device tensors (the trainer's SNK_TRAIN_DATA=device form) go through as they are; lists become one array as before
+        if not torch.is_tensor(X):
+            X = np.array(X, np.float32)
+        if not torch.is_tensor(Y):
+            Y = np.array(Y, np.float32)
+        ws = trainer_torch.fit(self._qnet.get_weights(), self.input_shape, X, Y, epochs, batch_size, self.lr_schedule)
         self._qnet.set_weights(ws)
 
     def copy_and_compile(self, learning_rate=0.0001, TPU=None):

@@ -7,7 +7,10 @@ recorded (state, Q) rows drawn without replacement (:63-72), mirror augmentation
 Q[left] and Q[right], :93-100), ``copy_and_compile(lr).train`` (:79-83), ``lr *= decay`` (:85), ``models/<name><n>.h5``
 (:89-91).  The health curriculum is 9 for generations <= 8, 3 up to 32, 1 afterwards (:42-47).
 
-Same constructor and ``train(nnet, name, iteration)`` signature; two additions, both inert by default:
+Same constructor and ``train(nnet, name, iteration)`` signature; three additions, all inert by default:
+  * ``SNK_TRAIN_DATA=device`` (read when the trainer is constructed): the sampled training set stays in HBM from the records to the
+    fit -- the observe kernel writes the mirror images in the launch that encodes the rows, and ``nnet.train`` receives two device
+    tensors with the rows and bits of the host form's lists (the default: the reference's Python lists of host arrays);
   * ``max_iterations`` (keyword of ``train``): stop after that many generations instead of looping for ever (tests);
   * several GPUs: when ``torch.distributed`` is initialised (one process per GPU, ``torchrun train.py``) the games are
     cut into per-rank shards, every rank samples its share of the rows, the rows are all-gathered and the six counters
@@ -16,6 +19,7 @@ Same constructor and ``train(nnet, name, iteration)`` signature; two additions, 
 One deliberate difference: with fewer than 2 048 records the reference draws zero samples and fails inside ``flip`` (its
 ``samples > len(records)`` branch can never be taken); here all records form one batch, which is what that branch says.
 """
+import os
 from random import sample
 from time import time
 
@@ -46,6 +50,10 @@ class AlphaSnakeZeroTrainer:
         self.width = width
         self.snake_cnt = snake_cnt
         self.TPU = TPU               # accepted for signature parity; there is no TPU path
+        mode = os.environ.get("SNK_TRAIN_DATA", "") or "host"
+        if mode not in ("host", "device"):
+            raise ValueError(f"SNK_TRAIN_DATA={mode!r}: expected 'host' (the default) or 'device'")
+        self.train_data = mode
 
     # ---- pieces of one generation -------------------------------------------------------------------
     @staticmethod
@@ -93,6 +101,8 @@ class AlphaSnakeZeroTrainer:
 
     def _collect(self, alice):
         """trainer.py:63-77: (X, V, batch_size) with the mirror images appended"""
+        if self.train_data == "device":
+            return self._collect_device(alice)
         from snake_engine.dist import sample_plan
         n = len(alice.records)
         dist = _dist()
@@ -126,6 +136,47 @@ class AlphaSnakeZeroTrainer:
         X += self.mirror_states(X)
         V += self.mirror_values(V)
         return X, V, batch_size
+
+    def _collect_device(self, alice):
+        """_collect without the host detour: X [2k, 2H-1, 2W-1, 3] and V [2k, 3] as float32 device tensors whose rows and bits
+        equal np.array of the lists _collect returns (same draws from the same generators, same row order: the k sampled rows,
+        then their mirror images)"""
+        import torch
+        from snake_engine.dist import sample_plan
+        if not hasattr(alice.records, "fetch_device"):
+            raise TypeError("SNK_TRAIN_DATA=device needs the engine-backed records of utils.agent.Agent (records.fetch_device)")
+        n = len(alice.records)
+        dist = _dist()
+        if dist is None:
+            wanted, batch_size, _ = sample_plan(n, 1)
+            picked = sample(range(n), wanted)
+            # one observe launch writes the whole augmented set: the second half of the rows is flagged to come out W-flipped
+            X = alice.records.fetch_device(picked + picked, mirror=[False] * wanted + [True] * wanted)
+            Vd = torch.as_tensor(alice._values_host()[np.asarray(picked, np.int64)], device=X.device)
+            V = torch.cat([Vd, Vd.flip(1)])
+        else:
+            from snake_engine.dist import gather_counts, share_counts, sample_share, all_gather_samples
+            world = dist.get_world_size()
+            counts, seed = gather_counts(n)                   # (see _collect: all ranks raise together)
+            n_all, n_empty = sum(counts), sum(c == 0 for c in counts)
+            if n_empty:
+                raise RuntimeError(f"{n_empty} of {world} ranks recorded no state to sample from (this rank: {n} records)")
+            wanted, batch_size, _ = sample_plan(n_all, world)
+            rows = share_counts(counts, wanted, seed)
+            idx = sample_share(n, rows[dist.get_rank()], np.random.RandomState(np.random.randint(1 << 31)))
+            Xd = alice.records.fetch_device(idx)
+            Vd = torch.as_tensor(alice._values_host()[idx], device=Xd.device)
+            Xg, Vg = all_gather_samples(Xd, Vd, rows)
+            X, V = self.mirror_device(Xg, Vg)
+        alice.clear()
+        return X, V, batch_size
+
+    @staticmethod
+    def mirror_device(Xg, Vg):
+        """the gathered rows followed by their mirror images, on the device the gather returned: what ``X += mirror_states(X)``
+        and ``V += mirror_values(V)`` make of the host lists"""
+        import torch
+        return torch.cat([Xg, torch.flip(Xg, dims=[2])]), torch.cat([Vg, torch.flip(Vg, dims=[1])])
 
     # ---- the loop train.py starts ----------------------------------------------------------------------
     def train(self, nnet, name="AlphaSnake", iteration=0, max_iterations=None):

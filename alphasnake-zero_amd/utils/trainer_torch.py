@@ -184,7 +184,7 @@ class KerasAdam:
 
 def fit(weights, input_shape, X, Y, epochs=32, batch_size=2048, lr_schedule=None, device=None, seed=None, verbose=True,
         shuffle=True, dtype=torch.float32):
-    """Returns the trained weights (Keras order).  X: (N, h, w, 3) float32, Y: (N, 3) float32 -- on every rank the SAME
+    """Returns the trained weights (Keras order).  X: (N, h, w, 3) float32, Y: (N, 3) float32, arrays or torch tensors -- on every rank the SAME
     arrays (and the same seed) when torch.distributed is initialised; rank r then works on rows r::world of every batch."""
     if _CONV_F16 and os.environ.get("SNK_WGRAD") == "slabs":
         from snake_engine.train_step import F16_SLABS_ERROR
@@ -195,8 +195,9 @@ def fit(weights, input_shape, X, Y, epochs=32, batch_size=2048, lr_schedule=None
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
     device = torch.device(device)
-    Xd = torch.as_tensor(np.ascontiguousarray(X), dtype=dtype, device=device)
-    Yd = torch.as_tensor(np.ascontiguousarray(Y), dtype=dtype, device=device)
+    # torch tensors (already on the device when the trainer collected them there) take no NumPy round trip
+    Xd = X.to(device=device, dtype=dtype).contiguous() if torch.is_tensor(X) else torch.as_tensor(np.ascontiguousarray(X), dtype=dtype, device=device)
+    Yd = Y.to(device=device, dtype=dtype).contiguous() if torch.is_tensor(Y) else torch.as_tensor(np.ascontiguousarray(Y), dtype=dtype, device=device)
     n = Xd.shape[0]
     if seed is None:
         s = torch.tensor([int(np.random.randint(1 << 31))], dtype=torch.int64, device=device if dist is not None and dist.get_backend() == "nccl" else "cpu")

@@ -149,6 +149,13 @@ int snk_engine_observe(const snk_engine *e, const int32_t *d_pairs, int m, int l
 int snk_engine_observe_rows(const snk_engine *e, const int32_t *d_pairs, const int32_t *d_index, int m, int layout,
                             float *d_planes, uint8_t *d_mask, uint64_t *d_key, int legacy_mask,
                             const uint8_t *d_sub_active, uint8_t *d_row_active, void *stream);
+/* Game.make_state (game.py:215-257) + the trainer's mirror augmentation, np.flip(states, axis=2) (trainer.py:93-97), in the one
+ * launch that encodes the sampled rows: output row i observes d_pairs[d_index ? d_index[i] : i] and, where d_mirror[i] != 0
+ * (d_mirror: uint8[m], one flag per OUTPUT row; NULL = no row), is written flipped on the W axis -- the flip comes after the rot90
+ * that turns the snake to face up, so it is no rotation of its own.  All three layouts; planes only (the mask and key of a
+ * mirrored row are not defined).  A pair naming a dead snake yields zero planes, mirrored or not.                              */
+int snk_engine_observe_mirror(const snk_engine *e, const int32_t *d_pairs, const int32_t *d_index,
+                              const uint8_t *d_mirror, int m, int layout, float *d_planes, void *stream);
 
 /* ---- host views (goldens, Game.snakes / .food / .rewards accessors, Game.draw) -----------
  * Synchronous.  h_slots: host int32[n] or NULL.                                               */
