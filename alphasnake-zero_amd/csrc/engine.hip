@@ -1105,6 +1105,105 @@ __global__ __launch_bounds__(CMP_THREADS) void k_cmp_one(const uint8_t *__restri
     if (threadIdx.x == 0) *count = total;
 }
 
+// ------------------------------------------------------------------------------------------
+// the pit's row list and verdict (pit_mp_game_runner.py:23-35, 39-62) on the device: games are slots 0..n-1, `live` marks the
+// games whose verdict is still open, snakes with id < a_cnt are team A
+// ------------------------------------------------------------------------------------------
+#define PIT_ITEMS 4
+#define PIT_TILE (CMP_THREADS * PIT_ITEMS)      // games per block
+
+// bit s = snake s of game gi is alive; 0 for a game that is closed (or past the end)
+__device__ static inline uint32_t pit_alive_bits(const uint8_t *__restrict__ state, const Layout &L, const uint8_t *live, int gi, int n)
+{
+    if (gi >= n || !live[gi]) return 0u;
+    const SnakeMeta *meta = (const SnakeMeta *)(state + (size_t)gi * L.stride + L.meta_off);
+    uint32_t b = 0u;
+    for (int s = 0; s < L.S; ++s) b |= (meta[s].alive ? 1u : 0u) << s;
+    return b;
+}
+
+// rows of each team in the block's PIT_TILE games: tile_sums[2 b] team A, [2 b + 1] team B
+__global__ __launch_bounds__(CMP_THREADS) void k_pit_count(const uint8_t *__restrict__ state, Layout L, const uint8_t *__restrict__ live,
+                                                           int n, uint32_t a_bits, int32_t *__restrict__ tile_sums)
+{
+    __shared__ int sh[8];
+    const int base = blockIdx.x * PIT_TILE + threadIdx.x * PIT_ITEMS;
+    int ca = 0, cb = 0;
+    for (int q = 0; q < PIT_ITEMS; ++q) {
+        const uint32_t b = pit_alive_bits(state, L, live, base + q, n);
+        ca += __popc(b & a_bits);
+        cb += __popc(b & ~a_bits);
+    }
+    int ta, tb;
+    block_exclusive_scan_256(ca, &ta, sh);
+    block_exclusive_scan_256(cb, &tb, sh);
+    if (threadIdx.x == 0) { tile_sums[2 * blockIdx.x] = ta; tile_sums[2 * blockIdx.x + 1] = tb; }
+}
+
+// single block: exclusive scan of both columns of the tile sums (any count, 256 tiles at a time); counts = {nA, nB}
+__global__ __launch_bounds__(CMP_THREADS) void k_pit_scan(int32_t *__restrict__ tile_sums, int n_tiles, int32_t *__restrict__ counts)
+{
+    __shared__ int sh[8];
+    int carry_a = 0, carry_b = 0;
+    for (int b = 0; b < n_tiles; b += CMP_THREADS) {
+        const int i = b + threadIdx.x;
+        const int va = i < n_tiles ? tile_sums[2 * i] : 0, vb = i < n_tiles ? tile_sums[2 * i + 1] : 0;
+        int ta, tb;
+        const int ea = block_exclusive_scan_256(va, &ta, sh);
+        const int eb = block_exclusive_scan_256(vb, &tb, sh);
+        if (i < n_tiles) { tile_sums[2 * i] = carry_a + ea; tile_sums[2 * i + 1] = carry_b + eb; }
+        carry_a += ta; carry_b += tb;
+    }
+    if (threadIdx.x == 0) { counts[0] = carry_a; counts[1] = carry_b; }
+}
+
+// team-A rows at [0, nA), team-B rows at [nA, nA + nB); inside a team games ascending, ids ascending (ids_A + ids_B)
+__global__ __launch_bounds__(CMP_THREADS) void k_pit_scatter(const uint8_t *__restrict__ state, Layout L, const uint8_t *__restrict__ live,
+                                                             int n, uint32_t a_bits, const int32_t *__restrict__ tile_offs,
+                                                             const int32_t *__restrict__ counts, int32_t *__restrict__ pairs)
+{
+    __shared__ int sh[8];
+    const int base = blockIdx.x * PIT_TILE + threadIdx.x * PIT_ITEMS;
+    uint32_t bits[PIT_ITEMS];
+    int ca = 0, cb = 0;
+    for (int q = 0; q < PIT_ITEMS; ++q) {
+        bits[q] = pit_alive_bits(state, L, live, base + q, n);
+        ca += __popc(bits[q] & a_bits);
+        cb += __popc(bits[q] & ~a_bits);
+    }
+    int ta, tb;
+    int pa = tile_offs[2 * blockIdx.x] + block_exclusive_scan_256(ca, &ta, sh);
+    int pb = counts[0] + tile_offs[2 * blockIdx.x + 1] + block_exclusive_scan_256(cb, &tb, sh);
+    for (int q = 0; q < PIT_ITEMS; ++q) {
+        for (uint32_t b = bits[q]; b; b &= b - 1u) {          // a closed or absent game has no bit set
+            const int s = __ffs((int)b) - 1;
+            const int pos = ((a_bits >> s) & 1u) ? pa++ : pb++;
+            pairs[2 * (size_t)pos] = base + q;
+            pairs[2 * (size_t)pos + 1] = s;
+        }
+    }
+}
+
+// the verdict of one turn (pit_mp_game_runner.py:39-62), a thread per game
+__global__ void k_pit_verdict(const uint8_t *__restrict__ state, Layout L, const uint8_t *__restrict__ done,
+                              const int8_t *__restrict__ rewards, int n, uint32_t a_bits, int turn, uint8_t *live,
+                              int32_t *__restrict__ winner, int32_t *__restrict__ length)
+{
+    const int gi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gi >= n || !live[gi]) return;
+    int w = -1;
+    if (done[gi]) {                                           // :43-47 the last id whose reward is +1, None without one
+        for (int s = 0; s < L.S; ++s) if (rewards[(size_t)gi * L.S + s] == 1) w = s;
+    } else {                                                  // :48-60 a team without snakes: the first alive id wins
+        const uint32_t b = pit_alive_bits(state, L, live, gi, n);
+        if ((b & a_bits) && (b & ~a_bits)) return;            // both teams present: the game stays open
+        w = b ? __ffs((int)b) - 1 : -1;
+    }
+    winner[gi] = w;
+    length[gi] = turn;
+    live[gi] = 0;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 // square boards of 5x5 (the eight standard start cells are distinct from there on, game.py:25-29) to 19x19 (SNK_MAX_CELLS);
 // the reference's observation is a rot90 of a (2H-1)x(2W-1) canvas, so only square boards batch (game.py:257)
@@ -1271,6 +1370,50 @@ extern "C" int snk_engine_step_active(snk_engine *e, const uint8_t *d_active, in
     if (n == 0) return 0;
     SNK_REQUIRE(d_moves != nullptr && d_active != nullptr, "snk_engine_step_active: NULL argument");
     return step_launch(e, nullptr, n, d_moves, nullptr, d_done, nullptr, nullptr, d_active, stream, d_skip);
+}
+
+extern "C" int snk_engine_step_active_tape(snk_engine *e, const uint8_t *d_active, int n, const uint8_t *d_moves,
+                                           const int16_t *d_spawn_tape, uint8_t *d_done, const int32_t *d_skip, void *stream)
+{
+    SNK_REQUIRE(e != nullptr, "snk_engine_step_active_tape: engine is NULL");
+    SNK_REQUIRE(n >= 0 && n <= e->n_slots, "snk_engine_step_active_tape: n=%d exceeds %d slots", n, e->n_slots);
+    if (n == 0) return 0;
+    SNK_REQUIRE(d_moves != nullptr && d_active != nullptr, "snk_engine_step_active_tape: NULL argument");
+    return step_launch(e, nullptr, n, d_moves, d_spawn_tape, d_done, nullptr, nullptr, d_active, stream, d_skip);
+}
+
+extern "C" int snk_pit_scratch_elems(int n) { return 2 * ((n + PIT_TILE - 1) / PIT_TILE) + 2; }
+
+extern "C" int snk_pit_rows(const snk_engine *e, const uint8_t *d_live, int n, int a_cnt, int32_t *d_pairs, int32_t *d_counts,
+                            int32_t *d_scratch, void *stream)
+{
+    SNK_REQUIRE(e && d_counts, "snk_pit_rows: NULL argument");
+    SNK_REQUIRE(n >= 0 && n <= e->n_slots, "snk_pit_rows: n=%d exceeds %d slots", n, e->n_slots);
+    SNK_REQUIRE(a_cnt >= 0 && a_cnt <= e->L.S, "snk_pit_rows: a_cnt=%d outside 0..%d", a_cnt, e->L.S);
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) { SNK_CHECK_HIP(hipMemsetAsync(d_counts, 0, 2 * sizeof(int32_t), st)); return 0; }
+    SNK_REQUIRE(d_live && d_pairs && d_scratch, "snk_pit_rows: NULL argument");
+    const uint32_t a_bits = (1u << a_cnt) - 1u;
+    const int tiles = (n + PIT_TILE - 1) / PIT_TILE;
+    k_pit_count<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, e->L, d_live, n, a_bits, d_scratch);
+    k_pit_scan<<<1, CMP_THREADS, 0, st>>>(d_scratch, tiles, d_counts);
+    k_pit_scatter<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, e->L, d_live, n, a_bits, d_scratch, d_counts, d_pairs);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_verdict(const snk_engine *e, const uint8_t *d_done, const int8_t *d_rewards, int n, int a_cnt, int turn,
+                               uint8_t *d_live, int32_t *d_winner, int32_t *d_length, void *stream)
+{
+    SNK_REQUIRE(e != nullptr, "snk_pit_verdict: engine is NULL");
+    SNK_REQUIRE(n >= 0 && n <= e->n_slots, "snk_pit_verdict: n=%d exceeds %d slots", n, e->n_slots);
+    SNK_REQUIRE(a_cnt >= 0 && a_cnt <= e->L.S, "snk_pit_verdict: a_cnt=%d outside 0..%d", a_cnt, e->L.S);
+    if (n == 0) return 0;
+    SNK_REQUIRE(d_done && d_rewards && d_live && d_winner && d_length, "snk_pit_verdict: NULL argument");
+    k_pit_verdict<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(e->d_state, e->L, d_done, d_rewards, n, (1u << a_cnt) - 1u, turn,
+                                                                   d_live, d_winner, d_length);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 extern "C" int snk_engine_alive(const snk_engine *e, const int32_t *d_slots, int n, uint8_t *d_alive,

@@ -362,6 +362,19 @@ __global__ void k_engine_rewards(const uint8_t *__restrict__ state, Layout L, co
     out[t] = ((const int8_t *)(state + (size_t)slot * L.stride + L.rew_off))[s];
 }
 
+// the pit agent's greedy move of every row (pit_agent.py:10-28), scattered into the dense per-game move array the step reads
+// (pit_mp_game_runner.py:36-38); the array was filled with 1 (straight) before, which a snake without a row keeps
+__global__ void k_pit_moves(const float *__restrict__ q, const int32_t *__restrict__ pairs, int m, int n, int S,
+                            uint8_t *__restrict__ moves)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const float z[3] = {q[3 * (size_t)i], q[3 * (size_t)i + 1], q[3 * (size_t)i + 2]};
+    const int g = pairs[2 * (size_t)i], s = pairs[2 * (size_t)i + 1];
+    if (g < 0 || g >= n || s < 0 || s >= S) return;          // a pair outside the array names no snake
+    moves[(size_t)g * S + s] = (uint8_t)argmax3(z);
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 static int tt_alloc(snk_tt *t, uint64_t cap)
 {
@@ -623,6 +636,18 @@ extern "C" int snk_engine_rewards(const snk_engine *e, const int32_t *d_slots, i
     if (n == 0) return 0;
     const int tot = n * e->L.S;
     k_engine_rewards<<<(tot + 255) / 256, 256, 0, (hipStream_t)stream>>>(e->d_state, e->L, d_slots, n, d_rewards);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_moves(const float *d_q, const int32_t *d_pairs, int m, int n, int n_snakes, uint8_t *d_moves, void *stream)
+{
+    SNK_REQUIRE(n >= 0 && m >= 0 && n_snakes >= 1 && n_snakes <= SNK_MAX_SNAKES, "snk_pit_moves: m=%d, n=%d, n_snakes=%d", m, n, n_snakes);
+    SNK_REQUIRE((long long)m <= (long long)n * n_snakes, "snk_pit_moves: %d rows for %d games of %d snakes", m, n, n_snakes);
+    if (n == 0) return 0;
+    SNK_REQUIRE(d_moves != nullptr && (m == 0 || (d_q && d_pairs)), "snk_pit_moves: NULL argument");
+    SNK_CHECK_HIP(hipMemsetAsync(d_moves, 1, (size_t)n * n_snakes, (hipStream_t)stream));
+    if (m > 0) k_pit_moves<<<(m + 255) / 256, 256, 0, (hipStream_t)stream>>>(d_q, d_pairs, m, n, n_snakes, d_moves);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

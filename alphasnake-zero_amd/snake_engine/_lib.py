@@ -46,6 +46,7 @@ PROTOTYPES = {
     "snk_engine_clone": (i32, [vp, vp, i32, vp, vp, i32, vp]),
     "snk_engine_step": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     "snk_engine_step_active": (i32, [vp, vp, i32, vp, vp, vp, vp]),
+    "snk_engine_step_active_tape": (i32, [vp, vp, i32, vp, vp, vp, vp, vp]),
     "snk_engine_alive": (i32, [vp, vp, i32, vp, vp, vp]),
     "snk_engine_ids": (i32, [vp, vp, i32, vp, vp, vp, vp, vp]),
     "snk_engine_observe": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, vp]),
@@ -112,6 +113,10 @@ PROTOTYPES = {
     "snk_mcts_root_moves": (i32, [vp, vp, i32, C.c_float, i32, vp, vp, C.c_int64, u64, C.c_uint32, C.c_uint32, vp, vp]),
     "snk_softermax_argmax": (i32, [vp, i32, C.c_float, vp, vp, vp]),
     "snk_engine_rewards": (i32, [vp, vp, i32, vp, vp]),
+    "snk_pit_scratch_elems": (i32, [i32]),
+    "snk_pit_rows": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
+    "snk_pit_moves": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "snk_pit_verdict": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "snk_head_f32": (i32, [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "snk_bn_train_partials": (i32, []),
     "snk_conv3x3_f16s_input_scale": (i32, [vp, C.c_long, vp, vp, vp]),

@@ -85,3 +85,16 @@ class MPGameRunner:
                         winners[gid] = int(ids_alive[0])
                         del games[gid]
         return winners
+
+    def run_device(self, Alice, Bob, Alice_snake_cnt=None, spawn_tape=None):
+        """`run` with the whole loop on the device (snake_engine.arena.Arena over this runner's engine): the same winners list,
+        None for a draw; one host read-back per turn instead of four and no per-game Python loop.  Alice and Bob are pit agents
+        (their nets are used) or nets with v_device(planes, mask); nothing is drawn for a single game."""
+        from snake_engine.arena import Arena
+        arena = Arena.from_engine(self.engine)
+        res = arena.match(getattr(Alice, "nnet", Alice), getattr(Bob, "nnet", Bob), Alice_snake_cnt, spawn_tape=spawn_tape)
+        for g in self.games.values():
+            g._dirty()
+        self.games.clear()
+        self.arena_result = res
+        return [None if w < 0 else w for w in res.winners.tolist()]

@@ -54,7 +54,8 @@ const char *snk_last_error(void);
                              * towers' own weight image and rectangle plan, round 5); 111: the training step's deferred batch
                              * norm (fifteen entry points added, snk_conv3x3_stats_partials returns more); 112: round 6,
                              * snk_engine_import_at_sync and snk_engine_observe_rows added; 113: the MX-FP8 tower's five entry
-                             * points: a caller compares it with snk_version() */
+                             * points: a caller compares it with snk_version().  The arena's entry points (snk_pit_*,
+                             * snk_engine_step_active_tape) were added under 113: no argument list of an older one changed */
 int snk_version(void);
 
 /* ---- engine lifetime -------------------------------------------------------------------
@@ -114,6 +115,11 @@ int snk_engine_step(snk_engine *e, const int32_t *d_slots, int n, const uint8_t 
  * whose leaf evaluation clamped an activation is not played, the host evaluates again and repeats it.            */
 int snk_engine_step_active(snk_engine *e, const uint8_t *d_active, int n, const uint8_t *d_moves,
                            uint8_t *d_done, const int32_t *d_skip, void *stream);
+/* snk_engine_step_active with a recorded food-spawn tape: the arena's tick (pit_mp_game_runner.py:40-42, Game.tic on every game
+ * whose verdict is open; d_active = the arena's live flags, so a game whose verdict is in keeps the board it was taken on).
+ * d_spawn_tape (optional): int16[n] as in snk_engine_step, indexed by slot; NULL = what snk_engine_step_active does.        */
+int snk_engine_step_active_tape(snk_engine *e, const uint8_t *d_active, int n, const uint8_t *d_moves,
+                                const int16_t *d_spawn_tape, uint8_t *d_done, const int32_t *d_skip, void *stream);
 
 /* ---- Game.get_ids / alive bookkeeping (game.py:76-77) -----------------------------------
  * d_alive: uint8[n][S] (1 = snake alive), d_n_alive (optional): int32[n].                     */
@@ -471,6 +477,29 @@ int snk_softermax_argmax(const float *d_z, int m, float softmax_base, float *d_p
                          void *stream);
 /* Game.rewards of n games as int8[n][S]: 0 None, +1, -1 (mp_game_runner.py:110) */
 int snk_engine_rewards(const snk_engine *e, const int32_t *d_slots, int n, int8_t *d_rewards, void *stream);
+
+/* ---- the pit match on the device (pit_mp_game_runner.py:14-63, pit_agent.py:10-28) -------------------------------------------
+ * Games are slots 0..n-1 of one engine; d_live: uint8[n], 1 = the game's verdict is still open; snakes with id < a_cnt are
+ * team A (Alice_snake_cnt, 0..S), the others team B.  A turn is snk_pit_rows, snk_engine_observe over the rows, the two nets,
+ * snk_pit_moves, snk_engine_step_active_tape with d_active = d_live, snk_engine_rewards, snk_pit_verdict; the host reads the two
+ * row counts and nothing else (snake_engine/arena.py).
+ * snk_pit_rows (pit_mp_game_runner.py:23-35): d_pairs int32[n*S][2] = (slot, snake id) of every alive snake of every live game --
+ *   all team-A rows first (ids_A: games ascending, ids ascending inside a game), then all team-B rows in the same order (ids_B),
+ *   i.e. the order of ids_A + ids_B; d_counts int32[2] = {nA, nB}; rows past nA + nB are not written.  Deterministic (a block
+ *   scan per team, no atomics).  d_scratch: int32[snk_pit_scratch_elems(n)].
+ * snk_pit_moves (pit_agent.py:10-28 + pit_mp_game_runner.py:36-38): d_q float32[m][3] = the nets' values of the m rows of d_pairs;
+ *   d_moves uint8[n][n_snakes] = 1 (straight) everywhere, then the row's greedy move at [slot][id]: Z0 > Z1 ? (Z0 > Z2 ? 0 : 2)
+ *   : (Z1 > Z2 ? 1 : 2), strict comparisons (what snk_softermax_argmax returns).  A pair outside the array is skipped.
+ * snk_pit_verdict (pit_mp_game_runner.py:39-62), after the step: d_done uint8[n] from the step, d_rewards int8[n][S] from
+ *   snk_engine_rewards.  A live game that is done: d_winner = the largest id whose reward is +1, -1 (None) without one.  A live
+ *   game that is not done and has no team-A or no team-B snake left: d_winner = the smallest alive id.  Both: d_live = 0,
+ *   d_length = turn.  Every other game keeps its d_live, d_winner int32[n] and d_length int32[n] entries.                     */
+int snk_pit_scratch_elems(int n);
+int snk_pit_rows(const snk_engine *e, const uint8_t *d_live, int n, int a_cnt, int32_t *d_pairs, int32_t *d_counts,
+                 int32_t *d_scratch, void *stream);
+int snk_pit_moves(const float *d_q, const int32_t *d_pairs, int m, int n, int n_snakes, uint8_t *d_moves, void *stream);
+int snk_pit_verdict(const snk_engine *e, const uint8_t *d_done, const int8_t *d_rewards, int n, int a_cnt, int turn,
+                    uint8_t *d_live, int32_t *d_winner, int32_t *d_length, void *stream);
 
 /* ---- training half: AlphaNNet.train = model.fit (alpha_nnet.py:58-59) -------------------------
  * Training-mode batch normalisation of a 128-channel channels-last float32 activation [rows = n * h * w][128] (the
