@@ -1184,6 +1184,43 @@ __global__ __launch_bounds__(CMP_THREADS) void k_pit_scatter(const uint8_t *__re
     }
 }
 
+// the root games of a searching side (agent.py:25-99 behind pit_mp_game_runner.py:23-38): the open slots ascending, what
+// DeviceMCTS.search takes as live_slots / root_alive.  Open games of the block's PIT_TILE games: tile_sums[b]; the tile sums
+// are scanned by k_cmp_scan (one column), which also writes the count G
+__global__ __launch_bounds__(CMP_THREADS) void k_pit_roots_count(const uint8_t *__restrict__ live, int n, int32_t *__restrict__ tile_sums)
+{
+    __shared__ int sh[8];
+    const int base = blockIdx.x * PIT_TILE + threadIdx.x * PIT_ITEMS;
+    int c = 0;
+    for (int q = 0; q < PIT_ITEMS; ++q) { const int gi = base + q; if (gi < n && live[gi]) ++c; }
+    int total;
+    block_exclusive_scan_256(c, &total, sh);
+    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
+}
+
+// slots[j] = the j-th open slot, alive[j][s] = its snakes' alive flags, rank[slot] = j (-1 for a closed game); nothing past G
+__global__ __launch_bounds__(CMP_THREADS) void k_pit_roots_scatter(const uint8_t *__restrict__ state, Layout L, const uint8_t *__restrict__ live,
+                                                                   int n, const int32_t *__restrict__ tile_offs, int32_t *__restrict__ slots,
+                                                                   uint8_t *__restrict__ alive, int32_t *__restrict__ rank)
+{
+    __shared__ int sh[8];
+    const int base = blockIdx.x * PIT_TILE + threadIdx.x * PIT_ITEMS;
+    bool open[PIT_ITEMS];
+    int c = 0;
+    for (int q = 0; q < PIT_ITEMS; ++q) { const int gi = base + q; open[q] = gi < n && live[gi]; if (open[q]) ++c; }
+    int total;
+    int pos = tile_offs[blockIdx.x] + block_exclusive_scan_256(c, &total, sh);
+    for (int q = 0; q < PIT_ITEMS; ++q) {
+        const int gi = base + q;
+        if (gi >= n) break;
+        if (!open[q]) { rank[gi] = -1; continue; }
+        const SnakeMeta *meta = (const SnakeMeta *)(state + (size_t)gi * L.stride + L.meta_off);
+        for (int s = 0; s < L.S; ++s) alive[(size_t)pos * L.S + s] = meta[s].alive ? 1 : 0;
+        slots[pos] = gi;
+        rank[gi] = pos++;
+    }
+}
+
 // the verdict of one turn (pit_mp_game_runner.py:39-62), a thread per game
 __global__ void k_pit_verdict(const uint8_t *__restrict__ state, Layout L, const uint8_t *__restrict__ done,
                               const int8_t *__restrict__ rewards, int n, uint32_t a_bits, int turn, uint8_t *live,
@@ -1398,6 +1435,22 @@ extern "C" int snk_pit_rows(const snk_engine *e, const uint8_t *d_live, int n, i
     k_pit_count<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, e->L, d_live, n, a_bits, d_scratch);
     k_pit_scan<<<1, CMP_THREADS, 0, st>>>(d_scratch, tiles, d_counts);
     k_pit_scatter<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, e->L, d_live, n, a_bits, d_scratch, d_counts, d_pairs);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_roots(const snk_engine *e, const uint8_t *d_live, int n, int32_t *d_slots, uint8_t *d_alive, int32_t *d_rank,
+                             int32_t *d_count, int32_t *d_scratch, void *stream)
+{
+    SNK_REQUIRE(e && d_count, "snk_pit_roots: NULL argument");
+    SNK_REQUIRE(n >= 0 && n <= e->n_slots, "snk_pit_roots: n=%d exceeds %d slots", n, e->n_slots);
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) { SNK_CHECK_HIP(hipMemsetAsync(d_count, 0, sizeof(int32_t), st)); return 0; }
+    SNK_REQUIRE(d_live && d_slots && d_alive && d_rank && d_scratch, "snk_pit_roots: NULL argument");
+    const int tiles = (n + PIT_TILE - 1) / PIT_TILE;
+    k_pit_roots_count<<<tiles, CMP_THREADS, 0, st>>>(d_live, n, d_scratch);
+    k_cmp_scan<<<1, CMP_THREADS, 0, st>>>(d_scratch, tiles, d_count);
+    k_pit_roots_scatter<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, e->L, d_live, n, d_scratch, d_slots, d_alive, d_rank);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

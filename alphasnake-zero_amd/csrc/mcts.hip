@@ -375,6 +375,26 @@ __global__ void k_pit_moves(const float *__restrict__ q, const int32_t *__restri
     moves[(size_t)g * S + s] = (uint8_t)argmax3(z);
 }
 
+// the searching sides' root moves (agent.py:25-99 behind pit_mp_game_runner.py:23-38) merged into the dense move array, a thread
+// per (slot, snake): moves_a / moves_b are [G][S] over the open games in rank order and only their own team's columns are read;
+// a dead snake and a closed game take 1; a cell of a team without an array keeps what snk_pit_moves wrote (keep_other) or takes 1
+__global__ void k_pit_search_moves(const uint8_t *__restrict__ moves_a, const uint8_t *__restrict__ moves_b,
+                                   const int32_t *__restrict__ rank, const uint8_t *__restrict__ alive, int n, int S, int a_cnt,
+                                   int keep_other, uint8_t *__restrict__ moves)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)n * S) return;
+    const int i = (int)(t / S), s = (int)(t - (size_t)i * S);
+    const int j = rank[i];
+    uint8_t mv = 1;
+    if (j >= 0 && j < n && alive[(size_t)j * S + s]) {
+        const uint8_t *src = s < a_cnt ? moves_a : moves_b;
+        if (src) mv = src[(size_t)j * S + s];
+        else if (keep_other) return;
+    }
+    moves[t] = mv;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 static int tt_alloc(snk_tt *t, uint64_t cap)
 {
@@ -648,6 +668,20 @@ extern "C" int snk_pit_moves(const float *d_q, const int32_t *d_pairs, int m, in
     SNK_REQUIRE(d_moves != nullptr && (m == 0 || (d_q && d_pairs)), "snk_pit_moves: NULL argument");
     SNK_CHECK_HIP(hipMemsetAsync(d_moves, 1, (size_t)n * n_snakes, (hipStream_t)stream));
     if (m > 0) k_pit_moves<<<(m + 255) / 256, 256, 0, (hipStream_t)stream>>>(d_q, d_pairs, m, n, n_snakes, d_moves);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_search_moves(const uint8_t *d_moves_a, const uint8_t *d_moves_b, const int32_t *d_rank, const uint8_t *d_alive,
+                                    int n, int n_snakes, int a_cnt, int keep_other, uint8_t *d_moves, void *stream)
+{
+    SNK_REQUIRE(n >= 0 && n_snakes >= 1 && n_snakes <= SNK_MAX_SNAKES, "snk_pit_search_moves: n=%d, n_snakes=%d", n, n_snakes);
+    SNK_REQUIRE(a_cnt >= 0 && a_cnt <= n_snakes, "snk_pit_search_moves: a_cnt=%d outside 0..%d", a_cnt, n_snakes);
+    if (n == 0) return 0;
+    SNK_REQUIRE(d_rank && d_alive && d_moves, "snk_pit_search_moves: NULL argument");
+    const size_t tot = (size_t)n * n_snakes;
+    k_pit_search_moves<<<(unsigned)((tot + 255) / 256), 256, 0, (hipStream_t)stream>>>(d_moves_a, d_moves_b, d_rank, d_alive, n, n_snakes,
+                                                                                       a_cnt, keep_other, d_moves);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

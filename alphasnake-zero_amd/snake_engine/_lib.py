@@ -117,6 +117,8 @@ PROTOTYPES = {
     "snk_pit_rows": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
     "snk_pit_moves": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "snk_pit_verdict": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "snk_pit_roots": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "snk_pit_search_moves": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "snk_head_f32": (i32, [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "snk_bn_train_partials": (i32, []),
     "snk_conv3x3_f16s_input_scale": (i32, [vp, C.c_long, vp, vp, vp]),

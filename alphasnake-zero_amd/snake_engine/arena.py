@@ -15,6 +15,23 @@ A turn of ``Arena.match``:
 There is no per-game Python loop and nothing else comes back to the host until the match is over.  The host loop of
 ``utils.pit_mp_game_runner.MPGameRunner.run`` (four synchronising copies, ``np.nonzero`` and a Python loop over the games each
 turn) stays as the parity-pinned form; ``MPGameRunner.run_device`` is this one behind the same interface.
+
+Either side may instead be a ``Searcher``: it moves the way ``Agent(nnet, training=False).make_moves`` moves (agent.py:25-99), by a
+``DeviceMCTS.search`` over the open games.  A turn with at least one searching side:
+
+    snk_pit_roots                 the open slots ascending, their alive rows, each slot's rank in that list, the count G
+    snk_pit_rows                  only when one side is greedy
+    the turn's read-back          G and the two row counts, one tensor, one .tolist(); G = 0 ends the match
+    the greedy side               observe + its net on its own rows, snk_pit_moves over those rows (the array is filled with 1)
+    searcher.search, end_of_turn  team A's searcher first; each simulates all snakes of the open games with its own net and
+                                  only its own team's columns of the root moves are used
+    snk_pit_search_moves          merges them into the dense move array
+    step, rewards, verdict        as above
+
+The arena's own read-back stays one per turn.  The search reads back on its own, and those are not the arena's: the largest root
+depth once per turn, the number of new keys once per rollout tick (it sizes the net batch), the table status after every epoch but
+the last and at the end of the turn together with the turn's sub-game tick counter; a taped (parity) search also reads its row
+counts.  A guarded net is calibrated once, on the first turn's root observations.
 """
 from collections import namedtuple
 
@@ -28,6 +45,67 @@ ArenaResult = namedtuple("ArenaResult", "winners lengths turns wins_a wins_b dra
 ArenaResult.__doc__ = """winners: int32[game_cnt] winning snake id, -1 for a draw (the reference's None); lengths: int32[game_cnt]
 the turn a game's verdict came in; turns: turns played; wins_a / wins_b: games won by a snake of team A (id < alice_snake_cnt) /
 team B; draws: games without a winner"""
+
+
+def _device_mcts():
+    """DeviceMCTS, looked up when the first Searcher plays: a match between two nets never loads the search"""
+    return __import__(__package__ + ".mcts", fromlist=["DeviceMCTS"]).DeviceMCTS
+
+
+class Searcher:
+    """A side of a pit match that moves by search: Agent(net, softmax_base, False, depth, breadth).make_moves (agent.py:25-99) over
+    the arena's open games.  It owns one DeviceMCTS with training=False (the root decision is Agent.argmaxs), with its own
+    transposition table and its own rollout engine, created at the first turn, when the geometry is known."""
+
+    def __init__(self, net, breadth=128, depth=8, softmax_base=100, seed=None, sequential=False, tape_u=None, tt_capacity=None):
+        if not hasattr(net, "v_device"):
+            raise TypeError(f"{type(net).__name__} has no v_device(planes, mask): the arena evaluates on the device only")
+        self.net = net
+        self.breadth, self.depth, self.softmax_base = int(breadth), int(depth), softmax_base
+        self.seed = int(np.random.randint(1 << 62)) if seed is None else int(seed)
+        self.sequential, self.tape_u, self.tt_capacity = sequential, tape_u, tt_capacity
+        self.mcts = None
+
+    def _evaluate(self, planes, mask):
+        if self.mcts.guard is not None:               # gated ticks: no synchronisation per leaf batch (utils/agent.py)
+            return self.net.v_device_unguarded(planes, mask)
+        return self.net.v_device(planes, mask)
+
+    def search(self, engine, slots, alive):
+        """slots int32[G], alive uint8[G][S] on the device -> the root moves uint8[G][S] of every snake of those games"""
+        m = self.mcts
+        if m is None or (m.H, m.W, m.S, m.dev_index) != (engine.H, engine.W, engine.S, engine.device.index):
+            m = self.mcts = _device_mcts()(self._evaluate, engine.H, engine.W, engine.S, self.softmax_base, False, self.depth,
+                                           self.breadth, seed=self.seed, device=engine.device.index, sequential=self.sequential,
+                                           tape_u=self.tape_u, tt_capacity=self.tt_capacity)
+        net = self.net
+        m.guard = getattr(net, "guard", None)         # the Q-net's range-guard word gates the rollout ticks
+        if hasattr(net, "calibrate") and not getattr(getattr(net, "_qnet", None), "calibrated", True):
+            # new weights: fit the split-f16 kernel's activation scales to real observations (the root states) once
+            pairs = torch.nonzero(alive)[:4096].to(torch.int32)
+            pairs[:, 0] = slots[pairs[:, 0].long()]
+            planes, _, _ = engine.observe_all(pairs.contiguous(), want_mask=False, want_key=False)
+            net.calibrate(planes)
+        return m.search(engine, slots, alive)[1]
+
+    def end_of_turn(self):
+        if self.mcts is not None:
+            self.mcts.end_of_turn()
+
+    def clear(self):
+        """Agent.clear (agent.py:140-147)"""
+        if self.mcts is not None:
+            self.mcts.clear()
+
+    @property
+    def tape_pos(self):
+        """uniforms of tape_u consumed so far"""
+        return 0 if self.mcts is None else self.mcts.tape_pos
+
+    @property
+    def stats(self):
+        """DeviceMCTS.stats: net_evals, rollout_ticks, sim_steps, lookups"""
+        return dict(net_evals=0, rollout_ticks=0, sim_steps=0, lookups=0) if self.mcts is None else self.mcts.stats
 
 
 class Arena:
@@ -54,6 +132,7 @@ class Arena:
         self._rewards = eng.new((n, S), torch.int8)
         self._winner = eng.new((n,), torch.int32)
         self._length = eng.new((n,), torch.int32)
+        self._roots = None                        # the searching turn's buffers, made by the first match that searches
 
     @classmethod
     def from_engine(cls, engine):
@@ -69,7 +148,9 @@ class Arena:
 
     # ---- one match -------------------------------------------------------------------------------------------------------
     def match(self, alice, bob, alice_snake_cnt=None, init_tape=None, spawn_tape=None):
-        """alice, bob: anything with v_device(planes, mask) -> float32[rows][3] on the device (AlphaNNet: its guarded forward).
+        """alice, bob: anything with v_device(planes, mask) -> float32[rows][3] on the device (AlphaNNet: its guarded forward),
+        or a Searcher around one; every combination is allowed.  With a Searcher the turn is the second one of the module's
+        docstring: the arena still reads back once per turn (G and the two row counts), the searches read back on their own.
         alice_snake_cnt: snakes 0 .. alice_snake_cnt-1 are alice's (default snake_cnt // 2, pit_mp_game_runner.py:17-18).
         init_tape: uint8[game_cnt][3][snake_cnt] recorded start draws (snk_engine_reset); without one the match plays on the
         boards the arena holds -- fresh ones are drawn on the device when a match has already been played on them.
@@ -77,22 +158,35 @@ class Arena:
         only: the upload is a copy from pageable host memory, which waits for the stream every turn -- host to device, so no
         read-back, but a match played with a tape says nothing about the speed of one played without."""
         eng, n, S = self.engine, self.game_cnt, self.snake_cnt
-        L = eng.L
         a_cnt = S // 2 if alice_snake_cnt is None else int(alice_snake_cnt)
         if not 0 <= a_cnt <= S:
             raise ValueError(f"alice_snake_cnt {a_cnt} outside 0..{S}")
         for net in (alice, bob):
-            if not hasattr(net, "v_device"):
+            if not isinstance(net, Searcher) and not hasattr(net, "v_device"):
                 raise TypeError(f"{type(net).__name__} has no v_device(planes, mask): the arena evaluates on the device only")
         if init_tape is not None:
             eng.reset(init_tape=init_tape)
         elif not self._fresh:
             eng.reset()
         self._fresh = False
-        live, pairs, counts, moves = self._live, self._pairs, self._counts, self._moves
-        live.fill_(1)
+        self._live.fill_(1)
         self._winner.fill_(-1)
         self._length.zero_()
+        if isinstance(alice, Searcher) or isinstance(bob, Searcher):
+            turn = self._search_turns(alice, bob, a_cnt, spawn_tape)
+        else:
+            turn = self._greedy_turns(alice, bob, a_cnt, spawn_tape)
+        winners = self._winner.cpu().numpy()
+        lengths = self._length.cpu().numpy()
+        wins_a = int(((winners >= 0) & (winners < a_cnt)).sum())
+        wins_b = int((winners >= a_cnt).sum())
+        return ArenaResult(winners, lengths, turn, wins_a, wins_b, n - wins_a - wins_b)
+
+    def _greedy_turns(self, alice, bob, a_cnt, spawn_tape):
+        """the turns of a match between two nets -> turns played"""
+        eng, n, S = self.engine, self.game_cnt, self.snake_cnt
+        L = eng.L
+        live, pairs, counts, moves = self._live, self._pairs, self._counts, self._moves
         turn = 0
         while True:
             check(L.snk_pit_rows(eng.h, _ptr(live), n, a_cnt, _ptr(pairs), _ptr(counts), _ptr(self._scratch), _stream()))
@@ -104,20 +198,62 @@ class Arena:
             planes, mask, _ = eng.observe_all(pairs[:m], want_key=False)
             q = self._values(alice, bob, planes, mask, nA, m)
             check(L.snk_pit_moves(_ptr(q), _ptr(pairs), m, n, S, _ptr(moves), _stream()))
-            tape = None
-            if spawn_tape is not None:
-                tape = torch.as_tensor(np.ascontiguousarray(spawn_tape(turn), np.int16), device=eng.device)
-                if tape.numel() != n:
-                    raise ValueError(f"spawn_tape({turn}) has {tape.numel()} entries for {n} games")
-            check(L.snk_engine_step_active_tape(eng.h, _ptr(live), n, _ptr(moves), _ptr(tape), _ptr(self._done), None, _stream()))
-            check(L.snk_engine_rewards(eng.h, None, n, _ptr(self._rewards), _stream()))
-            check(L.snk_pit_verdict(eng.h, _ptr(self._done), _ptr(self._rewards), n, a_cnt, turn, _ptr(live), _ptr(self._winner),
-                                    _ptr(self._length), _stream()))
-        winners = self._winner.cpu().numpy()
-        lengths = self._length.cpu().numpy()
-        wins_a = int(((winners >= 0) & (winners < a_cnt)).sum())
-        wins_b = int((winners >= a_cnt).sum())
-        return ArenaResult(winners, lengths, turn, wins_a, wins_b, n - wins_a - wins_b)
+            self._tick(turn, a_cnt, spawn_tape)
+        return turn
+
+    def _tick(self, turn, a_cnt, spawn_tape):
+        """the dense moves are in: open games move, games whose verdict is in stay as they are, then the turn's verdict"""
+        eng, n, live = self.engine, self.game_cnt, self._live
+        L = eng.L
+        tape = None
+        if spawn_tape is not None:
+            tape = torch.as_tensor(np.ascontiguousarray(spawn_tape(turn), np.int16), device=eng.device)
+            if tape.numel() != n:
+                raise ValueError(f"spawn_tape({turn}) has {tape.numel()} entries for {n} games")
+        check(L.snk_engine_step_active_tape(eng.h, _ptr(live), n, _ptr(self._moves), _ptr(tape), _ptr(self._done), None, _stream()))
+        check(L.snk_engine_rewards(eng.h, None, n, _ptr(self._rewards), _stream()))
+        check(L.snk_pit_verdict(eng.h, _ptr(self._done), _ptr(self._rewards), n, a_cnt, turn, _ptr(live), _ptr(self._winner),
+                                _ptr(self._length), _stream()))
+
+    def _search_turns(self, alice, bob, a_cnt, spawn_tape):
+        """the turns of a match in which at least one side is a Searcher -> turns played"""
+        eng, n, S = self.engine, self.game_cnt, self.snake_cnt
+        L = eng.L
+        live, pairs, moves = self._live, self._pairs, self._moves
+        if self._roots is None:
+            self._roots = (eng.new((n,), torch.int32), eng.new((n, S), torch.uint8), eng.new((n,), torch.int32),
+                           eng.new((3,), torch.int32))
+        slots, alive, rank, counts = self._roots              # counts: {nA, nB, G}
+        counts.zero_()
+        greedy = [not isinstance(side, Searcher) for side in (alice, bob)]
+        turn = 0
+        while True:
+            check(L.snk_pit_roots(eng.h, _ptr(live), n, _ptr(slots), _ptr(alive), _ptr(rank), _ptr(counts[2:]), _ptr(self._scratch),
+                                  _stream()))
+            if any(greedy):
+                check(L.snk_pit_rows(eng.h, _ptr(live), n, a_cnt, _ptr(pairs), _ptr(counts), _ptr(self._scratch), _stream()))
+            nA, nB, G = counts.tolist()           # the turn's one read-back
+            if G == 0:
+                break
+            turn += 1
+            if any(greedy):                       # the greedy side's net on its own rows; the array is filled with 1
+                lo, hi, net = (0, nA, alice) if greedy[0] else (nA, nA + nB, bob)
+                q = None
+                if hi > lo:
+                    planes, mask, _ = eng.observe_all(pairs[lo:hi], want_key=False)
+                    q = self._values(net, net, planes, mask, hi - lo, hi - lo)
+                check(L.snk_pit_moves(_ptr(q), _ptr(pairs[lo:hi]), hi - lo, n, S, _ptr(moves), _stream()))
+            found = [None, None]
+            for k, side in enumerate((alice, bob)):       # team A's searcher first
+                if not greedy[k]:
+                    found[k] = side.search(eng, slots[:G], alive[:G]).contiguous()
+                    if found[k].dtype != torch.uint8 or tuple(found[k].shape) != (G, S):
+                        raise EngineError(f"search returned {found[k].dtype} {tuple(found[k].shape)} for {G} games of {S} snakes")
+                    side.end_of_turn()
+            check(L.snk_pit_search_moves(_ptr(found[0]), _ptr(found[1]), _ptr(rank), _ptr(alive), n, S, a_cnt, int(any(greedy)),
+                                         _ptr(moves), _stream()))
+            self._tick(turn, a_cnt, spawn_tape)
+        return turn
 
     @staticmethod
     def _values(alice, bob, planes, mask, nA, m):
@@ -134,21 +270,31 @@ class Arena:
 
     # ---- the reference's two judges ------------------------------------------------------------------------------------------
     @staticmethod
-    def test_pit(alice, bob, games=300, height=11, width=11, health_dec=1, seed=None):
+    def _sides(alice, bob, search, seed):
+        """the two sides of one match: the nets themselves, or fresh Searchers around them (search: Searcher's keyword arguments)"""
+        if search is None:
+            return alice, bob
+        seeds = [None, None] if seed is None else [seed + 101, seed + 202]
+        return tuple(Searcher(net, seed=sd, **search) for net, sd in zip((alice, bob), seeds))
+
+    @staticmethod
+    def test_pit(alice, bob, games=300, height=11, width=11, health_dec=1, seed=None, search=None):
         """test_pit.py:24-65: `games` games each of alice alone against three snakes of bob, the same with the roles swapped,
         then the duel of two snakes the reference prints as "2v2".  Returns the rates it prints:
-        {"1v3_alice": (win rate, draw rate), "1v3_bob": (win rate, draw rate), "2v2": (alice's win rate, bob's win rate)}"""
+        {"1v3_alice": (win rate, draw rate), "1v3_bob": (win rate, draw rate), "2v2": (alice's win rate, bob's win rate)}
+        search=dict(breadth=..., depth=...): both nets move by search (a fresh Searcher each per match)"""
         seeds = [None] * 3 if seed is None else [seed, seed + 1, seed + 2]
-        r1 = Arena(height, width, 4, health_dec, games, seeds[0]).match(alice, bob, 1)
-        r2 = Arena(height, width, 4, health_dec, games, seeds[1]).match(bob, alice, 1)
-        r3 = Arena(height, width, 2, health_dec, games, seeds[2]).match(alice, bob, 1)
+        r1 = Arena(height, width, 4, health_dec, games, seeds[0]).match(*Arena._sides(alice, bob, search, seeds[0]), 1)
+        r2 = Arena(height, width, 4, health_dec, games, seeds[1]).match(*Arena._sides(bob, alice, search, seeds[1]), 1)
+        r3 = Arena(height, width, 2, health_dec, games, seeds[2]).match(*Arena._sides(alice, bob, search, seeds[2]), 1)
         return {"1v3_alice": (r1.wins_a / games, r1.draws / games), "1v3_bob": (r2.wins_a / games, r2.draws / games),
                 "2v2": (r3.wins_a / games, r3.wins_b / games)}
 
     @staticmethod
-    def ladder_row(challenger, champion, games=1000, height=11, width=11, seed=None):
+    def ladder_row(challenger, champion, games=1000, height=11, width=11, seed=None, search=None):
         """pit.py:30-44: `games` games of two snakes, the champion's snake first; a drawn game is half a point for each side.
-        Returns the challenger's score, the number pit.py writes to pit.txt (the title changes above 0.51, pit.py:45)"""
-        r = Arena(height, width, 2, 1, games, seed).match(champion, challenger, 1)
+        Returns the challenger's score, the number pit.py writes to pit.txt (the title changes above 0.51, pit.py:45).
+        search=dict(breadth=..., depth=...): both nets move by search"""
+        r = Arena(height, width, 2, 1, games, seed).match(*Arena._sides(champion, challenger, search, seed), 1)
         won, lost = r.wins_b + 0.5 * r.draws, r.wins_a + 0.5 * r.draws
         return won / (won + lost)

@@ -89,10 +89,18 @@ class MPGameRunner:
     def run_device(self, Alice, Bob, Alice_snake_cnt=None, spawn_tape=None):
         """`run` with the whole loop on the device (snake_engine.arena.Arena over this runner's engine): the same winners list,
         None for a draw; one host read-back per turn instead of four and no per-game Python loop.  Alice and Bob are pit agents
-        (their nets are used) or nets with v_device(planes, mask); nothing is drawn for a single game."""
-        from snake_engine.arena import Arena
+        (their nets are used), nets with v_device(planes, mask), or searching agents (utils.agent.Agent: its net, depth, breadth,
+        base and seed behind a snake_engine.arena.Searcher, which moves as Agent.make_moves with training=False does); nothing is
+        drawn for a single game."""
+        from snake_engine.arena import Arena, Searcher
+
+        def side(agent):
+            if not hasattr(agent, "max_MCTS_breadth"):
+                return getattr(agent, "nnet", agent)
+            return Searcher(agent.nnet, agent.max_MCTS_breadth, agent.max_MCTS_depth, agent.softmax_base, agent._seed,
+                            agent._sequential, agent._tape_u, agent._tt_capacity)
         arena = Arena.from_engine(self.engine)
-        res = arena.match(getattr(Alice, "nnet", Alice), getattr(Bob, "nnet", Bob), Alice_snake_cnt, spawn_tape=spawn_tape)
+        res = arena.match(side(Alice), side(Bob), Alice_snake_cnt, spawn_tape=spawn_tape)
         for g in self.games.values():
             g._dirty()
         self.games.clear()

@@ -55,7 +55,8 @@ const char *snk_last_error(void);
                              * norm (fifteen entry points added, snk_conv3x3_stats_partials returns more); 112: round 6,
                              * snk_engine_import_at_sync and snk_engine_observe_rows added; 113: the MX-FP8 tower's five entry
                              * points: a caller compares it with snk_version().  The arena's entry points (snk_pit_*,
-                             * snk_engine_step_active_tape) were added under 113: no argument list of an older one changed */
+                             * snk_engine_step_active_tape) were added under 113, and so were the searching pit's
+                             * (snk_pit_roots, snk_pit_search_moves): no argument list of an older one changed */
 int snk_version(void);
 
 /* ---- engine lifetime -------------------------------------------------------------------
@@ -493,8 +494,27 @@ int snk_engine_rewards(const snk_engine *e, const int32_t *d_slots, int n, int8_
  * snk_pit_verdict (pit_mp_game_runner.py:39-62), after the step: d_done uint8[n] from the step, d_rewards int8[n][S] from
  *   snk_engine_rewards.  A live game that is done: d_winner = the largest id whose reward is +1, -1 (None) without one.  A live
  *   game that is not done and has no team-A or no team-B snake left: d_winner = the smallest alive id.  Both: d_live = 0,
- *   d_length = turn.  Every other game keeps its d_live, d_winner int32[n] and d_length int32[n] entries.                     */
+ *   d_length = turn.  Every other game keeps its d_live, d_winner int32[n] and d_length int32[n] entries.
+ * A side may also move by search (Agent.make_moves with training=False, agent.py:25-99, behind pit_mp_game_runner.py:23-38):
+ * snake_engine.arena.Searcher runs DeviceMCTS.search over the open games and takes its own team's columns of the result.  The
+ * turn is then snk_pit_roots, for a greedy side snk_pit_rows / observe / its net / snk_pit_moves over that side's rows only, the
+ * read-back (G and the two row counts in one copy), the searches (team A's first; they read back on their own: the number of new
+ * keys once per rollout tick, the deepest root's tick count once per turn, the table status after every epoch and at the end of
+ * the turn), snk_pit_search_moves, and the step, rewards and verdict as above.
+ * snk_pit_roots (agent.py:25-99 behind pit_mp_game_runner.py:23-38): d_slots int32[n] = the slots with d_live != 0, ascending;
+ *   d_alive uint8[n][S]: row j = the alive flags of slot d_slots[j]; d_rank int32[n] = j for an open slot, -1 for a closed one;
+ *   *d_count = G, the number of open slots.  List entries and rows past G are not written.  Deterministic (a block scan, no
+ *   atomics).  d_scratch: int32[snk_pit_scratch_elems(n)].
+ * snk_pit_search_moves (agent.py:25-99 behind pit_mp_game_runner.py:23-38): a thread per cell [i][s] of d_moves uint8[n][n_snakes].
+ *   d_moves_a / d_moves_b: uint8[G][n_snakes], a searcher's root moves of the open games in d_slots order, or NULL for a side
+ *   that does not search; d_rank / d_alive as snk_pit_roots wrote them.  With j = d_rank[i]: an alive snake of an open game takes
+ *   its team's moves[j][s] (team A: s < a_cnt); a dead snake and a closed game take 1; an alive snake whose team has no array keeps
+ *   its cell when keep_other != 0 (what snk_pit_moves wrote there) and takes 1 otherwise.  Every cell has one writer.          */
 int snk_pit_scratch_elems(int n);
+int snk_pit_roots(const snk_engine *e, const uint8_t *d_live, int n, int32_t *d_slots, uint8_t *d_alive, int32_t *d_rank,
+                  int32_t *d_count, int32_t *d_scratch, void *stream);
+int snk_pit_search_moves(const uint8_t *d_moves_a, const uint8_t *d_moves_b, const int32_t *d_rank, const uint8_t *d_alive, int n,
+                         int n_snakes, int a_cnt, int keep_other, uint8_t *d_moves, void *stream);
 int snk_pit_rows(const snk_engine *e, const uint8_t *d_live, int n, int a_cnt, int32_t *d_pairs, int32_t *d_counts,
                  int32_t *d_scratch, void *stream);
 int snk_pit_moves(const float *d_q, const int32_t *d_pairs, int m, int n, int n_snakes, uint8_t *d_moves, void *stream);

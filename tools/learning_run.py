@@ -3,7 +3,10 @@ train.py's settings (11x11, 4 snakes, 256 self-play games, depth 8, breadth 128,
 reference's own judge decide on the device arena (snake_engine.arena.Arena.test_pit: test_pit.py's 1 v 3 in both seatings
 and its two-snake duel): generation N against generation 0 and against generation N/2, with 300 and with 4 096 games.
 
-    python tools/learning_run.py [N = 30] [--out profiles] [--games 300 4096] [--seed 1]
+    python tools/learning_run.py [N = 30] [--out profiles] [--games 300 4096] [--seed 1] [--search BREADTH]
+
+--search BREADTH plays the final pits both ways: with greedy sides as above, then with both nets moving by search
+(snake_engine.arena.Searcher, depth as in training, the given breadth).
 
 Writes <out>/learning_log.csv (the trainer's log.csv) and <out>/learning_run.log: seconds per generation, the range-guard
 widenings of self-play, the fit's mode, and the pit lines in the reference's wording with a 95 % Wilson interval on every
@@ -39,6 +42,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(REPO, "profiles"))
     ap.add_argument("--games", nargs="*", type=int, default=[300, 4096])
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--search", type=int, default=None, metavar="BREADTH")
     a = ap.parse_args()
     N, out = a.generations, os.path.abspath(a.out)
     os.makedirs(out, exist_ok=True)
@@ -104,19 +108,21 @@ def main():
                 continue
             old = load(old_gen)
             names = (f"gen{N}", f"gen{old_gen}")
+            judges = [("", None)] + ([(f" search breadth {a.search}", dict(breadth=a.search, depth=s["max_MCTS_depth"]))] if a.search else [])
             for games in a.games:
-                t1 = time.time()
-                r = Arena.test_pit(new, old, games, seed=1000 + games)
-                dt = time.time() - t1
-                for me, key in ((0, "1v3_alice"), (1, "1v3_bob")):
-                    win, draw = r[key]
-                    lo, hi = wilson(round(win * games), games)
-                    say(f"[{games} games] 1v3 Win Rate of {names[me]} {win} Draw Rate = {draw}   (95 % interval {lo:.3f}-{hi:.3f}, chance 0.25)")
-                for me in (0, 1):
-                    win = r["2v2"][me]
-                    lo, hi = wilson(round(win * games), games)
-                    say(f"[{games} games] 2v2 Win Rate of {names[me]} {win}   (95 % interval {lo:.3f}-{hi:.3f}, chance 0.5)")
-                say(f"[{games} games] Competing time {dt:.1f}")
+                for tag, search in judges:
+                    t1 = time.time()
+                    r = Arena.test_pit(new, old, games, seed=1000 + games, search=search)
+                    dt = time.time() - t1
+                    for me, key in ((0, "1v3_alice"), (1, "1v3_bob")):
+                        win, draw = r[key]
+                        lo, hi = wilson(round(win * games), games)
+                        say(f"[{games} games{tag}] 1v3 Win Rate of {names[me]} {win} Draw Rate = {draw}   (95 % interval {lo:.3f}-{hi:.3f}, chance 0.25)")
+                    for me in (0, 1):
+                        win = r["2v2"][me]
+                        lo, hi = wilson(round(win * games), games)
+                        say(f"[{games} games{tag}] 2v2 Win Rate of {names[me]} {win}   (95 % interval {lo:.3f}-{hi:.3f}, chance 0.5)")
+                    say(f"[{games} games{tag}] Competing time {dt:.1f}")
     finally:
         os.chdir(here)
         shutil.rmtree(work, ignore_errors=True)

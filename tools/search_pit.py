@@ -1,0 +1,127 @@
+"""What the search buys over the raw net, and what it costs: Arena.test_pit-style matches between a side that moves by search
+(snake_engine.arena.Searcher) and a greedy side of the SAME net, 11x11.
+
+    python tools/search_pit.py [--games 300] [--breadth 16] [--depth 8] [--blocks 4] [--weights CKPT] [--seed 1]
+                               [--time] [--pairs 2] [--log profiles/arena_search.log]
+
+Strength (default): 1 v 3 with the searcher alone, 1 v 3 with the searcher's three against the greedy one, and the duel; win and
+draw rates of the searching side with their binomial 95 % intervals (Wilson), ms per turn and net evaluations per turn.
+--time: greedy v greedy, search v greedy and search v search on the same start boards and engine seed, alternating inside this
+one process, `--pairs` times; ms per turn (host clock around a match that ends in a device synchronise), net evaluations per
+turn, and the host time DeviceMCTS._ensure took (its buffers are made again whenever the number of open games changes).
+The lines are appended to --log behind a line that names the device."""
+import argparse
+import math
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "alphasnake-zero_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def wilson(k, n, z=1.959964):
+    """the binomial 95 % interval of k successes in n trials"""
+    if n == 0:
+        return 0.0, 1.0
+    p, d = k / n, 1 + z * z / n
+    c, h = (p + z * z / (2 * n)) / d, z * math.sqrt(p * (1 - p) / n + z * z / (4 * n * n)) / d
+    return max(0.0, c - h), min(1.0, c + h)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--games", type=int, default=300)
+    ap.add_argument("--breadth", type=int, nargs="+", default=[16])
+    ap.add_argument("--depth", type=int, default=8)
+    ap.add_argument("--blocks", type=int, default=4)
+    ap.add_argument("--weights", default=None, help="a saved model (.h5) (default: generation-0 Glorot weights, seed 1)")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--time", action="store_true")
+    ap.add_argument("--pairs", type=int, default=2)
+    ap.add_argument("--log", default=None)
+    a = ap.parse_args()
+    import torch
+    from snake_engine.arena import Arena, Searcher
+    from snake_engine.mcts import DeviceMCTS
+    from snake_engine.net import glorot_uniform_weights
+    from utils.alpha_nnet import AlphaNNet
+
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+
+    def say(s):                                     # the log grows as the run goes: a run that is cut short leaves what it had
+        print(s, flush=True)
+        if a.log:
+            with open(a.log, "a") as f:
+                f.write(s + "\n")
+
+    if a.weights:
+        net, what = AlphaNNet(model_name=a.weights), os.path.basename(a.weights)
+    else:
+        net = AlphaNNet(input_shape=(21, 21, 3), _weights=glorot_uniform_weights((21, 21, 3), a.blocks, seed=1))
+        what = f"generation-0 Glorot net ({a.blocks} blocks, seed 1)"
+    prop = torch.cuda.get_device_properties(0)
+    say(f"search_pit: 11x11, {what} on both sides, depth {a.depth}, {a.games} games per match, "
+        f"{torch.cuda.get_device_name(0)} ({prop.gcnArchName}, {prop.multi_processor_count} CUs), ROCm / HIP {torch.version.hip}, "
+        f"torch {torch.__version__}")
+
+    ensure_s = [0.0]
+    ensure = DeviceMCTS._ensure
+
+    def timed_ensure(self, G, health_dec):
+        t0 = time.perf_counter()
+        out = ensure(self, G, health_dec)
+        ensure_s[0] += time.perf_counter() - t0
+        return out
+    DeviceMCTS._ensure = timed_ensure
+
+    def play(snakes, a_cnt, searching, breadth, seed, start=None):
+        """one match; searching: which sides move by search -> (result, seconds, net evaluations of the searchers, start boards)"""
+        arena = Arena(11, 11, snakes, 1, a.games, seed)
+        if start is None:
+            start = arena.engine.export()
+        else:
+            arena.import_states(start)
+        sides = [Searcher(net, breadth, a.depth, seed=seed + 11 * k) if s else net for k, s in enumerate(searching)]
+        ensure_s[0] = 0.0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = arena.match(sides[0], sides[1], a_cnt)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        evals = sum(s.stats["net_evals"] for s in sides if isinstance(s, Searcher))
+        return res, dt, evals, start
+
+    play(4, 1, (True, False), 8, 99)                       # first launches, plans and range-guard scales settle outside the timing
+    play(4, 1, (False, False), 8, 99)
+    if a.time:
+        forms = [("greedy v greedy", (False, False)), ("search v greedy", (True, False)), ("search v search", (True, True))]
+        for breadth in a.breadth:
+            start, per = None, {name: [] for name, _ in forms}
+            for k in range(a.pairs):
+                for name, searching in forms:
+                    res, dt, evals, start = play(4, 1, searching, breadth, a.seed, start)
+                    per[name].append(dt / res.turns * 1e3)
+                    say(f"time: breadth {breadth:3d} rep {k} {name}: {res.turns:4d} turns, {dt:8.3f} s, {dt / res.turns * 1e3:9.3f} ms per "
+                        f"turn, {evals / res.turns:10.1f} search evaluations per turn, _ensure {ensure_s[0] * 1e3:7.1f} ms of the match "
+                        f"({100 * ensure_s[0] / dt:.2f} %), wins {res.wins_a}-{res.wins_b}, draws {res.draws}")
+            say(f"time: breadth {breadth:3d} median ms per turn: " + ", ".join(f"{n} {statistics.median(v):.3f}" for n, v in per.items()))
+    else:
+        for breadth in a.breadth:
+            seats = [("1v3, the searcher alone", 4, 1, (True, False), 0), ("1v3, three searchers against one", 4, 1, (False, True), 1),
+                     ("duel, the searcher first", 2, 1, (True, False), 0)]
+            for i, (name, snakes, a_cnt, searching, who) in enumerate(seats):
+                res, dt, evals, _ = play(snakes, a_cnt, searching, breadth, a.seed + i)
+                wins = (res.wins_a, res.wins_b)[who]
+                (wl, wh), (dl, dh) = wilson(wins, a.games), wilson(res.draws, a.games)
+                say(f"strength: breadth {breadth:3d} {name}: search wins {wins / a.games:.3f} [{wl:.3f}, {wh:.3f}], draws "
+                    f"{res.draws / a.games:.3f} [{dl:.3f}, {dh:.3f}], greedy wins {(a.games - wins - res.draws) / a.games:.3f}; "
+                    f"{res.turns} turns, {dt / res.turns * 1e3:.3f} ms per turn, {evals / res.turns:.1f} search evaluations per turn")
+
+
+if __name__ == "__main__":
+    main()
