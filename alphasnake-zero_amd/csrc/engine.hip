@@ -1241,6 +1241,126 @@ __global__ void k_pit_verdict(const uint8_t *__restrict__ state, Layout L, const
     live[gi] = 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// the same row list and verdict with an owner per seat (snake_engine/league.py): owner[g][s] in 0..K-1 replaces the team split
+// s < a_cnt, the rows are bucketed by owner, a game's verdict is in when at most one owner has snakes left
+// ------------------------------------------------------------------------------------------
+// byte s = the owner of seat s of game gi if that snake is alive, the game open and the owner below K; 0xFF otherwise
+__device__ static inline uint64_t lg_owner_bytes(const uint8_t *__restrict__ state, const Layout &L, const uint8_t *live,
+                                                 const uint8_t *__restrict__ owner, int K, int gi, int n)
+{
+    uint64_t w = ~0ull;
+    if (gi >= n || !live[gi]) return w;
+    const SnakeMeta *meta = (const SnakeMeta *)(state + (size_t)gi * L.stride + L.meta_off);
+    for (int s = 0; s < L.S; ++s) {
+        const uint32_t o = owner[(size_t)gi * L.S + s];
+        if (meta[s].alive && o < (uint32_t)K) w = (w & ~(0xFFull << (8 * s))) | ((uint64_t)o << (8 * s));
+    }
+    return w;
+}
+
+// how many of the eight bytes of w equal o
+__device__ static inline int lg_count_bytes(uint64_t w, uint32_t o)
+{
+    int c = 0;
+#pragma unroll
+    for (int s = 0; s < SNK_MAX_SNAKES; ++s) c += ((uint32_t)(w >> (8 * s)) & 0xFFu) == o ? 1 : 0;
+    return c;
+}
+
+// rows of each owner in the block's PIT_TILE games: tile_sums[K b + o], a block scan per owner (column by column)
+__global__ __launch_bounds__(CMP_THREADS) void k_lg_count(const uint8_t *__restrict__ state, Layout L, const uint8_t *__restrict__ live,
+                                                          int n, const uint8_t *__restrict__ owner, int K, int32_t *__restrict__ tile_sums)
+{
+    __shared__ int sh[8];
+    const int base = blockIdx.x * PIT_TILE + threadIdx.x * PIT_ITEMS;
+    uint64_t w[PIT_ITEMS];
+    for (int q = 0; q < PIT_ITEMS; ++q) w[q] = lg_owner_bytes(state, L, live, owner, K, base + q, n);
+    for (int o = 0; o < K; ++o) {
+        int c = 0;
+        for (int q = 0; q < PIT_ITEMS; ++q) c += lg_count_bytes(w[q], (uint32_t)o);
+        int total;
+        block_exclusive_scan_256(c, &total, sh);
+        if (threadIdx.x == 0) tile_sums[(size_t)K * blockIdx.x + o] = total;
+    }
+}
+
+// single block: exclusive scan of every column of the tile sums (any count, 256 tiles at a time); counts[o] = owner o's rows
+__global__ __launch_bounds__(CMP_THREADS) void k_lg_scan(int32_t *__restrict__ tile_sums, int n_tiles, int K, int32_t *__restrict__ counts)
+{
+    __shared__ int sh[8];
+    for (int o = 0; o < K; ++o) {
+        int carry = 0;
+        for (int b = 0; b < n_tiles; b += CMP_THREADS) {
+            const int i = b + threadIdx.x;
+            const int v = i < n_tiles ? tile_sums[(size_t)K * i + o] : 0;
+            int total;
+            const int ex = block_exclusive_scan_256(v, &total, sh);
+            if (i < n_tiles) tile_sums[(size_t)K * i + o] = carry + ex;
+            carry += total;
+        }
+        if (threadIdx.x == 0) counts[o] = carry;
+    }
+}
+
+// owner o's rows at [sum of counts below o, + counts[o]); inside an owner games ascending, ids ascending
+__global__ __launch_bounds__(CMP_THREADS) void k_lg_scatter(const uint8_t *__restrict__ state, Layout L, const uint8_t *__restrict__ live,
+                                                            int n, const uint8_t *__restrict__ owner, int K,
+                                                            const int32_t *__restrict__ tile_offs, const int32_t *__restrict__ counts,
+                                                            int32_t *__restrict__ pairs)
+{
+    __shared__ int sh[8];
+    const int base = blockIdx.x * PIT_TILE + threadIdx.x * PIT_ITEMS;
+    uint64_t w[PIT_ITEMS];
+    for (int q = 0; q < PIT_ITEMS; ++q) w[q] = lg_owner_bytes(state, L, live, owner, K, base + q, n);
+    int owner_base = 0;
+    for (int o = 0; o < K; ++o) {
+        int c = 0;
+        for (int q = 0; q < PIT_ITEMS; ++q) c += lg_count_bytes(w[q], (uint32_t)o);
+        int total;
+        int pos = owner_base + tile_offs[(size_t)K * blockIdx.x + o] + block_exclusive_scan_256(c, &total, sh);
+        if (c) {
+            for (int q = 0; q < PIT_ITEMS; ++q) {
+#pragma unroll
+                for (int s = 0; s < SNK_MAX_SNAKES; ++s) {
+                    if (((uint32_t)(w[q] >> (8 * s)) & 0xFFu) == (uint32_t)o) {
+                        pairs[2 * (size_t)pos] = base + q;
+                        pairs[2 * (size_t)pos + 1] = s;
+                        ++pos;
+                    }
+                }
+            }
+        }
+        owner_base += counts[o];
+    }
+}
+
+// the verdict of one turn with an owner per seat (pit_mp_game_runner.py:39-62), a thread per game
+__global__ void k_lg_verdict(const uint8_t *__restrict__ state, Layout L, const uint8_t *__restrict__ done,
+                             const int8_t *__restrict__ rewards, int n, const uint8_t *__restrict__ owner, int turn, uint8_t *live,
+                             int32_t *__restrict__ winner, int32_t *__restrict__ winner_owner, int32_t *__restrict__ length)
+{
+    const int gi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gi >= n || !live[gi]) return;
+    const uint8_t *own = owner + (size_t)gi * L.S;
+    int w = -1;
+    if (done[gi]) {                                           // :43-47 the last id whose reward is +1, None without one
+        for (int s = 0; s < L.S; ++s) if (rewards[(size_t)gi * L.S + s] == 1) w = s;
+    } else {                                                  // :48-60 at most one owner left: the first alive id wins
+        const uint32_t b = pit_alive_bits(state, L, live, gi, n);
+        if (b) {
+            w = __ffs((int)b) - 1;
+            const uint8_t first = own[w];
+            for (int s = w + 1; s < L.S; ++s)
+                if (((b >> s) & 1u) && own[s] != first) return;   // two owners present: the game stays open
+        }
+    }
+    winner[gi] = w;
+    winner_owner[gi] = w >= 0 ? (int32_t)own[w] : -1;
+    length[gi] = turn;
+    live[gi] = 0;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 // square boards of 5x5 (the eight standard start cells are distinct from there on, game.py:25-29) to 19x19 (SNK_MAX_CELLS);
 // the reference's observation is a rot90 of a (2H-1)x(2W-1) canvas, so only square boards batch (game.py:257)
@@ -1465,6 +1585,47 @@ extern "C" int snk_pit_verdict(const snk_engine *e, const uint8_t *d_done, const
     SNK_REQUIRE(d_done && d_rewards && d_live && d_winner && d_length, "snk_pit_verdict: NULL argument");
     k_pit_verdict<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(e->d_state, e->L, d_done, d_rewards, n, (1u << a_cnt) - 1u, turn,
                                                                    d_live, d_winner, d_length);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_owned_scratch_elems(int n, int n_owners)
+{
+    if (n < 0 || n_owners < 1 || n_owners > SNK_PIT_MAX_OWNERS) return -1;
+    return n_owners * ((n + PIT_TILE - 1) / PIT_TILE) + n_owners;
+}
+
+extern "C" int snk_pit_rows_owned(const snk_engine *e, const uint8_t *d_live, int n, const uint8_t *d_owner, int n_owners,
+                                  int32_t *d_pairs, int32_t *d_counts, int32_t *d_scratch, void *stream)
+{
+    SNK_REQUIRE(e && d_counts, "snk_pit_rows_owned: NULL argument");
+    SNK_REQUIRE(n >= 0 && n <= e->n_slots, "snk_pit_rows_owned: n=%d exceeds %d slots", n, e->n_slots);
+    SNK_REQUIRE(n_owners >= 1 && n_owners <= SNK_PIT_MAX_OWNERS, "snk_pit_rows_owned: n_owners=%d outside 1..%d", n_owners,
+                SNK_PIT_MAX_OWNERS);
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) { SNK_CHECK_HIP(hipMemsetAsync(d_counts, 0, n_owners * sizeof(int32_t), st)); return 0; }
+    SNK_REQUIRE(d_live && d_owner && d_pairs && d_scratch, "snk_pit_rows_owned: NULL argument");
+    const int tiles = (n + PIT_TILE - 1) / PIT_TILE;
+    k_lg_count<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, e->L, d_live, n, d_owner, n_owners, d_scratch);
+    k_lg_scan<<<1, CMP_THREADS, 0, st>>>(d_scratch, tiles, n_owners, d_counts);
+    k_lg_scatter<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, e->L, d_live, n, d_owner, n_owners, d_scratch, d_counts, d_pairs);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_verdict_owned(const snk_engine *e, const uint8_t *d_done, const int8_t *d_rewards, int n, const uint8_t *d_owner,
+                                     int n_owners, int turn, uint8_t *d_live, int32_t *d_winner, int32_t *d_winner_owner,
+                                     int32_t *d_length, void *stream)
+{
+    SNK_REQUIRE(e != nullptr, "snk_pit_verdict_owned: engine is NULL");
+    SNK_REQUIRE(n >= 0 && n <= e->n_slots, "snk_pit_verdict_owned: n=%d exceeds %d slots", n, e->n_slots);
+    SNK_REQUIRE(n_owners >= 1 && n_owners <= SNK_PIT_MAX_OWNERS, "snk_pit_verdict_owned: n_owners=%d outside 1..%d", n_owners,
+                SNK_PIT_MAX_OWNERS);
+    if (n == 0) return 0;
+    SNK_REQUIRE(d_done && d_rewards && d_owner && d_live && d_winner && d_winner_owner && d_length,
+                "snk_pit_verdict_owned: NULL argument");
+    k_lg_verdict<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(e->d_state, e->L, d_done, d_rewards, n, d_owner, turn, d_live,
+                                                                  d_winner, d_winner_owner, d_length);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -117,6 +117,9 @@ PROTOTYPES = {
     "snk_pit_rows": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
     "snk_pit_moves": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "snk_pit_verdict": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "snk_pit_owned_scratch_elems": (i32, [i32, i32]),
+    "snk_pit_rows_owned": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, vp]),
+    "snk_pit_verdict_owned": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]),
     "snk_pit_roots": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     "snk_pit_search_moves": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "snk_head_f32": (i32, [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),

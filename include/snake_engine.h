@@ -56,7 +56,8 @@ const char *snk_last_error(void);
                              * snk_engine_import_at_sync and snk_engine_observe_rows added; 113: the MX-FP8 tower's five entry
                              * points: a caller compares it with snk_version().  The arena's entry points (snk_pit_*,
                              * snk_engine_step_active_tape) were added under 113, and so were the searching pit's
-                             * (snk_pit_roots, snk_pit_search_moves): no argument list of an older one changed */
+                             * (snk_pit_roots, snk_pit_search_moves) and the league's (snk_pit_owned_scratch_elems,
+                             * snk_pit_rows_owned, snk_pit_verdict_owned): no argument list of an older one changed */
 int snk_version(void);
 
 /* ---- engine lifetime -------------------------------------------------------------------
@@ -520,6 +521,31 @@ int snk_pit_rows(const snk_engine *e, const uint8_t *d_live, int n, int a_cnt, i
 int snk_pit_moves(const float *d_q, const int32_t *d_pairs, int m, int n, int n_snakes, uint8_t *d_moves, void *stream);
 int snk_pit_verdict(const snk_engine *e, const uint8_t *d_done, const int8_t *d_rewards, int n, int a_cnt, int turn,
                     uint8_t *d_live, int32_t *d_winner, int32_t *d_length, void *stream);
+
+/* ---- the league: an owner per seat (pit_mp_game_runner.py:14-63 with up to SNK_PIT_MAX_OWNERS nets) --------------------------------
+ * The team split id < a_cnt becomes a table d_owner uint8[n][S], row g = the owners (0 .. n_owners-1) of game g's seats; every
+ * owner is a net of its own.  A turn is snk_pit_rows_owned, the read-back of the n_owners row counts, snk_engine_observe over all
+ * rows, each net on its own slice in owner order, snk_pit_moves, snk_engine_step_active_tape with d_active = d_live,
+ * snk_engine_rewards, snk_pit_verdict_owned (snake_engine/league.py).  n_owners outside 1..SNK_PIT_MAX_OWNERS is an error.  With
+ * n_owners = 2 and d_owner[g][s] = (s >= a_cnt) both calls write what snk_pit_rows / snk_pit_verdict write.
+ * snk_pit_rows_owned (pit_mp_game_runner.py:23-35): d_pairs int32[n*S][2] = (slot, snake id) of every alive snake of every live
+ *   game -- owner 0's rows first, then owner 1's, ... owner n_owners-1's; inside an owner games ascending, ids ascending inside a
+ *   game (ids_A + ids_B with a list per owner); d_counts int32[n_owners] = the rows per owner; rows past their sum are not
+ *   written.  A seat whose owner byte is >= n_owners has no row and counts nowhere.  Deterministic (a block scan per owner, no
+ *   atomics).  d_scratch: int32[snk_pit_owned_scratch_elems(n, n_owners)] (-1 for an n_owners outside the range).
+ * snk_pit_verdict_owned (pit_mp_game_runner.py:39-62), after the step: d_done uint8[n] from the step, d_rewards int8[n][S] from
+ *   snk_engine_rewards.  A live game that is done: d_winner = the largest id whose reward is +1, -1 (None) without one.  A live
+ *   game that is not done and whose alive snakes all belong to one owner (:48-60 with a team read as an owner; no alive snake
+ *   counts as one owner): d_winner = the smallest alive id, -1 without one.  Both: d_live = 0, d_length = turn, d_winner_owner =
+ *   the winner's owner byte, -1 without a winner.  Every other game keeps its d_live, d_winner int32[n], d_winner_owner int32[n]
+ *   and d_length int32[n] entries.                                                                                             */
+#define SNK_PIT_MAX_OWNERS 16
+int snk_pit_owned_scratch_elems(int n, int n_owners);
+int snk_pit_rows_owned(const snk_engine *e, const uint8_t *d_live, int n, const uint8_t *d_owner, int n_owners, int32_t *d_pairs,
+                       int32_t *d_counts, int32_t *d_scratch, void *stream);
+int snk_pit_verdict_owned(const snk_engine *e, const uint8_t *d_done, const int8_t *d_rewards, int n, const uint8_t *d_owner,
+                          int n_owners, int turn, uint8_t *d_live, int32_t *d_winner, int32_t *d_winner_owner, int32_t *d_length,
+                          void *stream);
 
 /* ---- training half: AlphaNNet.train = model.fit (alpha_nnet.py:58-59) -------------------------
  * Training-mode batch normalisation of a 128-channel channels-last float32 activation [rows = n * h * w][128] (the

@@ -1,0 +1,143 @@
+"""A league of K nets in one device pit match (snake_engine.league): the cross table, the scores and Elo-scaled Bradley-Terry
+ratings of a round robin, 11x11.
+
+    python tools/league.py [--nets 6] [--games 300] [--seats duel|1v3|ffa] [--blocks 4] [--models NAME G0 G1 ...] [--seed 1]
+                           [--time] [--pairs 3] [--log profiles/league_ab.log]
+
+--nets K plays generation-0 Glorot nets of --blocks blocks, seeds 1..K; --models NAME G0 G1 ... loads NAME<G>.h5 instead (e.g.
+--models models/gen 0 15 30).  Every line-up of snake_engine.league.schedule plays --games games, all in lock step in one engine.
+--time (duel and 1v3): the league form -- one League.play of all pairings -- against the form the arena offers without it -- one
+Arena.match(net_i, net_j, 1) of --games games per ordered pair, one after another -- alternating inside this one process,
+`--pairs` times; a host clock around a form that ends in a device synchronise.  Seconds per form, turns played, rows evaluated,
+then the medians and their ratio.  The lines are appended to --log behind a line that names the device."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "alphasnake-zero_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def format_table(names, t, r):
+    """the cross table (wins of the row's net over the column's, draws behind a slash), the scores and the ratings as lines"""
+    K = len(names)
+    wide = max(7, max(len(n) for n in names) + 1)
+    lines = [" " * wide + "".join(f"{n:>{wide + 2}s}" for n in names) + f"{'score':>9s}{'rating':>9s}"]
+    for a in range(K):
+        cells = "".join(f"{'-':>{wide + 2}s}" if a == b else f"{f'{t.wins[a][b]}/{t.draws[a][b]}':>{wide + 2}s}" for b in range(K))
+        lines.append(f"{names[a]:<{wide}s}{cells}{t.score[a]:9.3f}{r[a]:+9.1f}")
+    return lines
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nets", type=int, default=6)
+    ap.add_argument("--games", type=int, default=300)
+    ap.add_argument("--seats", choices=("duel", "1v3", "ffa"), default="duel")
+    ap.add_argument("--blocks", type=int, default=4)
+    ap.add_argument("--models", nargs="+", default=None, metavar="NAME G0 G1 ...")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--time", action="store_true")
+    ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--log", default=None)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from snake_engine.arena import Arena
+    from snake_engine.league import SEATS, League, ratings, schedule, table
+    from snake_engine.net import glorot_uniform_weights
+    from utils.alpha_nnet import AlphaNNet
+
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+
+    def say(s):                                     # the log grows as the run goes: a run that is cut short leaves what it had
+        print(s, flush=True)
+        if a.log:
+            with open(a.log, "a") as f:
+                f.write(s + "\n")
+
+    if a.models:
+        names = [f"{os.path.basename(a.models[0])}{g}" for g in a.models[1:]]
+        nets = [AlphaNNet(model_name=f"{a.models[0]}{g}.h5") for g in a.models[1:]]
+        what = "checkpoints " + " ".join(names)
+    else:
+        names = [f"seed{s}" for s in range(1, a.nets + 1)]
+        nets = [AlphaNNet(input_shape=(21, 21, 3), _weights=glorot_uniform_weights((21, 21, 3), a.blocks, seed=s))
+                for s in range(1, a.nets + 1)]
+        what = f"generation-0 Glorot nets ({a.blocks} blocks, seeds 1..{a.nets})"
+
+    class Counted:
+        """a net that counts the rows it is given (a host counter: no synchronisation)"""
+        rows = 0
+
+        def __init__(self, net):
+            self.net = net
+
+        def v_device(self, planes, mask):
+            Counted.rows += planes.shape[0]
+            return self.net.v_device(planes, mask)
+
+    nets = [Counted(net) for net in nets]
+    K, S = len(nets), SEATS[a.seats]
+    owner = schedule(K, a.games, a.seats)
+    prop = torch.cuda.get_device_properties(0)
+    say(f"league: 11x11, {a.seats}, {K} nets: {what}, {a.games} games per line-up, {len(owner)} games in all, "
+        f"{torch.cuda.get_device_name(0)} ({prop.gcnArchName}, {prop.multi_processor_count} CUs), ROCm / HIP {torch.version.hip}, "
+        f"torch {torch.__version__}")
+
+    def league_form(seed):
+        """one League.play of every line-up -> (result, seconds, rows evaluated)"""
+        Counted.rows = 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = League(11, 11, S, 1, len(owner), seed).play(nets, owner)      # both forms pay for their engines inside the clock
+        torch.cuda.synchronize()
+        return res, time.perf_counter() - t0, Counted.rows
+
+    def arena_form(seed):
+        """one Arena.match per ordered pair, one after another -> (winner owners in schedule order, seconds, turns, rows)"""
+        wo, turns, Counted.rows = [], 0, 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(K):
+            for j in range(K):
+                if i != j:
+                    r = Arena(11, 11, S, 1, a.games, seed + 31 * (i * K + j)).match(nets[i], nets[j], 1)
+                    wo.append(np.where(r.winners < 0, -1, np.where(r.winners < 1, i, j)))
+                    turns += r.turns
+        torch.cuda.synchronize()
+        return np.concatenate(wo), time.perf_counter() - t0, turns, Counted.rows
+
+    Arena(11, 11, S, 1, 64, 99).match(nets[0], nets[-1], 1)    # first launches, plans and range-guard scales settle outside the timing
+    League(11, 11, S, 1, len(owner), 99).play(nets, owner)
+    if a.time:
+        if a.seats == "ffa":
+            raise SystemExit("--time compares with Arena.match, which has no free-for-all")
+        per = {"league": [], "arena": []}
+        for k in range(a.pairs):
+            res, dt, rows = league_form(a.seed)
+            per["league"].append(dt)
+            say(f"time: pair {k} league form: 1 match of {len(owner)} games, {res.turns} turns, {rows} rows evaluated, "
+                f"{dt:8.3f} s, {dt / res.turns * 1e3:.3f} ms per turn")
+            wo, dt, turns, rows = arena_form(a.seed)
+            per["arena"].append(dt)
+            say(f"time: pair {k} arena form: {K * (K - 1)} matches of {a.games} games, {turns} turns, {rows} rows evaluated, "
+                f"{dt:8.3f} s, {dt / turns * 1e3:.3f} ms per turn")
+        ml, ma = statistics.median(per["league"]), statistics.median(per["arena"])
+        say(f"time: median seconds: league form {ml:.3f} (min {min(per['league']):.3f}, max {max(per['league']):.3f}), arena form "
+            f"{ma:.3f} (min {min(per['arena']):.3f}, max {max(per['arena']):.3f}), ratio of medians arena / league {ma / ml:.2f}x")
+        return
+    res, dt, _ = league_form(a.seed)
+    t = table(res, owner, K)
+    say(f"{res.turns} turns, {dt:.3f} s, {dt / res.turns * 1e3:.3f} ms per turn; wins of the row's net over the column's / draws")
+    for line in format_table(names, t, ratings(t.wins, t.draws)):
+        say(line)
+
+
+if __name__ == "__main__":
+    main()

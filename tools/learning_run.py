@@ -3,10 +3,13 @@ train.py's settings (11x11, 4 snakes, 256 self-play games, depth 8, breadth 128,
 reference's own judge decide on the device arena (snake_engine.arena.Arena.test_pit: test_pit.py's 1 v 3 in both seatings
 and its two-snake duel): generation N against generation 0 and against generation N/2, with 300 and with 4 096 games.
 
-    python tools/learning_run.py [N = 30] [--out profiles] [--games 300 4096] [--seed 1] [--search BREADTH]
+    python tools/learning_run.py [N = 30] [--out profiles] [--games 300 4096] [--seed 1] [--search BREADTH] [--league M]
 
 --search BREADTH plays the final pits both ways: with greedy sides as above, then with both nets moving by search
 (snake_engine.arena.Searcher, depth as in training, the given breadth).
+
+--league M adds one league match (snake_engine.league.round_robin, duels, the first game count) among M generations spread
+evenly from 0 to N: the cross table, the scores and the Bradley-Terry ratings, beside the pit lines.
 
 Writes <out>/learning_log.csv (the trainer's log.csv) and <out>/learning_run.log: seconds per generation, the range-guard
 widenings of self-play, the fit's mode, and the pit lines in the reference's wording with a 95 % Wilson interval on every
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--games", nargs="*", type=int, default=[300, 4096])
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--search", type=int, default=None, metavar="BREADTH")
+    ap.add_argument("--league", type=int, default=None, metavar="M")
     a = ap.parse_args()
     N, out = a.generations, os.path.abspath(a.out)
     os.makedirs(out, exist_ok=True)
@@ -123,6 +127,18 @@ def main():
                         lo, hi = wilson(round(win * games), games)
                         say(f"[{games} games{tag}] 2v2 Win Rate of {names[me]} {win}   (95 % interval {lo:.3f}-{hi:.3f}, chance 0.5)")
                     say(f"[{games} games{tag}] Competing time {dt:.1f}")
+        if a.league:
+            from league import format_table                      # tools/league.py
+            from snake_engine.league import round_robin
+            M = max(2, min(a.league, N + 1, 16))
+            gens = sorted({round(i * N / (M - 1)) for i in range(M)})
+            games = a.games[0] if a.games else 300
+            t1 = time.time()
+            t, r = round_robin([load(g) for g in gens], games=games, seats="duel", height=h, width=w, seed=2000 + games)
+            say(f"[league, {games} games per ordered pair, duels] generations {gens}: wins of the row's net over the column's / draws, "
+                f"score, rating (generation {gens[0]} = 0); {time.time() - t1:.1f} s")
+            for line in format_table([f"gen{g}" for g in gens], t, r):
+                say(line)
     finally:
         os.chdir(here)
         shutil.rmtree(work, ignore_errors=True)
