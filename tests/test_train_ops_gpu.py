@@ -225,7 +225,8 @@ def _net64(torch, ws, X, Y):
 
 @pytest.mark.parametrize("n,blocks,hw", [(40, 2, 21), (23, 4, 21), (5, 1, 37), (9, 1, 13), (3, 10, 37), (41, 1, 37)])
 def test_one_whole_step_matches_float64_with_the_same_relu_masks(torch_gpu, n, blocks, hw):
-    """hw = 37: BASELINE configs[4]'s 19 x 19 board (its weight gradient runs in slabs of five image rows; (3, 10, 37) is that
+    """hw = 37: BASELINE configs[4]'s 19 x 19 board (its weight gradient runs the window form's (NK 4, MAXX 5, WT 37) body, as every
+    width up to 46 does; the slab form and more than one image per group: tests/test_wgrad_stream_gpu.py; (3, 10, 37) is that
     config's 10-block net; n = 41 is the smallest batch whose convolutions run that canvas's batched plan, nine blocks of 5 or 4
     M tiles per image -- tests/conv_plan_ref.py), 13: a 7 x 7 board"""
     torch = torch_gpu
@@ -437,7 +438,8 @@ def test_input_gradient_epilogue_reads_nothing_behind_the_last_image(torch_gpu, 
         assert float(s1.abs().max()) > 0
 
 
-@pytest.mark.parametrize("n,blocks,hw", [(24, 2, 21), (6, 1, 37), (10, 2, 13)])
+@pytest.mark.parametrize("n,blocks,hw", [(24, 2, 21), (6, 1, 37), (10, 2, 13),
+                                         (130, 1, 13)])    # two images in an image group of the weight gradient (tests/test_wgrad_stream_gpu.py)
 def test_deferred_batch_norm_reads_the_same_values_as_the_written_activation(torch_gpu, monkeypatch, n, blocks, hw):
     """round 5: the activation between the two convolutions of a residual block is never written -- its three readers (the
     block's second convolution, that layer's weight gradient, the first layer's batch-norm backward) evaluate relu(y * scale +
