@@ -1361,6 +1361,76 @@ __global__ void k_lg_verdict(const uint8_t *__restrict__ state, Layout L, const 
     live[gi] = 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// the root games of every searching owner (agent.py:25-99 behind pit_mp_game_runner.py:23-38 with an owner per seat): owner o's
+// list is the open games in which a snake of o is alive, the lists stand one after another in owner order (k_pit_roots_* bucketed
+// the way k_lg_* bucket the rows).  search_mask bit o = owner o searches; an owner outside the mask has no list
+// ------------------------------------------------------------------------------------------
+// games of each searching owner in the block's PIT_TILE games: tile_sums[K b + o] (0 for an owner outside the mask), which
+// k_lg_scan scans column by column
+__global__ __launch_bounds__(CMP_THREADS) void k_lgs_count(const uint8_t *__restrict__ state, Layout L, const uint8_t *__restrict__ live,
+                                                           int n, const uint8_t *__restrict__ owner, int K, uint32_t search_mask,
+                                                           int32_t *__restrict__ tile_sums)
+{
+    __shared__ int sh[8];
+    const int base = blockIdx.x * PIT_TILE + threadIdx.x * PIT_ITEMS;
+    uint64_t w[PIT_ITEMS];
+    for (int q = 0; q < PIT_ITEMS; ++q) w[q] = lg_owner_bytes(state, L, live, owner, K, base + q, n);
+    for (int o = 0; o < K; ++o) {
+        int total = 0;
+        if ((search_mask >> o) & 1u) {                        // the mask is the same for every thread of the block
+            int c = 0;
+            for (int q = 0; q < PIT_ITEMS; ++q) c += lg_count_bytes(w[q], (uint32_t)o) ? 1 : 0;
+            block_exclusive_scan_256(c, &total, sh);
+        }
+        if (threadIdx.x == 0) tile_sums[(size_t)K * blockIdx.x + o] = total;
+    }
+}
+
+// owner o's games at [sum of counts below o, + counts[o]), slots ascending: slots[r] = the game, alive[r][s] = the alive flags
+// of ALL its snakes, rank[g][s] = r for an alive seat of o in that game; every other cell of rank takes -1.  Every cell of rank
+// is written once, by the thread of its game; nothing past the sum of the counts is written
+__global__ __launch_bounds__(CMP_THREADS) void k_lgs_scatter(const uint8_t *__restrict__ state, Layout L, const uint8_t *__restrict__ live,
+                                                             int n, const uint8_t *__restrict__ owner, int K, uint32_t search_mask,
+                                                             const int32_t *__restrict__ tile_offs, const int32_t *__restrict__ counts,
+                                                             int32_t *__restrict__ slots, uint8_t *__restrict__ alive,
+                                                             int32_t *__restrict__ rank)
+{
+    __shared__ int sh[8];
+    const int base = blockIdx.x * PIT_TILE + threadIdx.x * PIT_ITEMS;
+    uint64_t w[PIT_ITEMS];
+    for (int q = 0; q < PIT_ITEMS; ++q) {
+        const int gi = base + q;
+        w[q] = lg_owner_bytes(state, L, live, owner, K, gi, n);
+        if (gi >= n) continue;
+        for (int s = 0; s < L.S; ++s) {                       // a seat no list covers: dead, closed, no owner, or a greedy owner
+            const uint32_t o = (uint32_t)(w[q] >> (8 * s)) & 0xFFu;
+            if (o == 0xFFu || !((search_mask >> o) & 1u)) rank[(size_t)gi * L.S + s] = -1;
+        }
+    }
+    int owner_base = 0;
+    for (int o = 0; o < K; ++o) {
+        if (!((search_mask >> o) & 1u)) continue;             // counts[o] is 0
+        int c = 0;
+        for (int q = 0; q < PIT_ITEMS; ++q) c += lg_count_bytes(w[q], (uint32_t)o) ? 1 : 0;
+        int total;
+        int pos = owner_base + tile_offs[(size_t)K * blockIdx.x + o] + block_exclusive_scan_256(c, &total, sh);
+        if (c) {
+            for (int q = 0; q < PIT_ITEMS; ++q) {
+                if (!lg_count_bytes(w[q], (uint32_t)o)) continue;     // never true for a game past the end: its bytes are 0xFF
+                const int gi = base + q;
+                const SnakeMeta *meta = (const SnakeMeta *)(state + (size_t)gi * L.stride + L.meta_off);
+                for (int s = 0; s < L.S; ++s) {
+                    alive[(size_t)pos * L.S + s] = meta[s].alive ? 1 : 0;
+                    if (((uint32_t)(w[q] >> (8 * s)) & 0xFFu) == (uint32_t)o) rank[(size_t)gi * L.S + s] = pos;
+                }
+                slots[pos++] = gi;
+            }
+        }
+        owner_base += counts[o];
+    }
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 // square boards of 5x5 (the eight standard start cells are distinct from there on, game.py:25-29) to 19x19 (SNK_MAX_CELLS);
 // the reference's observation is a rot90 of a (2H-1)x(2W-1) canvas, so only square boards batch (game.py:257)
@@ -1626,6 +1696,27 @@ extern "C" int snk_pit_verdict_owned(const snk_engine *e, const uint8_t *d_done,
                 "snk_pit_verdict_owned: NULL argument");
     k_lg_verdict<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(e->d_state, e->L, d_done, d_rewards, n, d_owner, turn, d_live,
                                                                   d_winner, d_winner_owner, d_length);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_roots_owned(const snk_engine *e, const uint8_t *d_live, int n, const uint8_t *d_owner, int n_owners,
+                                   uint32_t search_mask, int32_t *d_counts, int32_t *d_slots, uint8_t *d_alive, int32_t *d_rank,
+                                   int32_t *d_scratch, void *stream)
+{
+    SNK_REQUIRE(e && d_counts, "snk_pit_roots_owned: NULL argument");
+    SNK_REQUIRE(n >= 0 && n <= e->n_slots, "snk_pit_roots_owned: n=%d exceeds %d slots", n, e->n_slots);
+    SNK_REQUIRE(n_owners >= 1 && n_owners <= SNK_PIT_MAX_OWNERS, "snk_pit_roots_owned: n_owners=%d outside 1..%d", n_owners,
+                SNK_PIT_MAX_OWNERS);
+    hipStream_t st = (hipStream_t)stream;
+    search_mask &= (1u << n_owners) - 1u;
+    if (n == 0 || search_mask == 0u) { SNK_CHECK_HIP(hipMemsetAsync(d_counts, 0, n_owners * sizeof(int32_t), st)); return 0; }
+    SNK_REQUIRE(d_live && d_owner && d_slots && d_alive && d_rank && d_scratch, "snk_pit_roots_owned: NULL argument");
+    const int tiles = (n + PIT_TILE - 1) / PIT_TILE;
+    k_lgs_count<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, e->L, d_live, n, d_owner, n_owners, search_mask, d_scratch);
+    k_lg_scan<<<1, CMP_THREADS, 0, st>>>(d_scratch, tiles, n_owners, d_counts);
+    k_lgs_scatter<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, e->L, d_live, n, d_owner, n_owners, search_mask, d_scratch, d_counts, d_slots,
+                                                 d_alive, d_rank);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -395,6 +395,20 @@ __global__ void k_pit_search_moves(const uint8_t *__restrict__ moves_a, const ui
     moves[t] = mv;
 }
 
+// the same merge with an owner per seat (snake_engine/league.py): found is [total][S], the searching owners' root moves one
+// owner after another in the order of snk_pit_roots_owned's lists, rank[g][s] the row of that array a seat reads (-1: no
+// searcher moves it).  A thread per (slot, snake); a cell without a row keeps what snk_pit_moves wrote (keep_other) or takes 1
+__global__ void k_pit_search_moves_owned(const uint8_t *__restrict__ found, const int32_t *__restrict__ rank, int n, int S, int total,
+                                         int keep_other, uint8_t *__restrict__ moves)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)n * S) return;
+    const int s = (int)(t % S);
+    const int r = rank[t];
+    if (r >= 0 && r < total) moves[t] = found[(size_t)r * S + s];
+    else if (!keep_other) moves[t] = 1;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 static int tt_alloc(snk_tt *t, uint64_t cap)
 {
@@ -682,6 +696,21 @@ extern "C" int snk_pit_search_moves(const uint8_t *d_moves_a, const uint8_t *d_m
     const size_t tot = (size_t)n * n_snakes;
     k_pit_search_moves<<<(unsigned)((tot + 255) / 256), 256, 0, (hipStream_t)stream>>>(d_moves_a, d_moves_b, d_rank, d_alive, n, n_snakes,
                                                                                        a_cnt, keep_other, d_moves);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_search_moves_owned(const uint8_t *d_found, const int32_t *d_rank, int n, int n_snakes, int total, int keep_other,
+                                          uint8_t *d_moves, void *stream)
+{
+    SNK_REQUIRE(n >= 0 && n_snakes >= 1 && n_snakes <= SNK_MAX_SNAKES, "snk_pit_search_moves_owned: n=%d, n_snakes=%d", n, n_snakes);
+    SNK_REQUIRE(total >= 0 && (long long)total <= (long long)n * n_snakes, "snk_pit_search_moves_owned: %d rows for %d games of %d snakes",
+                total, n, n_snakes);
+    if (n == 0) return 0;
+    SNK_REQUIRE(d_rank && d_moves && (total == 0 || d_found), "snk_pit_search_moves_owned: NULL argument");
+    const size_t tot = (size_t)n * n_snakes;
+    k_pit_search_moves_owned<<<(unsigned)((tot + 255) / 256), 256, 0, (hipStream_t)stream>>>(d_found, d_rank, n, n_snakes, total, keep_other,
+                                                                                             d_moves);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -16,7 +16,22 @@ With two nets and owner[g][s] = (s >= a_cnt) every launch and every batch is wha
 and turns are the same bit for bit.  What the table adds: a free-for-all in which every seat belongs to another net, and every
 pairing of a round robin in lock step in one engine (``schedule``, ``round_robin``), scored by ``table`` and ``ratings``.
 
-Searching sides (arena.Searcher) are refused: a searcher simulates whole games and would need the sub-list of games it has a seat in.
+Any owner may instead be an ``arena.Searcher`` (``League.play_search``; ``play`` itself keeps refusing one): a searcher simulates
+whole games, so each turn it gets the sub-list of open games in which it holds a seat -- a game that is open, with an alive snake
+whose seat is the owner's -- and only its own seats take the moves it finds.  A turn of ``League.play_search``:
+
+    snk_pit_roots_owned           per searching owner the open games it holds a seat in, the lists one after another in owner
+                                  order, the alive rows of those games, and per seat the row of the list it reads
+    snk_pit_rows_owned            only when some owner is greedy, over a second table made once per match: the searching owners'
+                                  bytes out of range, the greedy owners renumbered densely, so their rows are contiguous
+    the turn's read-back          the greedy row counts and the K game counts, one tensor, one .tolist(); all zeros ends the match
+    the greedy owners             observe + each net on its own slice, one snk_pit_moves (the array is filled with 1)
+    searcher.search, end_of_turn  in owner order, each on its own slice of the lists; an owner without a game is skipped for good
+    snk_pit_search_moves_owned    merges the found moves into the dense move array
+    step, rewards, verdict        as above
+
+With two Searchers and the two-team table this is ``Arena.match`` with the same Searchers, and with no Searcher it is ``play``.
+The league's own read-back stays one per turn; the searches read back on their own (snake_engine/arena.py).
 """
 from collections import namedtuple
 
@@ -65,6 +80,7 @@ class League:
         self._winner = eng.new((n,), torch.int32)
         self._winner_owner = eng.new((n,), torch.int32)
         self._length = eng.new((n,), torch.int32)
+        self._roots = None                        # the searching turn's buffers, made by the first match that searches
 
     @classmethod
     def from_engine(cls, engine):
@@ -78,14 +94,16 @@ class League:
         self.engine.import_states(states)
         self._fresh = True
 
-    def _owner_table(self, nets, owner):
+    def _owner_table(self, nets, owner, searchers=False):
         """the checked table as uint8[game_cnt][snake_cnt] on the host"""
         n, S = self.game_cnt, self.snake_cnt
         if not 1 <= len(nets) <= MAX_OWNERS:
             raise ValueError(f"{len(nets)} nets: a league match takes 1..{MAX_OWNERS}")
         for net in nets:
             if isinstance(net, Searcher):
-                raise TypeError("a Searcher cannot sit in a league match: it simulates whole games (use Arena.match)")
+                if searchers:
+                    continue
+                raise TypeError("a Searcher cannot sit in League.play: it simulates whole games (use League.play_search)")
             if not hasattr(net, "v_device"):
                 raise TypeError(f"{type(net).__name__} has no v_device(planes, mask): the league evaluates on the device only")
         owner = np.asarray(owner)
@@ -132,6 +150,94 @@ class League:
             planes, mask, _ = eng.observe_all(pairs[:m], want_key=False)
             q = self._values(nets, rows, planes, mask)
             check(L.snk_pit_moves(_ptr(q), _ptr(pairs), m, n, S, _ptr(moves), _stream()))
+            tape = None
+            if spawn_tape is not None:
+                tape = torch.as_tensor(np.ascontiguousarray(spawn_tape(turn), np.int16), device=eng.device)
+                if tape.numel() != n:
+                    raise ValueError(f"spawn_tape({turn}) has {tape.numel()} entries for {n} games")
+            check(L.snk_engine_step_active_tape(eng.h, _ptr(live), n, _ptr(moves), _ptr(tape), _ptr(self._done), None, _stream()))
+            check(L.snk_engine_rewards(eng.h, None, n, _ptr(self._rewards), _stream()))
+            check(L.snk_pit_verdict_owned(eng.h, _ptr(self._done), _ptr(self._rewards), n, _ptr(d_owner), K, turn, _ptr(live),
+                                          _ptr(self._winner), _ptr(self._winner_owner), _ptr(self._length), _stream()))
+        return LeagueResult(self._winner.cpu().numpy(), self._winner_owner.cpu().numpy(), self._length.cpu().numpy(), turn)
+
+    def play_search(self, sides, owner, init_tape=None, spawn_tape=None, counts_log=None):
+        """play with any owner moving by search: sides[o] is a net with v_device or a Searcher around one, in any mix (1..16
+        owners); owner, init_tape and spawn_tape as in play.  The same Searcher object twice is a ValueError: it owns one
+        transposition table, aged once a turn.  counts_log: a list that receives the whole read-back of every turn -- the row
+        counts of the greedy owners in owner order, then the K counts of games per owner (0 for a greedy owner); without a Searcher
+        the K row counts alone, as in play."""
+        eng, n, S = self.engine, self.game_cnt, self.snake_cnt
+        sides = list(sides)
+        K = len(sides)
+        table = self._owner_table(sides, owner, searchers=True)
+        searching = [isinstance(side, Searcher) for side in sides]
+        if len({id(side) for side, s in zip(sides, searching) if s}) != sum(searching):
+            raise ValueError("the same Searcher sits twice: it owns one transposition table, aged once a turn (wrap the net twice)")
+        search_mask = sum(1 << o for o in range(K) if searching[o])
+        greedy = [side for side, s in zip(sides, searching) if not s]
+        Kg = len(greedy)
+        d_owner = torch.as_tensor(table, device=eng.device)
+        d_greedy = None
+        if Kg:                                    # the greedy owners' table: searching owners out of range, the others 0..Kg-1
+            dense = np.full(256, 255, np.uint8)
+            dense[[o for o in range(K) if not searching[o]]] = np.arange(Kg, dtype=np.uint8)
+            d_greedy = torch.as_tensor(dense[table], device=eng.device)
+        if search_mask and self._roots is None:
+            self._roots = (eng.new((n * S,), torch.int32), eng.new((n * S, S), torch.uint8), eng.new((n, S), torch.int32),
+                           eng.new((2 * MAX_OWNERS,), torch.int32))
+        if init_tape is not None:
+            eng.reset(init_tape=init_tape)
+        elif not self._fresh:
+            eng.reset()
+        self._fresh = False
+        self._live.fill_(1)
+        self._winner.fill_(-1)
+        self._winner_owner.fill_(-1)
+        self._length.zero_()
+        L = eng.L
+        live, pairs, moves = self._live, self._pairs, self._moves
+        if search_mask:
+            slots, alive, rank, counts = self._roots
+            counts = counts[:Kg + K]              # {the greedy owners' rows, every owner's games}
+            counts.zero_()
+        else:
+            counts = self._counts[:K]             # no searcher: the turn of play
+        turn = 0
+        while True:
+            if search_mask:
+                check(L.snk_pit_roots_owned(eng.h, _ptr(live), n, _ptr(d_owner), K, search_mask, _ptr(counts[Kg:]), _ptr(slots),
+                                            _ptr(alive), _ptr(rank), _ptr(self._scratch), _stream()))
+            if Kg:
+                check(L.snk_pit_rows_owned(eng.h, _ptr(live), n, _ptr(d_greedy), Kg, _ptr(pairs), _ptr(counts), _ptr(self._scratch),
+                                           _stream()))
+            read = counts.tolist()                # the turn's one read-back
+            if not any(read):
+                break
+            turn += 1
+            if counts_log is not None:
+                counts_log.append(read)
+            if Kg:                                # the greedy owners' nets on their own rows; the array is filled with 1
+                rows = read[:Kg]
+                m, q = sum(rows), None
+                if m:
+                    planes, mask, _ = eng.observe_all(pairs[:m], want_key=False)
+                    q = self._values(greedy, rows, planes, mask)
+                check(L.snk_pit_moves(_ptr(q), _ptr(pairs), m, n, S, _ptr(moves), _stream()))
+            if search_mask:
+                found, lo = [], 0
+                for o in range(K):                # in owner order, each on its own slice of the lists
+                    G = read[Kg + o]
+                    if G == 0:                    # a greedy owner, or a searcher that has left every game (for good)
+                        continue
+                    f = sides[o].search(eng, slots[lo:lo + G], alive[lo:lo + G]).contiguous()
+                    if f.dtype != torch.uint8 or tuple(f.shape) != (G, S):
+                        raise EngineError(f"search returned {f.dtype} {tuple(f.shape)} for {G} games of {S} snakes")
+                    sides[o].end_of_turn()
+                    found.append(f)
+                    lo += G
+                d_found = None if not found else found[0] if len(found) == 1 else torch.cat(found)
+                check(L.snk_pit_search_moves_owned(_ptr(d_found), _ptr(rank), n, S, lo, int(Kg > 0), _ptr(moves), _stream()))
             tape = None
             if spawn_tape is not None:
                 tape = torch.as_tensor(np.ascontiguousarray(spawn_tape(turn), np.int16), device=eng.device)
@@ -234,11 +340,21 @@ def ratings(wins, draws, iterations=200):
     return r - r[0]
 
 
-def round_robin(nets, games=300, seats="duel", height=11, width=11, health_dec=1, seed=None):
-    """every line-up of schedule(len(nets), games, seats) in lock step in one engine -> (LeagueTable, ratings)"""
+def searchers(nets, search, seed=None):
+    """a fresh Searcher around every net (search: Searcher's keyword arguments), as Arena._sides makes them; with a seed net o
+    searches with seed + 101 * (o + 1)"""
+    return [Searcher(net, seed=None if seed is None else seed + 101 * (o + 1), **search) for o, net in enumerate(nets)]
+
+
+def round_robin(nets, games=300, seats="duel", height=11, width=11, health_dec=1, seed=None, search=None):
+    """every line-up of schedule(len(nets), games, seats) in lock step in one engine -> (LeagueTable, ratings)
+    search=dict(breadth=..., depth=...): every net moves by search (a fresh Searcher each, League.play_search)"""
     nets = list(nets)
     owner = schedule(len(nets), games, seats)
     league = League(height, width, SEATS[seats], health_dec, len(owner), seed)
-    result = league.play(nets, owner)
+    if search is None:
+        result = league.play(nets, owner)
+    else:
+        result = league.play_search(searchers(nets, search, seed), owner)
     t = table(result, owner, len(nets))
     return t, ratings(t.wins, t.draws)

@@ -57,7 +57,8 @@ const char *snk_last_error(void);
                              * points: a caller compares it with snk_version().  The arena's entry points (snk_pit_*,
                              * snk_engine_step_active_tape) were added under 113, and so were the searching pit's
                              * (snk_pit_roots, snk_pit_search_moves) and the league's (snk_pit_owned_scratch_elems,
-                             * snk_pit_rows_owned, snk_pit_verdict_owned): no argument list of an older one changed */
+                             * snk_pit_rows_owned, snk_pit_verdict_owned) and the searching league's (snk_pit_roots_owned,
+                             * snk_pit_search_moves_owned): no argument list of an older one changed */
 int snk_version(void);
 
 /* ---- engine lifetime -------------------------------------------------------------------
@@ -546,6 +547,32 @@ int snk_pit_rows_owned(const snk_engine *e, const uint8_t *d_live, int n, const 
 int snk_pit_verdict_owned(const snk_engine *e, const uint8_t *d_done, const int8_t *d_rewards, int n, const uint8_t *d_owner,
                           int n_owners, int turn, uint8_t *d_live, int32_t *d_winner, int32_t *d_winner_owner, int32_t *d_length,
                           void *stream);
+/* Any owner may instead move by search (Agent.make_moves with training=False, agent.py:25-99, behind pit_mp_game_runner.py:23-38):
+ * League.play_search runs each searching owner's DeviceMCTS.search over the open games in which that owner holds a seat and takes
+ * the owner's own seats of the result.  Owner o HOLDS A SEAT in game g when g is open, some snake s of g is alive,
+ * d_owner[g][s] == o and o < n_owners.  A turn is snk_pit_roots_owned, for the greedy owners snk_pit_rows_owned over a second
+ * table (searching owners out of range, greedy owners renumbered densely) / observe / their nets / snk_pit_moves, one read-back
+ * (the greedy row counts and the searching game counts in one copy), the searches in owner order,
+ * snk_pit_search_moves_owned, and the step, rewards and snk_pit_verdict_owned as above.  With n_owners = 2, d_owner[g][s] =
+ * (s >= a_cnt), search_mask = 3 and games in which both teams have a snake (every open game of a match) each owner's list is
+ * what snk_pit_roots writes, d_rank[g][s] is snk_pit_roots' d_rank[g] plus the owner's base on every alive seat, and
+ * snk_pit_search_moves_owned merges what snk_pit_search_moves merges from the two arrays laid one after the other.
+ * snk_pit_roots_owned (agent.py:25-99 behind pit_mp_game_runner.py:23-38): search_mask bit o = owner o searches (bits from
+ *   n_owners up are ignored).  d_counts int32[n_owners]: the open games in which o holds a seat for an owner in the mask, 0 for
+ *   the others; d_slots int32[n*S]: those games, owner 0's list first, then owner 1's, ..., slots ascending inside an owner;
+ *   d_alive uint8[n*S][S]: row r = the alive flags of ALL snakes of slot d_slots[r] (DeviceMCTS.search's root_alive); d_rank
+ *   int32[n][S]: cell [g][s] = the row r at which g stands in the list of d_owner[g][s] when g is open, s alive and that owner in
+ *   the mask, -1 otherwise; every cell with g < n is written, list entries and rows past the sum of the counts are not.
+ *   search_mask == 0 (after the cut to n_owners bits) or n == 0 zeroes d_counts and writes nothing else.  Deterministic (a block
+ *   scan per searching owner, no atomics).  d_scratch: int32[snk_pit_owned_scratch_elems(n, n_owners)].
+ * snk_pit_search_moves_owned (agent.py:25-99 behind pit_mp_game_runner.py:23-38): a thread per cell [g][s] of d_moves
+ *   uint8[n][n_snakes].  d_found uint8[total][n_snakes]: the searchers' root moves concatenated in the order of d_slots (NULL when
+ *   total is 0).  With r = d_rank[g][s]: 0 <= r < total takes d_found[r][s]; any other cell keeps its value when keep_other != 0
+ *   (what snk_pit_moves wrote there) and takes 1 otherwise.  Every cell has one writer.                                       */
+int snk_pit_roots_owned(const snk_engine *e, const uint8_t *d_live, int n, const uint8_t *d_owner, int n_owners, uint32_t search_mask,
+                        int32_t *d_counts, int32_t *d_slots, uint8_t *d_alive, int32_t *d_rank, int32_t *d_scratch, void *stream);
+int snk_pit_search_moves_owned(const uint8_t *d_found, const int32_t *d_rank, int n, int n_snakes, int total, int keep_other,
+                               uint8_t *d_moves, void *stream);
 
 /* ---- training half: AlphaNNet.train = model.fit (alpha_nnet.py:58-59) -------------------------
  * Training-mode batch normalisation of a 128-channel channels-last float32 activation [rows = n * h * w][128] (the

@@ -2,14 +2,17 @@
 ratings of a round robin, 11x11.
 
     python tools/league.py [--nets 6] [--games 300] [--seats duel|1v3|ffa] [--blocks 4] [--models NAME G0 G1 ...] [--seed 1]
-                           [--time] [--pairs 3] [--log profiles/league_ab.log]
+                           [--search B [--depth 8]] [--time] [--pairs 3] [--log profiles/league_ab.log]
 
 --nets K plays generation-0 Glorot nets of --blocks blocks, seeds 1..K; --models NAME G0 G1 ... loads NAME<G>.h5 instead (e.g.
 --models models/gen 0 15 30).  Every line-up of snake_engine.league.schedule plays --games games, all in lock step in one engine.
 --time (duel and 1v3): the league form -- one League.play of all pairings -- against the form the arena offers without it -- one
 Arena.match(net_i, net_j, 1) of --games games per ordered pair, one after another -- alternating inside this one process,
 `--pairs` times; a host clock around a form that ends in a device synchronise.  Seconds per form, turns played, rows evaluated,
-then the medians and their ratio.  The lines are appended to --log behind a line that names the device."""
+then the medians and their ratio.  The lines are appended to --log behind a line that names the device.
+--search B: every seat moves by search (a fresh snake_engine.arena.Searcher of breadth B and --depth around each net per form:
+League.play_search against one Arena.match of two Searchers per ordered pair); the time lines then also give the net evaluations
+of the searches (Searcher.stats) and, since a searching turn is bound by them, the microseconds per evaluation."""
 import argparse
 import os
 import statistics
@@ -41,14 +44,16 @@ def main():
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--models", nargs="+", default=None, metavar="NAME G0 G1 ...")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--search", type=int, default=None, metavar="B")
+    ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--log", default=None)
     a = ap.parse_args()
     import numpy as np
     import torch
-    from snake_engine.arena import Arena
-    from snake_engine.league import SEATS, League, ratings, schedule, table
+    from snake_engine.arena import Arena, Searcher
+    from snake_engine.league import SEATS, League, ratings, schedule, searchers, table
     from snake_engine.net import glorot_uniform_weights
     from utils.alpha_nnet import AlphaNNet
 
@@ -82,57 +87,72 @@ def main():
             Counted.rows += planes.shape[0]
             return self.net.v_device(planes, mask)
 
-    nets = [Counted(net) for net in nets]
+    if not a.search:                                # a searcher talks to its net's range guard directly: no wrapper in between
+        nets = [Counted(net) for net in nets]
     K, S = len(nets), SEATS[a.seats]
     owner = schedule(K, a.games, a.seats)
     prop = torch.cuda.get_device_properties(0)
     say(f"league: 11x11, {a.seats}, {K} nets: {what}, {a.games} games per line-up, {len(owner)} games in all, "
         f"{torch.cuda.get_device_name(0)} ({prop.gcnArchName}, {prop.multi_processor_count} CUs), ROCm / HIP {torch.version.hip}, "
-        f"torch {torch.__version__}")
+        f"torch {torch.__version__}" + (f"; every seat searches, breadth {a.search}, depth {a.depth}" if a.search else ""))
+    search = dict(breadth=a.search, depth=a.depth) if a.search else None
 
     def league_form(seed):
-        """one League.play of every line-up -> (result, seconds, rows evaluated)"""
+        """one League.play (play_search) of every line-up -> (result, seconds, rows evaluated, the searches' net evaluations)"""
         Counted.rows = 0
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        res = League(11, 11, S, 1, len(owner), seed).play(nets, owner)      # both forms pay for their engines inside the clock
+        league = League(11, 11, S, 1, len(owner), seed)                     # both forms pay for their engines inside the clock
+        sides = searchers(nets, search, seed) if search else nets           # ... and for their searchers' tables
+        res = league.play_search(sides, owner) if search else league.play(nets, owner)
         torch.cuda.synchronize()
-        return res, time.perf_counter() - t0, Counted.rows
+        return res, time.perf_counter() - t0, Counted.rows, sum(s.stats["net_evals"] for s in sides) if search else 0
 
     def arena_form(seed):
-        """one Arena.match per ordered pair, one after another -> (winner owners in schedule order, seconds, turns, rows)"""
-        wo, turns, Counted.rows = [], 0, 0
+        """one Arena.match per ordered pair, one after another -> (winner owners in schedule order, seconds, turns, rows, the
+        searches' net evaluations)"""
+        wo, turns, evals, Counted.rows = [], 0, 0, 0
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(K):
             for j in range(K):
                 if i != j:
-                    r = Arena(11, 11, S, 1, a.games, seed + 31 * (i * K + j)).match(nets[i], nets[j], 1)
+                    sd = seed + 31 * (i * K + j)
+                    sides = [Searcher(net, seed=sd + 101 * (k + 1), **search) for k, net in enumerate((nets[i], nets[j]))] if search \
+                        else (nets[i], nets[j])
+                    r = Arena(11, 11, S, 1, a.games, sd).match(sides[0], sides[1], 1)
+                    evals += sum(s.stats["net_evals"] for s in sides) if search else 0
                     wo.append(np.where(r.winners < 0, -1, np.where(r.winners < 1, i, j)))
                     turns += r.turns
         torch.cuda.synchronize()
-        return np.concatenate(wo), time.perf_counter() - t0, turns, Counted.rows
+        return np.concatenate(wo), time.perf_counter() - t0, turns, Counted.rows, evals
 
     Arena(11, 11, S, 1, 64, 99).match(nets[0], nets[-1], 1)    # first launches, plans and range-guard scales settle outside the timing
-    League(11, 11, S, 1, len(owner), 99).play(nets, owner)
+    if search:                                                 # ... and the search's, on a small match of each form
+        warm = schedule(K, 2, a.seats)
+        Arena(11, 11, S, 1, 8, 99).match(Searcher(nets[0], seed=1, **search), Searcher(nets[-1], seed=2, **search), 1)
+        League(11, 11, S, 1, len(warm), 99).play_search(searchers(nets, search, 99), warm)
+    else:
+        League(11, 11, S, 1, len(owner), 99).play(nets, owner)
     if a.time:
         if a.seats == "ffa":
             raise SystemExit("--time compares with Arena.match, which has no free-for-all")
         per = {"league": [], "arena": []}
+        evals_text = lambda evals, dt: f", {evals} net evaluations by the searches, {dt / evals * 1e6:.2f} us each" if evals else ""
         for k in range(a.pairs):
-            res, dt, rows = league_form(a.seed)
+            res, dt, rows, evals = league_form(a.seed)
             per["league"].append(dt)
             say(f"time: pair {k} league form: 1 match of {len(owner)} games, {res.turns} turns, {rows} rows evaluated, "
-                f"{dt:8.3f} s, {dt / res.turns * 1e3:.3f} ms per turn")
-            wo, dt, turns, rows = arena_form(a.seed)
+                f"{dt:8.3f} s, {dt / res.turns * 1e3:.3f} ms per turn" + evals_text(evals, dt))
+            wo, dt, turns, rows, evals = arena_form(a.seed)
             per["arena"].append(dt)
             say(f"time: pair {k} arena form: {K * (K - 1)} matches of {a.games} games, {turns} turns, {rows} rows evaluated, "
-                f"{dt:8.3f} s, {dt / turns * 1e3:.3f} ms per turn")
+                f"{dt:8.3f} s, {dt / turns * 1e3:.3f} ms per turn" + evals_text(evals, dt))
         ml, ma = statistics.median(per["league"]), statistics.median(per["arena"])
         say(f"time: median seconds: league form {ml:.3f} (min {min(per['league']):.3f}, max {max(per['league']):.3f}), arena form "
             f"{ma:.3f} (min {min(per['arena']):.3f}, max {max(per['arena']):.3f}), ratio of medians arena / league {ma / ml:.2f}x")
         return
-    res, dt, _ = league_form(a.seed)
+    res, dt, _, _ = league_form(a.seed)
     t = table(res, owner, K)
     say(f"{res.turns} turns, {dt:.3f} s, {dt / res.turns * 1e3:.3f} ms per turn; wins of the row's net over the column's / draws")
     for line in format_table(names, t, ratings(t.wins, t.draws)):

@@ -9,7 +9,8 @@ and its two-snake duel): generation N against generation 0 and against generatio
 (snake_engine.arena.Searcher, depth as in training, the given breadth).
 
 --league M adds one league match (snake_engine.league.round_robin, duels, the first game count) among M generations spread
-evenly from 0 to N: the cross table, the scores and the Bradley-Terry ratings, beside the pit lines.
+evenly from 0 to N: the cross table, the scores and the Bradley-Terry ratings, beside the pit lines.  Together with
+--search BREADTH the same round robin is played once more with every seat moving by search (League.play_search).
 
 Writes <out>/learning_log.csv (the trainer's log.csv) and <out>/learning_run.log: seconds per generation, the range-guard
 widenings of self-play, the fit's mode, and the pit lines in the reference's wording with a 95 % Wilson interval on every
@@ -133,12 +134,14 @@ def main():
             M = max(2, min(a.league, N + 1, 16))
             gens = sorted({round(i * N / (M - 1)) for i in range(M)})
             games = a.games[0] if a.games else 300
-            t1 = time.time()
-            t, r = round_robin([load(g) for g in gens], games=games, seats="duel", height=h, width=w, seed=2000 + games)
-            say(f"[league, {games} games per ordered pair, duels] generations {gens}: wins of the row's net over the column's / draws, "
-                f"score, rating (generation {gens[0]} = 0); {time.time() - t1:.1f} s")
-            for line in format_table([f"gen{g}" for g in gens], t, r):
-                say(line)
+            judges = [("", None)] + ([(f", search breadth {a.search}", dict(breadth=a.search, depth=s["max_MCTS_depth"]))] if a.search else [])
+            for tag, search in judges:
+                t1 = time.time()
+                t, r = round_robin([load(g) for g in gens], games=games, seats="duel", height=h, width=w, seed=2000 + games, search=search)
+                say(f"[league, {games} games per ordered pair, duels{tag}] generations {gens}: wins of the row's net over the column's / "
+                    f"draws, score, rating (generation {gens[0]} = 0); {time.time() - t1:.1f} s")
+                for line in format_table([f"gen{g}" for g in gens], t, r):
+                    say(line)
     finally:
         os.chdir(here)
         shutil.rmtree(work, ignore_errors=True)
