@@ -1431,6 +1431,158 @@ __global__ __launch_bounds__(CMP_THREADS) void k_lgs_scatter(const uint8_t *__re
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// the scripted opponent of the pit (snake_engine.arena.Scripted): the three move scores of every row of a row list, from the
+// compact records alone -- no observation, no net.  The policy is the project's own (the reference has no scripted snake); it is
+// stated in include/snake_engine.h and, in plain Python, in tests/script_ref.py.
+// A quad of lanes per row, sixteen rows per wavefront.  All four lanes build the occupancy bit plane of the row's game (lane k
+// walks the rings of snakes k and k + 4) and OR it across the quad with two DPP quad_perm moves per half word; lanes 0..2 then
+// each score one move, the flood fill as whole-plane shifts of a reach mask.  The plane is FW 64-bit words in registers (FW = 1:
+// up to 64 cells, 2: up to 128, 6: up to 361), every loop over them unrolled, so no array is indexed by a run-time value.
+// Every loop is bounded whatever the record holds: a ring walk by min(len, cap), the fill by NC rounds, the food scan by the
+// bits of a word; a cell index is compared with NC before it sets a bit.  The DPP moves are the only cross-lane operations and
+// no lane has left when they run: a row without a snake (a dead or out-of-range pair, a row past m) walks nothing, takes part
+// with an empty plane and writes its three -1 (past m: nothing) at the end.
+// ------------------------------------------------------------------------------------------
+struct ScriptMasks {
+    uint64_t valid[6];      // bit c = c < NC
+    uint64_t not_c0[6];     // bit c = c < NC and c % W != 0: a cell that has a left neighbour
+    uint64_t not_cl[6];     // bit c = c < NC and c % W != W - 1: a cell that has a right neighbour
+};
+
+__device__ static inline int script_ring_cell(const uint8_t *rec, const Layout &L, int s, int idx)
+{
+    const uint8_t *r = rec + (size_t)s * L.ring_bytes;
+    idx &= L.cap_mask;
+    return L.cell_bytes == 1 ? (int)r[idx] : (int)((const uint16_t *)r)[idx];
+}
+
+template <int FW>
+__global__ __launch_bounds__(BLOCK_THREADS) void k_pit_script(const uint8_t *__restrict__ state, Layout L, int n_slots,
+                                                             const int32_t *__restrict__ pairs, int m, uint32_t flags,
+                                                             ScriptMasks K, float *__restrict__ q)
+{
+    const int t = blockIdx.x * BLOCK_THREADS + threadIdx.x;
+    const int row = t >> 2, k = t & 3;
+    const bool in = row < m;
+    int g = -1, s = -1;
+    if (in) { g = pairs[2 * (size_t)row]; s = pairs[2 * (size_t)row + 1]; }
+    const bool pair_ok = in && g >= 0 && g < n_slots && s >= 0 && s < L.S;
+    const uint8_t *rec = state + (size_t)(pair_ok ? g : 0) * L.stride;
+    const SnakeMeta *meta = (const SnakeMeta *)(rec + L.meta_off);
+    SnakeMeta me = {0, 0, 0, 0, 0};
+    if (pair_ok) me = meta[s];
+    const bool ok = pair_ok && me.alive;
+
+    // ---- occupied: every ring cell of every alive snake, tails and the row's own body included
+    uint64_t occ[FW];
+#pragma unroll
+    for (int w = 0; w < FW; ++w) occ[w] = 0ull;
+    if (ok) {
+        for (int o = k; o < L.S; o += 4) {
+            const SnakeMeta mo = meta[o];
+            if (!mo.alive) continue;
+            const int len = (int)mo.len < L.cap ? (int)mo.len : L.cap;
+            for (int i = 0; i < len; ++i) {
+                const int c = script_ring_cell(rec, L, o, mo.tail + i);
+                if (c < L.NC) {
+#pragma unroll
+                    for (int w = 0; w < FW; ++w) occ[w] |= (c >> 6) == w ? 1ull << (c & 63) : 0ull;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int w = 0; w < FW; ++w) {                    // all 64 lanes are here: the quad's four partial planes become one
+        int lo = (int)(uint32_t)occ[w], hi = (int)(uint32_t)(occ[w] >> 32);
+        lo |= __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xF, 0xF, true);      // quad_perm [1,0,3,2]
+        hi |= __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xF, 0xF, true);
+        lo |= __builtin_amdgcn_update_dpp(0, lo, 0x4E, 0xF, 0xF, true);      // quad_perm [2,3,0,1]
+        hi |= __builtin_amdgcn_update_dpp(0, hi, 0x4E, 0xF, 0xF, true);
+        occ[w] = ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
+    }
+
+    // ---- lane k < 3 scores relative move k
+    int score = -1;
+    if (ok && k < 3) {
+        const int HH = L.H, WW = L.W;
+        const int len_s = me.len;
+        const int hc = script_ring_cell(rec, L, s, me.tail + len_s - 1);
+        const int d = (k + me.dir + 3) & 3;                   // k_step's heading: 0 = y-1, 1 = x+1, 2 = y+1, 3 = x-1
+        int y = hc / WW, x = hc - y * WW;
+        y += (d == 2) - (d == 0);
+        x += (d == 1) - (d == 3);
+        const bool oob = (y < 0) | (y >= HH) | (x < 0) | (x >= WW);
+        const int tc = oob ? 0 : y * WW + x;
+        bool blocked = oob;
+#pragma unroll
+        for (int w = 0; w < FW; ++w) blocked |= (tc >> 6) == w && ((occ[w] >> (tc & 63)) & 1ull);
+        if (!blocked) {
+            int space = 0;
+            if (flags & SNK_SCRIPT_SPACE) {
+                uint64_t fr[FW], r[FW];
+#pragma unroll
+                for (int w = 0; w < FW; ++w) {
+                    fr[w] = ~occ[w] & K.valid[w];
+                    r[w] = (tc >> 6) == w ? 1ull << (tc & 63) : 0ull;
+                }
+                for (int round = 0; round < L.NC; ++round) {  // a round that changes the mask adds a cell: at most NC - 1 of them
+                    uint64_t nx[FW];
+                    bool changed = false;
+#pragma unroll
+                    for (int w = 0; w < FW; ++w) {
+                        const uint64_t below = w > 0 ? r[w > 0 ? w - 1 : 0] : 0ull, above = w < FW - 1 ? r[w < FW - 1 ? w + 1 : 0] : 0ull;
+                        const uint64_t from_up = (r[w] << WW) | (below >> (64 - WW));         // cell c takes cell c - W
+                        const uint64_t from_dn = (r[w] >> WW) | (above << (64 - WW));         // cell c takes cell c + W
+                        const uint64_t from_lf = ((r[w] << 1) | (below >> 63)) & K.not_c0[w]; // cell c takes cell c - 1, not across a row end
+                        const uint64_t from_rt = ((r[w] >> 1) | (above << 63)) & K.not_cl[w]; // cell c takes cell c + 1
+                        nx[w] = (r[w] | from_up | from_dn | from_lf | from_rt) & fr[w];
+                        changed |= nx[w] != r[w];
+                    }
+#pragma unroll
+                    for (int w = 0; w < FW; ++w) r[w] = nx[w];
+                    if (!changed) break;
+                }
+#pragma unroll
+                for (int w = 0; w < FW; ++w) space += __popcll(r[w]);
+            }
+            int safe = 1;
+            if (flags & SNK_SCRIPT_HEADS) {
+                for (int o = 0; o < L.S; ++o) {
+                    if (o == s) continue;
+                    const SnakeMeta mo = meta[o];
+                    if (!mo.alive || (int)mo.len < len_s) continue;
+                    const int ho = script_ring_cell(rec, L, o, mo.tail + mo.len - 1);
+                    const int oy = ho / WW, ox = ho - oy * WW;
+                    if (abs(oy - y) + abs(ox - x) == 1) safe = 0;
+                }
+            }
+            int food = 0;
+            if (flags & SNK_SCRIPT_FOOD) {
+                const uint64_t *fw = (const uint64_t *)(rec + L.food_off);
+                int best = 1 << 20;
+#pragma unroll
+                for (int w = 0; w < FW; ++w) {
+                    uint64_t f = fw[w < L.FW ? w : 0] & K.valid[w];          // valid[] is 0 from the layout's word count up
+                    while (f) {                                              // one set bit less per pass: at most 64
+                        const int c = w * 64 + __builtin_ctzll(f);
+                        f &= f - 1ull;
+                        const int fy = c / WW, fx = c - fy * WW;
+                        const int dist = abs(fy - y) + abs(fx - x);
+                        best = dist < best ? dist : best;
+                    }
+                }
+                if (best != (1 << 20)) food = HH + WW - best;
+            }
+            int room = space < len_s ? space : len_s;
+            room = room < 255 ? room : 255;
+            const int fill = space < 511 ? space : 511;
+            score = ((room * 2 + safe) * 64 + food) * 512 + fill;
+        }
+    }
+    if (in && k < 3) q[3 * (size_t)row + k] = (float)score;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 // square boards of 5x5 (the eight standard start cells are distinct from there on, game.py:25-29) to 19x19 (SNK_MAX_CELLS);
 // the reference's observation is a rot90 of a (2H-1)x(2W-1) canvas, so only square boards batch (game.py:257)
@@ -1717,6 +1869,33 @@ extern "C" int snk_pit_roots_owned(const snk_engine *e, const uint8_t *d_live, i
     k_lg_scan<<<1, CMP_THREADS, 0, st>>>(d_scratch, tiles, n_owners, d_counts);
     k_lgs_scatter<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, e->L, d_live, n, d_owner, n_owners, search_mask, d_scratch, d_counts, d_slots,
                                                  d_alive, d_rank);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_script_values(const snk_engine *e, const int32_t *d_pairs, int m, uint32_t flags, float *d_q, void *stream)
+{
+    SNK_REQUIRE(e != nullptr, "snk_pit_script_values: engine is NULL");
+    SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
+                "snk_pit_script_values: unknown flag bits in 0x%x", flags);
+    SNK_REQUIRE(m >= 0, "snk_pit_script_values: m=%d", m);
+    if (m == 0) return 0;
+    SNK_REQUIRE(d_pairs && d_q, "snk_pit_script_values: NULL argument");
+    const Layout L = e->L;
+    ScriptMasks K;
+    memset(&K, 0, sizeof(K));
+    for (int c = 0; c < L.NC; ++c) {
+        const uint64_t bit = 1ull << (c & 63);
+        K.valid[c >> 6] |= bit;
+        if (c % L.W != 0) K.not_c0[c >> 6] |= bit;
+        if (c % L.W != L.W - 1) K.not_cl[c >> 6] |= bit;
+    }
+    const int grid = (m + BLOCK_THREADS / 4 - 1) / (BLOCK_THREADS / 4);      // a quad per row
+#define SCRIPT_ARGS e->d_state, L, e->n_slots, d_pairs, m, flags, K, d_q
+    if (L.FW == 1) k_pit_script<1><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
+    else if (L.FW == 2) k_pit_script<2><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
+    else k_pit_script<6><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
+#undef SCRIPT_ARGS
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -32,6 +32,14 @@ The arena's own read-back stays one per turn.  The search reads back on its own,
 depth once per turn, the number of new keys once per rollout tick (it sizes the net batch), the table status after every epoch but
 the last and at the end of the turn together with the turn's sub-game tick counter; a taped (parity) search also reads its row
 counts.  A guarded net is calibrated once, on the first turn's root observations.
+
+Either side may also be a ``Scripted``: the flood-fill heuristic snake every Battlesnake project keeps as its fixed point (the
+project's own policy -- the reference has none; include/snake_engine.h states it, tests/script_ref.py restates it in plain
+Python).  It costs no weights and is the same opponent in every run.  Its rows are scored from the compact game records by
+snk_pit_script_values, and snk_pit_moves turns the scores into moves as it does a net's values; the observe launch and the net
+then run over the other side's rows only (the row list is team A first, so both are contiguous slices), and ``Scripted`` against
+``Scripted`` launches neither.  The turn's read-back stays the one it is.  A match without a ``Scripted`` issues exactly the
+launches it issued before there was one.
 """
 from collections import namedtuple
 
@@ -108,6 +116,59 @@ class Searcher:
         return dict(net_evals=0, rollout_ticks=0, sim_steps=0, lookups=0) if self.mcts is None else self.mcts.stats
 
 
+SCRIPT_SPACE, SCRIPT_HEADS, SCRIPT_FOOD = 1, 2, 4          # SNK_SCRIPT_* of include/snake_engine.h
+
+
+class Scripted:
+    """A side of a pit match (or an owner of a league match) that moves by the scripted policy of include/snake_engine.h: avoid
+    walls and bodies, do not enter a pocket smaller than yourself, step away from the head of a snake at least as long, go for
+    food.  flags switch the parts (SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD; 0 = any unblocked move), so one class gives several
+    fixed yardsticks.  It has no net and no v_device: a Searcher around it is a TypeError."""
+
+    def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD):
+        flags = int(flags)
+        if flags & ~(SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD):
+            raise ValueError(f"Scripted flags {flags:#x}: bits outside SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD")
+        self.flags = flags
+
+    def q_rows(self, engine, pairs):
+        """pairs int32[rows][2] (slot, snake id) on the device -> the three move scores float32[rows][3] on the device"""
+        m = int(pairs.shape[0])
+        q = engine.new((m, 3), torch.float32)
+        check(engine.L.snk_pit_script_values(engine.h, _ptr(pairs), m, self.flags, _ptr(q), _stream()))
+        return q
+
+
+def mixed_values(eng, sides, rows, pairs):
+    """the values float32[sum(rows)][3] of a row list in which side o moves the next rows[o] rows and some side is Scripted: a
+    Scripted side's slice is scored by the kernel; every run of consecutive nets shares one observe launch over its rows only"""
+    parts, lo, o, K = [], 0, 0, len(sides)
+    while o < K:
+        if isinstance(sides[o], Scripted):
+            if rows[o]:
+                parts.append(sides[o].q_rows(eng, pairs[lo:lo + rows[o]]))
+            lo += rows[o]
+            o += 1
+            continue
+        end = o
+        while end < K and not isinstance(sides[end], Scripted):
+            end += 1
+        cnt = sum(rows[o:end])
+        if cnt:
+            planes, mask, _ = eng.observe_all(pairs[lo:lo + cnt], want_key=False)
+            at = 0
+            for net, c in zip(sides[o:end], rows[o:end]):
+                if c:
+                    parts.append(net.v_device(planes[at:at + c], mask[at:at + c]))
+                    at += c
+        lo += cnt
+        o = end
+    q = parts[0] if len(parts) == 1 else torch.cat(parts)
+    if q.dtype != torch.float32 or tuple(q.shape) != (lo, 3) or not q.is_cuda:
+        raise EngineError(f"v_device returned {q.dtype} {tuple(q.shape)} on {q.device} for {lo} rows: float32 [rows][3] on the device expected")
+    return q.contiguous()
+
+
 class Arena:
 
     def __init__(self, height=11, width=11, snake_cnt=4, health_dec=1, game_cnt=1, seed=None):
@@ -149,7 +210,7 @@ class Arena:
     # ---- one match -------------------------------------------------------------------------------------------------------
     def match(self, alice, bob, alice_snake_cnt=None, init_tape=None, spawn_tape=None):
         """alice, bob: anything with v_device(planes, mask) -> float32[rows][3] on the device (AlphaNNet: its guarded forward),
-        or a Searcher around one; every combination is allowed.  With a Searcher the turn is the second one of the module's
+        a Searcher around one, or a Scripted; every combination is allowed.  With a Searcher the turn is the second one of the module's
         docstring: the arena still reads back once per turn (G and the two row counts), the searches read back on their own.
         alice_snake_cnt: snakes 0 .. alice_snake_cnt-1 are alice's (default snake_cnt // 2, pit_mp_game_runner.py:17-18).
         init_tape: uint8[game_cnt][3][snake_cnt] recorded start draws (snk_engine_reset); without one the match plays on the
@@ -162,7 +223,7 @@ class Arena:
         if not 0 <= a_cnt <= S:
             raise ValueError(f"alice_snake_cnt {a_cnt} outside 0..{S}")
         for net in (alice, bob):
-            if not isinstance(net, Searcher) and not hasattr(net, "v_device"):
+            if not isinstance(net, (Searcher, Scripted)) and not hasattr(net, "v_device"):
                 raise TypeError(f"{type(net).__name__} has no v_device(planes, mask): the arena evaluates on the device only")
         if init_tape is not None:
             eng.reset(init_tape=init_tape)
@@ -183,10 +244,11 @@ class Arena:
         return ArenaResult(winners, lengths, turn, wins_a, wins_b, n - wins_a - wins_b)
 
     def _greedy_turns(self, alice, bob, a_cnt, spawn_tape):
-        """the turns of a match between two nets -> turns played"""
+        """the turns of a match between two nets (either may be a Scripted) -> turns played"""
         eng, n, S = self.engine, self.game_cnt, self.snake_cnt
         L = eng.L
         live, pairs, counts, moves = self._live, self._pairs, self._counts, self._moves
+        scripted = isinstance(alice, Scripted) or isinstance(bob, Scripted)
         turn = 0
         while True:
             check(L.snk_pit_rows(eng.h, _ptr(live), n, a_cnt, _ptr(pairs), _ptr(counts), _ptr(self._scratch), _stream()))
@@ -195,8 +257,11 @@ class Arena:
             if m == 0:
                 break
             turn += 1
-            planes, mask, _ = eng.observe_all(pairs[:m], want_key=False)
-            q = self._values(alice, bob, planes, mask, nA, m)
+            if scripted:                          # the kernel scores the scripted rows; observe and net on the other side's only
+                q = mixed_values(eng, (alice, bob), (nA, nB), pairs)
+            else:
+                planes, mask, _ = eng.observe_all(pairs[:m], want_key=False)
+                q = self._values(alice, bob, planes, mask, nA, m)
             check(L.snk_pit_moves(_ptr(q), _ptr(pairs), m, n, S, _ptr(moves), _stream()))
             self._tick(turn, a_cnt, spawn_tape)
         return turn
@@ -239,7 +304,9 @@ class Arena:
             if any(greedy):                       # the greedy side's net on its own rows; the array is filled with 1
                 lo, hi, net = (0, nA, alice) if greedy[0] else (nA, nA + nB, bob)
                 q = None
-                if hi > lo:
+                if hi > lo and isinstance(net, Scripted):
+                    q = net.q_rows(eng, pairs[lo:hi])
+                elif hi > lo:
                     planes, mask, _ = eng.observe_all(pairs[lo:hi], want_key=False)
                     q = self._values(net, net, planes, mask, hi - lo, hi - lo)
                 check(L.snk_pit_moves(_ptr(q), _ptr(pairs[lo:hi]), hi - lo, n, S, _ptr(moves), _stream()))
@@ -271,11 +338,12 @@ class Arena:
     # ---- the reference's two judges ------------------------------------------------------------------------------------------
     @staticmethod
     def _sides(alice, bob, search, seed):
-        """the two sides of one match: the nets themselves, or fresh Searchers around them (search: Searcher's keyword arguments)"""
+        """the two sides of one match: the nets themselves, or fresh Searchers around them (search: Searcher's keyword arguments);
+        a Scripted stays as it is either way"""
         if search is None:
             return alice, bob
         seeds = [None, None] if seed is None else [seed + 101, seed + 202]
-        return tuple(Searcher(net, seed=sd, **search) for net, sd in zip((alice, bob), seeds))
+        return tuple(net if isinstance(net, Scripted) else Searcher(net, seed=sd, **search) for net, sd in zip((alice, bob), seeds))
 
     @staticmethod
     def test_pit(alice, bob, games=300, height=11, width=11, health_dec=1, seed=None, search=None):

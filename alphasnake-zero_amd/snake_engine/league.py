@@ -32,6 +32,11 @@ whose seat is the owner's -- and only its own seats take the moves it finds.  A 
 
 With two Searchers and the two-team table this is ``Arena.match`` with the same Searchers, and with no Searcher it is ``play``.
 The league's own read-back stays one per turn; the searches read back on their own (snake_engine/arena.py).
+
+An owner of either may be an ``arena.Scripted`` (the fixed yardstick of a table: the same opponent in every run): it counts as a
+greedy owner, its slice of the row list is scored by snk_pit_script_values, and the observe launch and the nets run over the
+other owners' rows only -- one observe per run of consecutive net owners.  A match without a ``Scripted`` issues exactly the
+launches it issued before there was one.
 """
 from collections import namedtuple
 
@@ -39,7 +44,7 @@ import numpy as np
 import torch
 
 from ._lib import check, EngineError
-from .arena import Searcher
+from .arena import Scripted, Searcher, mixed_values
 from .engine import Engine, _ptr, _stream
 
 MAX_OWNERS = 16          # SNK_PIT_MAX_OWNERS of include/snake_engine.h
@@ -100,6 +105,8 @@ class League:
         if not 1 <= len(nets) <= MAX_OWNERS:
             raise ValueError(f"{len(nets)} nets: a league match takes 1..{MAX_OWNERS}")
         for net in nets:
+            if isinstance(net, Scripted):
+                continue
             if isinstance(net, Searcher):
                 if searchers:
                     continue
@@ -115,7 +122,7 @@ class League:
 
     # ---- one match -------------------------------------------------------------------------------------------------------
     def play(self, nets, owner, init_tape=None, spawn_tape=None, counts_log=None):
-        """nets: 1..16 objects with v_device(planes, mask) -> float32[rows][3] on the device; owner: integer array
+        """nets: 1..16 objects with v_device(planes, mask) -> float32[rows][3] on the device (or Scripted); owner: integer array
         [game_cnt][snake_cnt] on the host, owner[g][s] = the index in nets of the net that moves snake s of game g.
         init_tape / spawn_tape: as in Arena.match (recorded start draws; callable turn -> int16[game_cnt] recorded food spawns,
         for parity runs only).  counts_log: a list that receives the K row counts of every turn (what the turn's read-back
@@ -136,6 +143,7 @@ class League:
         L = eng.L
         live, pairs, moves = self._live, self._pairs, self._moves
         counts = self._counts[:K]
+        scripted = any(isinstance(net, Scripted) for net in nets)
         turn = 0
         while True:
             check(L.snk_pit_rows_owned(eng.h, _ptr(live), n, _ptr(d_owner), K, _ptr(pairs), _ptr(counts), _ptr(self._scratch),
@@ -147,8 +155,11 @@ class League:
             turn += 1
             if counts_log is not None:
                 counts_log.append(rows)
-            planes, mask, _ = eng.observe_all(pairs[:m], want_key=False)
-            q = self._values(nets, rows, planes, mask)
+            if scripted:                          # the kernel scores the scripted rows; observe and nets on the others' only
+                q = mixed_values(eng, nets, rows, pairs)
+            else:
+                planes, mask, _ = eng.observe_all(pairs[:m], want_key=False)
+                q = self._values(nets, rows, planes, mask)
             check(L.snk_pit_moves(_ptr(q), _ptr(pairs), m, n, S, _ptr(moves), _stream()))
             tape = None
             if spawn_tape is not None:
@@ -162,8 +173,8 @@ class League:
         return LeagueResult(self._winner.cpu().numpy(), self._winner_owner.cpu().numpy(), self._length.cpu().numpy(), turn)
 
     def play_search(self, sides, owner, init_tape=None, spawn_tape=None, counts_log=None):
-        """play with any owner moving by search: sides[o] is a net with v_device or a Searcher around one, in any mix (1..16
-        owners); owner, init_tape and spawn_tape as in play.  The same Searcher object twice is a ValueError: it owns one
+        """play with any owner moving by search: sides[o] is a net with v_device, a Scripted or a Searcher around a net, in any
+        mix (1..16 owners); owner, init_tape and spawn_tape as in play.  The same Searcher object twice is a ValueError: it owns one
         transposition table, aged once a turn.  counts_log: a list that receives the whole read-back of every turn -- the row
         counts of the greedy owners in owner order, then the K counts of games per owner (0 for a greedy owner); without a Searcher
         the K row counts alone, as in play."""
@@ -177,6 +188,7 @@ class League:
         search_mask = sum(1 << o for o in range(K) if searching[o])
         greedy = [side for side, s in zip(sides, searching) if not s]
         Kg = len(greedy)
+        scripted = any(isinstance(side, Scripted) for side in greedy)
         d_owner = torch.as_tensor(table, device=eng.device)
         d_greedy = None
         if Kg:                                    # the greedy owners' table: searching owners out of range, the others 0..Kg-1
@@ -220,7 +232,9 @@ class League:
             if Kg:                                # the greedy owners' nets on their own rows; the array is filled with 1
                 rows = read[:Kg]
                 m, q = sum(rows), None
-                if m:
+                if m and scripted:
+                    q = mixed_values(eng, greedy, rows, pairs)
+                elif m:
                     planes, mask, _ = eng.observe_all(pairs[:m], want_key=False)
                     q = self._values(greedy, rows, planes, mask)
                 check(L.snk_pit_moves(_ptr(q), _ptr(pairs), m, n, S, _ptr(moves), _stream()))
@@ -342,13 +356,15 @@ def ratings(wins, draws, iterations=200):
 
 def searchers(nets, search, seed=None):
     """a fresh Searcher around every net (search: Searcher's keyword arguments), as Arena._sides makes them; with a seed net o
-    searches with seed + 101 * (o + 1)"""
-    return [Searcher(net, seed=None if seed is None else seed + 101 * (o + 1), **search) for o, net in enumerate(nets)]
+    searches with seed + 101 * (o + 1).  A Scripted stays as it is."""
+    return [net if isinstance(net, Scripted) else Searcher(net, seed=None if seed is None else seed + 101 * (o + 1), **search)
+            for o, net in enumerate(nets)]
 
 
 def round_robin(nets, games=300, seats="duel", height=11, width=11, health_dec=1, seed=None, search=None):
     """every line-up of schedule(len(nets), games, seats) in lock step in one engine -> (LeagueTable, ratings)
-    search=dict(breadth=..., depth=...): every net moves by search (a fresh Searcher each, League.play_search)"""
+    search=dict(breadth=..., depth=...): every net moves by search (a fresh Searcher each, League.play_search).
+    Any entry of nets may be a Scripted: it moves by its script with or without search="""
     nets = list(nets)
     owner = schedule(len(nets), games, seats)
     league = League(height, width, SEATS[seats], health_dec, len(owner), seed)

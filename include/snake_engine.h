@@ -58,7 +58,8 @@ const char *snk_last_error(void);
                              * snk_engine_step_active_tape) were added under 113, and so were the searching pit's
                              * (snk_pit_roots, snk_pit_search_moves) and the league's (snk_pit_owned_scratch_elems,
                              * snk_pit_rows_owned, snk_pit_verdict_owned) and the searching league's (snk_pit_roots_owned,
-                             * snk_pit_search_moves_owned): no argument list of an older one changed */
+                             * snk_pit_search_moves_owned) and the scripted opponent's (snk_pit_script_values): no argument list
+                             * of an older one changed */
 int snk_version(void);
 
 /* ---- engine lifetime -------------------------------------------------------------------
@@ -573,6 +574,31 @@ int snk_pit_roots_owned(const snk_engine *e, const uint8_t *d_live, int n, const
                         int32_t *d_counts, int32_t *d_slots, uint8_t *d_alive, int32_t *d_rank, int32_t *d_scratch, void *stream);
 int snk_pit_search_moves_owned(const uint8_t *d_found, const int32_t *d_rank, int n, int n_snakes, int total, int keep_other,
                                uint8_t *d_moves, void *stream);
+
+/* ---- the scripted opponent: a fixed yardstick for the pit (no reference lines: the reference has no scripted snake, and no
+ *      heuristic agent of any kind; the policy below is this project's own) ----------------------------------------------------
+ * A seat of Arena.match / League.play / League.play_search may belong to snake_engine.arena.Scripted instead of a net: its rows
+ * of the row list (snk_pit_rows, snk_pit_rows_owned) are scored by this kernel from the compact records -- no observation, no
+ * net -- and snk_pit_moves turns the scores into moves as it does a net's values, so its tie order (strict comparisons: of equal
+ * best scores the later move wins, all equal gives 2) is part of the policy.  Integers only, so it is pinned exactly
+ * (tests/script_ref.py is the statement in plain Python).  For row (slot g, snake s), s alive, and relative move a = 0, 1, 2:
+ *   target    the head cell moved by d = (a + dir + 3) & 3, 0 = y-1, 1 = x+1, 2 = y+1, 3 = x-1 (what snk_engine_step does)
+ *   occupied  ring cells 0 .. len-1 of every ALIVE snake of the game, tails and s's own body included; dead snakes occupy nothing
+ *   blocked   the target is off the board or occupied: the score is -1
+ *   space     cells reachable from the target by 4-neighbour steps over on-board, unoccupied cells, the target included
+ *   room      min(space, len_s, 255)
+ *   safe      0 when another alive snake t with len_t >= len_s has its head at Manhattan distance 1 from the target, else 1
+ *   food      H + W - (the smallest Manhattan distance from the target to a food cell); 0 without food on the board
+ *   fill      min(space, 511)
+ *   score     ((room * 2 + safe) * 64 + food) * 512 + fill, below 2^24 and therefore exact as float32
+ * flags switch the parts: without SNK_SCRIPT_SPACE room = fill = 0 (no fill is run), without SNK_SCRIPT_HEADS safe = 1, without
+ * SNK_SCRIPT_FOOD food = 0; flags = 0 is "any unblocked move".  A bit outside the three is an error.
+ * d_pairs int32[m][2] as snk_pit_rows writes it; d_q float32[m][3], nothing past row m is written; m == 0 is a no-op.  A pair
+ * that names a dead snake, or a slot outside 0..n_slots-1 or a snake id outside 0..S-1, gets -1, -1, -1.                       */
+#define SNK_SCRIPT_SPACE 1u
+#define SNK_SCRIPT_HEADS 2u
+#define SNK_SCRIPT_FOOD 4u
+int snk_pit_script_values(const snk_engine *e, const int32_t *d_pairs, int m, uint32_t flags, float *d_q, void *stream);
 
 /* ---- training half: AlphaNNet.train = model.fit (alpha_nnet.py:58-59) -------------------------
  * Training-mode batch normalisation of a 128-channel channels-last float32 activation [rows = n * h * w][128] (the

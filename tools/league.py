@@ -2,7 +2,7 @@
 ratings of a round robin, 11x11.
 
     python tools/league.py [--nets 6] [--games 300] [--seats duel|1v3|ffa] [--blocks 4] [--models NAME G0 G1 ...] [--seed 1]
-                           [--search B [--depth 8]] [--time] [--pairs 3] [--log profiles/league_ab.log]
+                           [--search B [--depth 8]] [--time] [--pairs 3] [--log profiles/league_ab.log] [--baseline [FLAGS ...]]
 
 --nets K plays generation-0 Glorot nets of --blocks blocks, seeds 1..K; --models NAME G0 G1 ... loads NAME<G>.h5 instead (e.g.
 --models models/gen 0 15 30).  Every line-up of snake_engine.league.schedule plays --games games, all in lock step in one engine.
@@ -12,7 +12,10 @@ Arena.match(net_i, net_j, 1) of --games games per ordered pair, one after anothe
 then the medians and their ratio.  The lines are appended to --log behind a line that names the device.
 --search B: every seat moves by search (a fresh snake_engine.arena.Searcher of breadth B and --depth around each net per form:
 League.play_search against one Arena.match of two Searchers per ordered pair); the time lines then also give the net evaluations
-of the searches (Searcher.stats) and, since a searching turn is bound by them, the microseconds per evaluation."""
+of the searches (Searcher.stats) and, since a searching turn is bound by them, the microseconds per evaluation.
+--baseline [FLAGS ...]: scripted owners (snake_engine.arena.Scripted, the fixed yardstick: the same opponent in every run) join the
+table and the ratings behind the nets, one per FLAGS value (bits 1 space, 2 heads, 4 food; no value: 7, the whole policy).  A
+scripted owner moves by its script under --search too.  --nets 0 --baseline 0 1 3 7 is the round robin of four flag settings."""
 import argparse
 import os
 import statistics
@@ -49,10 +52,11 @@ def main():
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--log", default=None)
+    ap.add_argument("--baseline", nargs="*", type=int, default=None, metavar="FLAGS")
     a = ap.parse_args()
     import numpy as np
     import torch
-    from snake_engine.arena import Arena, Searcher
+    from snake_engine.arena import Arena, Scripted, Searcher
     from snake_engine.league import SEATS, League, ratings, schedule, searchers, table
     from snake_engine.net import glorot_uniform_weights
     from utils.alpha_nnet import AlphaNNet
@@ -89,6 +93,11 @@ def main():
 
     if not a.search:                                # a searcher talks to its net's range guard directly: no wrapper in between
         nets = [Counted(net) for net in nets]
+    if a.baseline is not None:
+        for flags in a.baseline or [7]:
+            names.append(f"script{flags}")
+            nets.append(Scripted(flags))
+        what += f" and {len(a.baseline or [7])} scripted owners"
     K, S = len(nets), SEATS[a.seats]
     owner = schedule(K, a.games, a.seats)
     prop = torch.cuda.get_device_properties(0)
@@ -106,7 +115,7 @@ def main():
         sides = searchers(nets, search, seed) if search else nets           # ... and for their searchers' tables
         res = league.play_search(sides, owner) if search else league.play(nets, owner)
         torch.cuda.synchronize()
-        return res, time.perf_counter() - t0, Counted.rows, sum(s.stats["net_evals"] for s in sides) if search else 0
+        return res, time.perf_counter() - t0, Counted.rows, sum(s.stats["net_evals"] for s in sides if isinstance(s, Searcher)) if search else 0
 
     def arena_form(seed):
         """one Arena.match per ordered pair, one after another -> (winner owners in schedule order, seconds, turns, rows, the
@@ -118,10 +127,9 @@ def main():
             for j in range(K):
                 if i != j:
                     sd = seed + 31 * (i * K + j)
-                    sides = [Searcher(net, seed=sd + 101 * (k + 1), **search) for k, net in enumerate((nets[i], nets[j]))] if search \
-                        else (nets[i], nets[j])
+                    sides = searchers((nets[i], nets[j]), search, sd) if search else (nets[i], nets[j])
                     r = Arena(11, 11, S, 1, a.games, sd).match(sides[0], sides[1], 1)
-                    evals += sum(s.stats["net_evals"] for s in sides) if search else 0
+                    evals += sum(s.stats["net_evals"] for s in sides if isinstance(s, Searcher)) if search else 0
                     wo.append(np.where(r.winners < 0, -1, np.where(r.winners < 1, i, j)))
                     turns += r.turns
         torch.cuda.synchronize()
@@ -130,7 +138,7 @@ def main():
     Arena(11, 11, S, 1, 64, 99).match(nets[0], nets[-1], 1)    # first launches, plans and range-guard scales settle outside the timing
     if search:                                                 # ... and the search's, on a small match of each form
         warm = schedule(K, 2, a.seats)
-        Arena(11, 11, S, 1, 8, 99).match(Searcher(nets[0], seed=1, **search), Searcher(nets[-1], seed=2, **search), 1)
+        Arena(11, 11, S, 1, 8, 99).match(*searchers((nets[0], nets[-1]), search, 1), 1)
         League(11, 11, S, 1, len(warm), 99).play_search(searchers(nets, search, 99), warm)
     else:
         League(11, 11, S, 1, len(owner), 99).play(nets, owner)

@@ -2,6 +2,9 @@
 train.py's settings (11x11, 4 snakes, 256 self-play games, depth 8, breadth 128, lr 1e-4, decay 0.98), then lets the
 reference's own judge decide on the device arena (snake_engine.arena.Arena.test_pit: test_pit.py's 1 v 3 in both seatings
 and its two-snake duel): generation N against generation 0 and against generation N/2, with 300 and with 4 096 games.
+Every judged generation (N, N/2 and 0) also meets the scripted opponent (snake_engine.arena.Scripted with the whole policy) in
+the same three seatings: the one opponent whose strength does not move from run to run, so these lines can be compared with last
+week's.  (Since the scripted opponent was added this script has not been run: profiles/learning_run.log has no such line yet.)
 
     python tools/learning_run.py [N = 30] [--out profiles] [--games 300 4096] [--seed 1] [--search BREADTH] [--league M]
 
@@ -54,7 +57,7 @@ def main():
     import numpy as np
     import torch
     import train as train_script
-    from snake_engine.arena import Arena
+    from snake_engine.arena import Arena, Scripted
     from utils import trainer_torch
     from utils.alpha_nnet import AlphaNNet
     from utils.alpha_snake_zero_trainer import AlphaSnakeZeroTrainer
@@ -128,6 +131,20 @@ def main():
                         lo, hi = wilson(round(win * games), games)
                         say(f"[{games} games{tag}] 2v2 Win Rate of {names[me]} {win}   (95 % interval {lo:.3f}-{hi:.3f}, chance 0.5)")
                     say(f"[{games} games{tag}] Competing time {dt:.1f}")
+        for gen in sorted({0, N // 2, N}, reverse=True):          # the fixed yardstick: each judged generation against the script
+            net = load(gen)
+            for games in a.games:
+                t1 = time.time()
+                r = Arena.test_pit(net, Scripted(), games, seed=3000 + games)
+                for (win, draw), seating, chance in ((r["1v3_alice"], f"gen{gen} alone against three of the script", 0.25),
+                                                     (r["1v3_bob"], f"the script alone against three of gen{gen}", 0.25)):
+                    lo, hi = wilson(round(win * games), games)
+                    say(f"[{games} games, script] 1v3 Win Rate of the lone snake, {seating}: {win} Draw Rate = {draw}   "
+                        f"(95 % interval {lo:.3f}-{hi:.3f}, chance {chance})")
+                for who, win in zip((f"gen{gen}", "the script"), r["2v2"]):
+                    lo, hi = wilson(round(win * games), games)
+                    say(f"[{games} games, script] 2v2 Win Rate of {who} {win}   (95 % interval {lo:.3f}-{hi:.3f})")
+                say(f"[{games} games, script] Competing time {time.time() - t1:.1f}")
         if a.league:
             from league import format_table                      # tools/league.py
             from snake_engine.league import round_robin

@@ -1,0 +1,110 @@
+"""The scripted opponent's cost (snake_engine.arena.Scripted, snk_pit_script_values) beside what it replaces for its seats.
+
+    python tools/script_time.py [--reps 20] [--pairs 3] [--games 300 4096] [--blocks 4] [--log profiles/script_time.log]
+
+kernel: HIP-event time of one snk_pit_script_values launch over the first 16 384 alive rows of 11x11x4 boards and the first 4 096
+of 19x19x8 boards, both taken from games the script itself has played for 20 turns (mid-game bodies, some snakes dead), beside the
+observe launch plus a --blocks-block forward over the same rows; medians of --reps launches after one that is not timed.
+match: ms per turn of Arena.match(Scripted, Scripted) beside greedy net against greedy net (1 v 3, 11x11), alternating inside this
+one process, --pairs times; a host clock around a match that ends in a device synchronise."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "alphasnake-zero_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--games", type=int, nargs="*", default=[300, 4096])
+    ap.add_argument("--blocks", type=int, default=4)
+    ap.add_argument("--log", default=None)
+    a = ap.parse_args()
+    import torch
+    from snake_engine import Engine
+    from snake_engine._lib import check
+    from snake_engine.arena import Arena, Scripted
+    from snake_engine.engine import _ptr, _stream
+    from snake_engine.net import glorot_uniform_weights
+    from utils.alpha_nnet import AlphaNNet
+
+    def say(s):
+        print(s, flush=True)
+        if a.log:
+            os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+            with open(a.log, "a") as f:
+                f.write(s + "\n")
+
+    prop = torch.cuda.get_device_properties(0)
+    say(f"script_time: {torch.cuda.get_device_name(0)} ({prop.gcnArchName}, {prop.multi_processor_count} CUs), ROCm / HIP "
+        f"{torch.version.hip}, torch {torch.__version__}")
+    script = Scripted()
+
+    def events(fn):
+        fn()
+        ms = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1) * 1e3)
+        return statistics.median(ms), min(ms), max(ms)
+
+    for hw, S, n, rows in ((11, 4, 6144, 16384), (19, 8, 1024, 4096)):
+        eng = Engine(n, hw, hw, S, 1, 0.15, seed=3)
+        eng.reset()
+        moves = eng.new((n, S), torch.uint8)
+        for _ in range(20):                          # the script plays every seat: mid-game boards
+            pairs, cnt = eng.ids()
+            m = int(cnt.item())
+            check(eng.L.snk_pit_moves(_ptr(script.q_rows(eng, pairs[:m])), _ptr(pairs), m, n, S, _ptr(moves), _stream()))
+            eng.step(moves)
+        pairs, cnt = eng.ids()
+        m = int(cnt.item())
+        if m < rows:
+            raise SystemExit(f"{hw}x{hw}x{S}: only {m} alive rows of {rows} after 20 turns")
+        pairs = pairs[:rows].contiguous()
+        net = AlphaNNet(input_shape=(2 * hw - 1, 2 * hw - 1, 3), _weights=glorot_uniform_weights((2 * hw - 1, 2 * hw - 1, 3), a.blocks, seed=1))
+
+        def forward():
+            planes, mask, _ = eng.observe_all(pairs, want_key=False)
+            return net.v_device(planes, mask)
+        forward()
+        k = events(lambda: script.q_rows(eng, pairs))
+        o = events(lambda: eng.observe_all(pairs, want_key=False))
+        f = events(forward)
+        say(f"kernel: {hw}x{hw}x{S}, {rows} rows of {n} games after 20 scripted turns ({m} alive rows): snk_pit_script_values "
+            f"{k[0]:.1f} us (min {k[1]:.1f}, max {k[2]:.1f}); observe alone {o[0]:.1f} us; observe + {a.blocks}-block forward "
+            f"{f[0]:.1f} us (min {f[1]:.1f}, max {f[2]:.1f}); ratio {f[0] / k[0]:.1f}x")
+
+    nets = [AlphaNNet(input_shape=(21, 21, 3), _weights=glorot_uniform_weights((21, 21, 3), a.blocks, seed=s)) for s in (1, 2)]
+    Arena(11, 11, 4, 1, 64, 99).match(nets[0], nets[1], 1)             # first launches, plans and range-guard scales settle outside the timing
+    Arena(11, 11, 4, 1, 64, 99).match(script, Scripted(), 1)
+    for n in a.games:
+        per = {"script v script": [], "net v net": []}
+        for k in range(a.pairs):
+            for name, sides in (("script v script", (script, Scripted())), ("net v net", nets)):
+                arena = Arena(11, 11, 4, 1, n, seed=7)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = arena.match(sides[0], sides[1], 1)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                per[name].append(dt / res.turns * 1e3)
+                say(f"match: games {n:5d} pair {k} {name}: {res.turns:4d} turns, {dt:7.3f} s, {dt / res.turns * 1e3:7.3f} ms per turn, "
+                    f"wins {res.wins_a}-{res.wins_b}, draws {res.draws}")
+        s, g = statistics.median(per["script v script"]), statistics.median(per["net v net"])
+        say(f"match: games {n:5d} median ms per turn: script v script {s:.3f}, net v net {g:.3f}, ratio {g / s:.2f}x")
+
+
+if __name__ == "__main__":
+    main()

@@ -2,13 +2,16 @@
 (snake_engine.arena.Searcher) and a greedy side of the SAME net, 11x11.
 
     python tools/search_pit.py [--games 300] [--breadth 16] [--depth 8] [--blocks 4] [--weights CKPT] [--seed 1]
-                               [--time] [--pairs 2] [--log profiles/arena_search.log]
+                               [--time] [--pairs 2] [--log profiles/arena_search.log] [--baseline]
 
 Strength (default): 1 v 3 with the searcher alone, 1 v 3 with the searcher's three against the greedy one, and the duel; win and
 draw rates of the searching side with their binomial 95 % intervals (Wilson), ms per turn and net evaluations per turn.
 --time: greedy v greedy, search v greedy and search v search on the same start boards and engine seed, alternating inside this
 one process, `--pairs` times; ms per turn (host clock around a match that ends in a device synchronise), net evaluations per
 turn, and the host time DeviceMCTS._ensure took (its buffers are made again whenever the number of open games changes).
+--baseline: the net against the scripted opponent (snake_engine.arena.Scripted with the whole policy, the fixed yardstick) instead
+of against itself: the greedy net in the duel and in 1 v 3 both ways, then the net moving by search in the duel; the net side's
+win and draw rates with the same intervals.
 The lines are appended to --log behind a line that names the device."""
 import argparse
 import math
@@ -43,9 +46,10 @@ def main():
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--pairs", type=int, default=2)
     ap.add_argument("--log", default=None)
+    ap.add_argument("--baseline", action="store_true")
     a = ap.parse_args()
     import torch
-    from snake_engine.arena import Arena, Searcher
+    from snake_engine.arena import Arena, Scripted, Searcher
     from snake_engine.mcts import DeviceMCTS
     from snake_engine.net import glorot_uniform_weights
     from utils.alpha_nnet import AlphaNNet
@@ -98,7 +102,24 @@ def main():
 
     play(4, 1, (True, False), 8, 99)                       # first launches, plans and range-guard scales settle outside the timing
     play(4, 1, (False, False), 8, 99)
-    if a.time:
+    if a.baseline:
+        script = Scripted()
+        lineups = [("duel, the net first", 2, 1, 0), ("1v3, the net alone", 4, 1, 0), ("1v3, three of the net against the script", 4, 3, 0)]
+        movers = [("greedy net", None, lineups)] + [(f"search breadth {b:3d}", b, lineups[:1]) for b in a.breadth]
+        for mover, breadth, ups in movers:
+            for i, (name, snakes, a_cnt, who) in enumerate(ups):
+                side = net if breadth is None else Searcher(net, breadth, a.depth, seed=a.seed + 11)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = Arena(11, 11, snakes, 1, a.games, a.seed + i).match(side, script, a_cnt)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                wins = (res.wins_a, res.wins_b)[who]
+                (wl, wh), (dl, dh) = wilson(wins, a.games), wilson(res.draws, a.games)
+                say(f"baseline: {mover} against the script, {name}: net wins {wins / a.games:.3f} [{wl:.3f}, {wh:.3f}], draws "
+                    f"{res.draws / a.games:.3f} [{dl:.3f}, {dh:.3f}], script wins {(a.games - wins - res.draws) / a.games:.3f}; "
+                    f"{res.turns} turns, {dt / res.turns * 1e3:.3f} ms per turn")
+    elif a.time:
         forms = [("greedy v greedy", (False, False)), ("search v greedy", (True, False)), ("search v search", (True, True))]
         for breadth in a.breadth:
             start, per = None, {name: [] for name, _ in forms}
