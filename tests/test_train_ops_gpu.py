@@ -577,7 +577,7 @@ def test_sums_taken_in_the_stem_and_the_head_on_their_way_out(torch_gpu, n, hw):
     """round 5: the stem's convolution leaves with the sums its batch norm starts from (snk_stem_conv_f32_stats), and the last
     tower layer's batch-norm kernel with the head's 1x1 convolution and ITS sums (snk_bn_train_apply_head) -- two passes over a
     462 MB tensor less in every step.  Outputs bit-identical to the separate kernels', sums equal up to summation order
-    (alpha_nnet.py:21-24, 46-50 under Keras fit)"""
+    (alpha_nnet.py:21-24, 46-50 under Keras fit).  da, dw1x1 and the sums against float64: tests/test_train_head_gpu.py"""
     torch = torch_gpu
     from snake_engine._lib import lib, check
     L, st = lib(), torch.cuda.current_stream().cuda_stream
