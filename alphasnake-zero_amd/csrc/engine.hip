@@ -1583,6 +1583,143 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_pit_script(const uint8_t *__r
     if (in && k < 3) q[3 * (size_t)row + k] = (float)score;
 }
 
+// ------------------------------------------------------------------------------------------
+// replays of chosen games of a pit match (snake_engine.replay.Replay): the two boards Game.tic(show=True) appends per tick
+// (Game.draw game.py:281-300, called at game.py:140-141 and 194-195) for a list of recorded slots, drawn into a log in HBM.
+// One wavefront per recorded game.  Lane s holds snake s: where its head is drawn, the length it is sorted by, and the run of
+// ring entries that are its body.  The board is built in the wave's own LDS in three phases ordered by GAME_SYNC -- food (or
+// zeros), heads, bodies -- and stored as dwords plus at most three tail bytes, so the stride padding is never written.
+// Heads: sorted() by length is stable over a list in id order (game.py:287), so of the heads on one cell the largest (length, id)
+// is drawn last; here the lanes that lose that comparison do not write, and the cell has one writer.  Bodies of different snakes
+// share no cell (both would be dead) and a doubled tail writes one value twice.  Every ring walk is bounded by the ring's size
+// and every cell index is compared with NC before it indexes the board, whatever the record holds.
+// ------------------------------------------------------------------------------------------
+#define REC_CELLS ((SNK_MAX_CELLS + 15) / 16 * 16)
+
+__device__ static inline void rec_draw_snakes(int8_t *board, const uint8_t *rec, const Layout &L, int lane, int head, int len_sort,
+                                              int first, int cnt)
+{
+    bool beaten = false;                                  // game.py:287-291: the last head drawn on a cell stays
+    for (int o = 0; o < SNK_MAX_SNAKES; ++o) {
+        const int ho = __shfl(head, o, 64), lo = __shfl(len_sort, o, 64);
+        if (o != lane && ho == head && (lo > len_sort || (lo == len_sort && o > lane))) beaten = true;
+    }
+    if (head >= 0 && !beaten) board[head] = (int8_t)(-(lane + 1));
+    GAME_SYNC();
+    for (int s = 0; s < L.S; ++s) {                       // game.py:292-294: the bodies, over the heads
+        const int first_s = __shfl(first, s, 64);
+        int cnt_s = __shfl(cnt, s, 64);
+        cnt_s = cnt_s < L.cap ? cnt_s : L.cap;
+        for (int k = lane; k < cnt_s; k += 64) {
+            const int c = script_ring_cell(rec, L, s, first_s + k);
+            if (c < L.NC) board[c] = (int8_t)(s + 1);
+        }
+    }
+    GAME_SYNC();
+}
+
+__device__ static inline void rec_store(const int8_t *board, int8_t *out, int NC, int lane)
+{
+    for (int j = lane; j < NC / 4; j += 64) ((uint32_t *)out)[j] = ((const uint32_t *)board)[j];
+    const int c = (NC & ~3) + lane;
+    if (c < NC) out[c] = board[c];
+}
+
+// before the step: the snakes of the mid-tick board (game.py:90-127, drawn at :140-141)
+__global__ __launch_bounds__(BLOCK_THREADS) void k_pit_record_moves(const uint8_t *__restrict__ state, Layout L, int n_slots,
+                                                                   const uint8_t *__restrict__ live, const int32_t *__restrict__ slots,
+                                                                   int r, const uint8_t *__restrict__ moves, int8_t *__restrict__ frames,
+                                                                   int fstride)
+{
+    __shared__ __align__(16) int8_t sboard[WAVES_PER_BLOCK][REC_CELLS];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int i = blockIdx.x * WAVES_PER_BLOCK + wv;
+    if (i >= r) return;                                   // whole wavefronts leave: nothing below waits for another wave
+    const int slot = slots[i];
+    if (slot < 0 || slot >= n_slots || !live[slot]) return;
+    int8_t *board = sboard[wv];
+    const uint8_t *rec = state + (size_t)slot * L.stride;
+    const SnakeMeta *meta = (const SnakeMeta *)(rec + L.meta_off);
+    const uint64_t *food = (const uint64_t *)(rec + L.food_off);
+    const bool act = lane < L.S;
+    SnakeMeta m = {0, 0, 0, 0, 0};
+    int mv = 1;
+    if (act) { m = meta[lane]; mv = moves[(size_t)slot * L.S + lane]; }
+    const bool alive = act && m.alive && m.len >= 1;
+    const bool moved = __popcll(__ballot(alive)) >= 2;    // k_step: a game with fewer than two snakes alive stands still
+    int head = -1, len_sort = 0, first = 0, cnt = 0;
+    if (alive) {
+        const int hc = script_ring_cell(rec, L, lane, m.tail + m.len - 1);
+        len_sort = m.len;
+        cnt = m.len - 1;
+        if (moved) {
+            const int d = (mv + m.dir + 3) & 3;           // game.py:92
+            int y = hc / L.W, x = hc - y * L.W;
+            y += (d == 2) - (d == 0);
+            x += (d == 1) - (d == 3);
+            const bool oob = (y < 0) | (y >= L.H) | (x < 0) | (x >= L.W);
+            head = oob ? -1 : y * L.W + x;
+            first = m.tail + 1;                           // the tail node is popped, the old head joins the body
+        } else {
+            head = hc < L.NC ? hc : -1;
+            first = m.tail;
+        }
+    }
+    const bool hasfood = moved && head >= 0 && food_bit(food, head);
+    bool eats = hasfood;                                  // game.py:121-127: the first snake in list order on a food cell eats
+    for (int o = 0; o < SNK_MAX_SNAKES; ++o) {
+        const int ho = __shfl(head, o, 64), fo = __shfl((int)hasfood, o, 64);
+        if (o < lane && fo && ho == head) eats = false;
+    }
+    len_sort += eats;
+    for (int j = lane; j < fstride / 4; j += 64) ((uint32_t *)board)[j] = 0u;
+    GAME_SYNC();
+    rec_draw_snakes(board, rec, L, lane, head, len_sort, first, cnt);
+    rec_store(board, frames + (size_t)(2 * i) * fstride, L.NC, lane);
+}
+
+// after the step: the food into the mid-tick board (game.py:129-138), and the post-tick board (game.py:194-195)
+__global__ __launch_bounds__(BLOCK_THREADS) void k_pit_record_boards(const uint8_t *__restrict__ state, Layout L, int n_slots,
+                                                                    const uint8_t *__restrict__ live, const int32_t *__restrict__ slots,
+                                                                    int r, int8_t *__restrict__ frames, int fstride)
+{
+    __shared__ __align__(16) int8_t sboard[WAVES_PER_BLOCK][REC_CELLS];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int i = blockIdx.x * WAVES_PER_BLOCK + wv;
+    if (i >= r) return;
+    const int slot = slots[i];
+    if (slot < 0 || slot >= n_slots || !live[slot]) return;
+    int8_t *board = sboard[wv];
+    const uint8_t *rec = state + (size_t)slot * L.stride;
+    const SnakeMeta *meta = (const SnakeMeta *)(rec + L.meta_off);
+    const uint64_t *food = (const uint64_t *)(rec + L.food_off);
+    const int NC = L.NC;
+    for (int c = lane; c < fstride; c += 64) board[c] = (int8_t)((c < NC && food_bit(food, c)) ? 9 : 0);      // game.py:284-285
+    GAME_SYNC();
+    SnakeMeta m = {0, 0, 0, 0, 0};
+    if (lane < L.S) m = meta[lane];
+    int head = -1, len_sort = 0, first = 0, cnt = 0;
+    if (lane < L.S && m.alive && m.len >= 1) {
+        const int hc = script_ring_cell(rec, L, lane, m.tail + m.len - 1);
+        head = hc < NC ? hc : -1;
+        len_sort = m.len;
+        first = m.tail;
+        cnt = m.len - 1;
+    }
+    rec_draw_snakes(board, rec, L, lane, head, len_sort, first, cnt);
+    int8_t *mid = frames + (size_t)(2 * i) * fstride;
+    rec_store(board, mid + fstride, NC, lane);
+    for (int j = lane; j < NC / 4; j += 64) {             // a cell of the mid-tick board that shows a snake keeps it
+        uint32_t v = ((const uint32_t *)mid)[j];
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            if (((v >> (8 * b)) & 0xFFu) == 0u && food_bit(food, 4 * j + b)) v |= 9u << (8 * b);
+        ((uint32_t *)mid)[j] = v;
+    }
+    const int c = (NC & ~3) + lane;
+    if (c < NC && mid[c] == 0 && food_bit(food, c)) mid[c] = 9;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 // square boards of 5x5 (the eight standard start cells are distinct from there on, game.py:25-29) to 19x19 (SNK_MAX_CELLS);
 // the reference's observation is a rot90 of a (2H-1)x(2W-1) canvas, so only square boards batch (game.py:257)
@@ -1896,6 +2033,57 @@ extern "C" int snk_pit_script_values(const snk_engine *e, const int32_t *d_pairs
     else if (L.FW == 2) k_pit_script<2><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
     else k_pit_script<6><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
 #undef SCRIPT_ARGS
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_record_stride(int H, int W)
+{
+    if (!supported_board(H, W)) return -1;
+    return align_up(H * W, 16);
+}
+
+extern "C" int snk_pit_record_slots(const snk_engine *e, const int32_t *h_slots, int r, int32_t *d_slots, void *stream)
+{
+    SNK_REQUIRE(r >= 0, "snk_pit_record_slots: r=%d", r);
+    if (r == 0) return 0;
+    SNK_REQUIRE(e && h_slots && d_slots, "snk_pit_record_slots: NULL argument");
+    SNK_REQUIRE(r <= e->n_slots, "snk_pit_record_slots: r=%d exceeds %d slots", r, e->n_slots);
+    std::vector<uint8_t> seen((size_t)e->n_slots, 0);
+    for (int i = 0; i < r; ++i) {
+        const int s = h_slots[i];
+        SNK_REQUIRE(s >= 0 && s < e->n_slots, "snk_pit_record_slots: slot %d (entry %d) outside 0..%d", s, i, e->n_slots - 1);
+        SNK_REQUIRE(!seen[s], "snk_pit_record_slots: slot %d is listed twice", s);
+        seen[s] = 1;
+    }
+    SNK_CHECK_HIP(hipMemcpyAsync(d_slots, h_slots, (size_t)r * sizeof(int32_t), hipMemcpyHostToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int snk_pit_record_moves(const snk_engine *e, const uint8_t *d_live, const int32_t *d_slots, int r, const uint8_t *d_moves,
+                                    int8_t *d_frames, void *stream)
+{
+    SNK_REQUIRE(r >= 0, "snk_pit_record_moves: r=%d", r);
+    if (r == 0) return 0;
+    SNK_REQUIRE(e && d_live && d_slots && d_moves && d_frames, "snk_pit_record_moves: NULL argument");
+    SNK_REQUIRE(((uintptr_t)d_frames & 3u) == 0, "snk_pit_record_moves: d_frames is not 4-byte aligned");
+    const int fstride = align_up(e->L.NC, 16);
+    k_pit_record_moves<<<wave_grid(r), BLOCK_THREADS, 0, (hipStream_t)stream>>>(e->d_state, e->L, e->n_slots, d_live, d_slots, r, d_moves,
+                                                                                d_frames, fstride);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_record_boards(const snk_engine *e, const uint8_t *d_live, const int32_t *d_slots, int r, int8_t *d_frames,
+                                     void *stream)
+{
+    SNK_REQUIRE(r >= 0, "snk_pit_record_boards: r=%d", r);
+    if (r == 0) return 0;
+    SNK_REQUIRE(e && d_live && d_slots && d_frames, "snk_pit_record_boards: NULL argument");
+    SNK_REQUIRE(((uintptr_t)d_frames & 3u) == 0, "snk_pit_record_boards: d_frames is not 4-byte aligned");
+    const int fstride = align_up(e->L.NC, 16);
+    k_pit_record_boards<<<wave_grid(r), BLOCK_THREADS, 0, (hipStream_t)stream>>>(e->d_state, e->L, e->n_slots, d_live, d_slots, r, d_frames,
+                                                                                 fstride);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

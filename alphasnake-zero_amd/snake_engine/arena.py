@@ -40,13 +40,18 @@ snk_pit_script_values, and snk_pit_moves turns the scores into moves as it does 
 then run over the other side's rows only (the row list is team A first, so both are contiguous slices), and ``Scripted`` against
 ``Scripted`` launches neither.  The turn's read-back stays the one it is.  A match without a ``Scripted`` issues exactly the
 launches it issued before there was one.
+
+``Arena.record(games)`` returns a ``replay.Replay`` that the next match fills with the boards Game.tic(show=True) draws for those
+games (game.py:140-141, 194-195): snk_pit_record_moves before the step and snk_pit_record_boards after it draw them into a log on
+the device, which is copied to the host once, after the last turn (``Replay`` below; snake_engine/replay.py names it).  The turn's read-back stays the one
+it is, and a match without a recorder issues exactly the launches and read-backs it issued before there was one.
 """
 from collections import namedtuple
 
 import numpy as np
 import torch
 
-from ._lib import check, EngineError
+from ._lib import check, lib, EngineError
 from .engine import Engine, _ptr, _stream
 
 ArenaResult = namedtuple("ArenaResult", "winners lengths turns wins_a wins_b draws")
@@ -169,6 +174,103 @@ def mixed_values(eng, sides, rows, pairs):
     return q.contiguous()
 
 
+# ---- replays of chosen games (snake_engine/replay.py is the module a user imports; the code stands here because this module
+# ---- imports the library binding and the engine and nothing else of the package) ---------------------------------------------
+def checked_games(games, game_cnt):
+    """the recorded game indices as int32[r]: distinct, each inside 0..game_cnt-1, in the caller's order"""
+    out = []
+    for g in games:
+        if isinstance(g, (bool, np.bool_)) or int(g) != g:
+            raise ValueError(f"game index {g!r} is no integer")
+        out.append(int(g))
+    for g in out:
+        if not 0 <= g < game_cnt:
+            raise ValueError(f"game index {g} outside 0..{game_cnt - 1}")
+    if len(set(out)) != len(out):
+        twice = sorted(g for g in set(out) if out.count(g) > 1)
+        raise ValueError(f"game index {twice[0]} is given twice")
+    return np.array(out, np.int32)
+
+
+def board_text(frame):
+    """the bytes Game.draw appends for one board (game.py:296-300): str(row) + newline per row, then an empty line"""
+    return ("".join(str([int(v) for v in row]) + "\n" for row in frame) + "\n").encode("ascii")
+
+
+class Replay:
+    """the frames of the recorded games of one match.  frames / text / write are there once that match is over."""
+
+    def __init__(self, games, height, width, game_cnt, first_turns=64):
+        self.games = checked_games(games, game_cnt)
+        self.height, self.width = int(height), int(width)
+        self.stride = lib().snk_pit_record_stride(self.height, self.width)
+        if self.stride < 0:
+            raise ValueError(f"no replay of a {height}x{width} board")
+        if int(first_turns) < 1:
+            raise ValueError(f"first_turns {first_turns}: the log starts with at least one turn")
+        self.first_turns = int(first_turns)
+        self.grown = 0                  # how often the log was doubled
+        self.lengths = None             # int32[len(games)] once the match is over
+        self._row = {int(g): i for i, g in enumerate(self.games)}
+        self._log = self._slots = self._host = None
+
+    # ---- the match's side ------------------------------------------------------------------------------------------------
+    def begin(self, engine):
+        """the device list of recorded slots and the first log; the library checks the list once more"""
+        r = len(self.games)
+        self.grown, self.lengths, self._host = 0, None, None
+        self._slots = engine.new((max(r, 1),), torch.int32)
+        self._log = engine.new((self.first_turns, max(r, 1), 2, self.stride), torch.int8)
+        check(engine.L.snk_pit_record_slots(engine.h, self.games.ctypes.data if r else None, r, _ptr(self._slots), _stream()))
+
+    def _turn_ptr(self, turn):
+        return self._log.data_ptr() + (turn - 1) * self._log.shape[1] * 2 * self.stride
+
+    def before_step(self, engine, turn, live, moves):
+        if turn > self._log.shape[0]:   # the host counts the turns: double the log, device to device
+            log = engine.new((2 * self._log.shape[0],) + tuple(self._log.shape[1:]), torch.int8)
+            log[:self._log.shape[0]].copy_(self._log)
+            self._log = log
+            self.grown += 1
+        check(engine.L.snk_pit_record_moves(engine.h, _ptr(live), _ptr(self._slots), len(self.games), _ptr(moves),
+                                            self._turn_ptr(turn), _stream()))
+
+    def after_step(self, engine, turn, live):
+        check(engine.L.snk_pit_record_boards(engine.h, _ptr(live), _ptr(self._slots), len(self.games), self._turn_ptr(turn),
+                                             _stream()))
+
+    def end(self, turns, lengths):
+        """the one copy of the log, after the last turn; lengths: the result's verdict turns of all games (on the host)"""
+        self.lengths = np.asarray(lengths, np.int32)[self.games]
+        self._host = self._log[:turns].cpu().numpy()
+        self._log = self._slots = None
+
+    # ---- the reader's side -----------------------------------------------------------------------------------------------
+    def frames(self, g):
+        """int8[2 * lengths[g]][H][W]: per turn the mid-tick board (game.py:140-141), then the post-tick board (:194-195)"""
+        if self._host is None:
+            raise RuntimeError("the match this Replay records has not been played")
+        if int(g) not in self._row:
+            raise KeyError(f"game {g} was not recorded (recorded: {self.games.tolist()})")
+        i = self._row[int(g)]
+        nc = self.height * self.width
+        out = self._host[:int(self.lengths[i]), i, :, :nc]
+        return np.ascontiguousarray(out).reshape(-1, self.height, self.width)
+
+    def text(self, g):
+        """the bytes Game.draw would have appended to replay.rep over game g"""
+        return frames_text(self.frames(g))
+
+    def write(self, g, path="replay.rep", append=True):
+        with open(path, "ab" if append else "wb") as f:
+            f.write(self.text(g))
+
+
+def frames_text(frames):
+    """int8[k][H][W] -> the k boards in Game.draw's text form"""
+    return b"".join(board_text(fr) for fr in np.asarray(frames))
+
+
 class Arena:
 
     def __init__(self, height=11, width=11, snake_cnt=4, health_dec=1, game_cnt=1, seed=None):
@@ -194,6 +296,14 @@ class Arena:
         self._winner = eng.new((n,), torch.int32)
         self._length = eng.new((n,), torch.int32)
         self._roots = None                        # the searching turn's buffers, made by the first match that searches
+        self._recorder = self._rec = None         # the Replay the next match fills / the one the running match is filling
+
+    def record(self, games, first_turns=64):
+        """games: distinct game indices in any order (an index out of range or given twice is a ValueError, before anything
+        touches the device).  Returns the Replay the next match on this arena fills; the recorder is dropped when that match
+        ends.  first_turns: the turns the log on the device is first sized for (it doubles as the match goes on)."""
+        self._recorder = Replay(games, self.height, self.width, self.game_cnt, first_turns)
+        return self._recorder
 
     @classmethod
     def from_engine(cls, engine):
@@ -233,12 +343,21 @@ class Arena:
         self._live.fill_(1)
         self._winner.fill_(-1)
         self._length.zero_()
-        if isinstance(alice, Searcher) or isinstance(bob, Searcher):
-            turn = self._search_turns(alice, bob, a_cnt, spawn_tape)
-        else:
-            turn = self._greedy_turns(alice, bob, a_cnt, spawn_tape)
+        rec, self._recorder = self._recorder, None
+        if rec is not None:
+            rec.begin(eng)
+        self._rec = rec
+        try:
+            if isinstance(alice, Searcher) or isinstance(bob, Searcher):
+                turn = self._search_turns(alice, bob, a_cnt, spawn_tape)
+            else:
+                turn = self._greedy_turns(alice, bob, a_cnt, spawn_tape)
+        finally:
+            self._rec = None
         winners = self._winner.cpu().numpy()
         lengths = self._length.cpu().numpy()
+        if rec is not None:
+            rec.end(turn, lengths)                # the log's one copy, after the last turn
         wins_a = int(((winners >= 0) & (winners < a_cnt)).sum())
         wins_b = int((winners >= a_cnt).sum())
         return ArenaResult(winners, lengths, turn, wins_a, wins_b, n - wins_a - wins_b)
@@ -275,7 +394,12 @@ class Arena:
             tape = torch.as_tensor(np.ascontiguousarray(spawn_tape(turn), np.int16), device=eng.device)
             if tape.numel() != n:
                 raise ValueError(f"spawn_tape({turn}) has {tape.numel()} entries for {n} games")
+        rec = self._rec
+        if rec is not None:                       # the mid-tick snakes, from the records the step is about to change
+            rec.before_step(eng, turn, live, self._moves)
         check(L.snk_engine_step_active_tape(eng.h, _ptr(live), n, _ptr(self._moves), _ptr(tape), _ptr(self._done), None, _stream()))
+        if rec is not None:                       # by the live flags the step saw: before the verdict clears them
+            rec.after_step(eng, turn, live)
         check(L.snk_engine_rewards(eng.h, None, n, _ptr(self._rewards), _stream()))
         check(L.snk_pit_verdict(eng.h, _ptr(self._done), _ptr(self._rewards), n, a_cnt, turn, _ptr(live), _ptr(self._winner),
                                 _ptr(self._length), _stream()))

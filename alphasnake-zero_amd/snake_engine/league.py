@@ -37,6 +37,9 @@ An owner of either may be an ``arena.Scripted`` (the fixed yardstick of a table:
 greedy owner, its slice of the row list is scored by snk_pit_script_values, and the observe launch and the nets run over the
 other owners' rows only -- one observe per run of consecutive net owners.  A match without a ``Scripted`` issues exactly the
 launches it issued before there was one.
+
+``League.record(games)`` is ``Arena.record``: the Replay it returns is filled by the next ``play`` or ``play_search`` with the
+boards of those games (snake_engine/replay.py) -- two more launches per turn, the read-back unchanged, one copy at the end.
 """
 from collections import namedtuple
 
@@ -44,7 +47,7 @@ import numpy as np
 import torch
 
 from ._lib import check, EngineError
-from .arena import Scripted, Searcher, mixed_values
+from .arena import Replay, Scripted, Searcher, mixed_values
 from .engine import Engine, _ptr, _stream
 
 MAX_OWNERS = 16          # SNK_PIT_MAX_OWNERS of include/snake_engine.h
@@ -86,6 +89,13 @@ class League:
         self._winner_owner = eng.new((n,), torch.int32)
         self._length = eng.new((n,), torch.int32)
         self._roots = None                        # the searching turn's buffers, made by the first match that searches
+        self._recorder = None                     # the Replay the next match fills
+
+    def record(self, games, first_turns=64):
+        """Arena.record: distinct game indices in any order (out of range or twice: a ValueError before anything touches the
+        device) -> the Replay the next play / play_search fills; the recorder is dropped when that match ends"""
+        self._recorder = Replay(games, self.height, self.width, self.game_cnt, first_turns)
+        return self._recorder
 
     @classmethod
     def from_engine(cls, engine):
@@ -140,6 +150,9 @@ class League:
         self._winner.fill_(-1)
         self._winner_owner.fill_(-1)
         self._length.zero_()
+        rec, self._recorder = self._recorder, None
+        if rec is not None:
+            rec.begin(eng)
         L = eng.L
         live, pairs, moves = self._live, self._pairs, self._moves
         counts = self._counts[:K]
@@ -166,11 +179,18 @@ class League:
                 tape = torch.as_tensor(np.ascontiguousarray(spawn_tape(turn), np.int16), device=eng.device)
                 if tape.numel() != n:
                     raise ValueError(f"spawn_tape({turn}) has {tape.numel()} entries for {n} games")
+            if rec is not None:                   # the mid-tick snakes, from the records the step is about to change
+                rec.before_step(eng, turn, live, moves)
             check(L.snk_engine_step_active_tape(eng.h, _ptr(live), n, _ptr(moves), _ptr(tape), _ptr(self._done), None, _stream()))
+            if rec is not None:                   # by the live flags the step saw: before the verdict clears them
+                rec.after_step(eng, turn, live)
             check(L.snk_engine_rewards(eng.h, None, n, _ptr(self._rewards), _stream()))
             check(L.snk_pit_verdict_owned(eng.h, _ptr(self._done), _ptr(self._rewards), n, _ptr(d_owner), K, turn, _ptr(live),
                                           _ptr(self._winner), _ptr(self._winner_owner), _ptr(self._length), _stream()))
-        return LeagueResult(self._winner.cpu().numpy(), self._winner_owner.cpu().numpy(), self._length.cpu().numpy(), turn)
+        result = LeagueResult(self._winner.cpu().numpy(), self._winner_owner.cpu().numpy(), self._length.cpu().numpy(), turn)
+        if rec is not None:
+            rec.end(turn, result.lengths)         # the log's one copy, after the last turn
+        return result
 
     def play_search(self, sides, owner, init_tape=None, spawn_tape=None, counts_log=None):
         """play with any owner moving by search: sides[o] is a net with v_device, a Scripted or a Searcher around a net, in any
@@ -207,6 +227,9 @@ class League:
         self._winner.fill_(-1)
         self._winner_owner.fill_(-1)
         self._length.zero_()
+        rec, self._recorder = self._recorder, None
+        if rec is not None:
+            rec.begin(eng)
         L = eng.L
         live, pairs, moves = self._live, self._pairs, self._moves
         if search_mask:
@@ -257,11 +280,18 @@ class League:
                 tape = torch.as_tensor(np.ascontiguousarray(spawn_tape(turn), np.int16), device=eng.device)
                 if tape.numel() != n:
                     raise ValueError(f"spawn_tape({turn}) has {tape.numel()} entries for {n} games")
+            if rec is not None:                   # the mid-tick snakes, from the records the step is about to change
+                rec.before_step(eng, turn, live, moves)
             check(L.snk_engine_step_active_tape(eng.h, _ptr(live), n, _ptr(moves), _ptr(tape), _ptr(self._done), None, _stream()))
+            if rec is not None:                   # by the live flags the step saw: before the verdict clears them
+                rec.after_step(eng, turn, live)
             check(L.snk_engine_rewards(eng.h, None, n, _ptr(self._rewards), _stream()))
             check(L.snk_pit_verdict_owned(eng.h, _ptr(self._done), _ptr(self._rewards), n, _ptr(d_owner), K, turn, _ptr(live),
                                           _ptr(self._winner), _ptr(self._winner_owner), _ptr(self._length), _stream()))
-        return LeagueResult(self._winner.cpu().numpy(), self._winner_owner.cpu().numpy(), self._length.cpu().numpy(), turn)
+        result = LeagueResult(self._winner.cpu().numpy(), self._winner_owner.cpu().numpy(), self._length.cpu().numpy(), turn)
+        if rec is not None:
+            rec.end(turn, result.lengths)         # the log's one copy, after the last turn
+        return result
 
     @staticmethod
     def _values(nets, rows, planes, mask):

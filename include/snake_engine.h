@@ -58,8 +58,9 @@ const char *snk_last_error(void);
                              * snk_engine_step_active_tape) were added under 113, and so were the searching pit's
                              * (snk_pit_roots, snk_pit_search_moves) and the league's (snk_pit_owned_scratch_elems,
                              * snk_pit_rows_owned, snk_pit_verdict_owned) and the searching league's (snk_pit_roots_owned,
-                             * snk_pit_search_moves_owned) and the scripted opponent's (snk_pit_script_values): no argument list
-                             * of an older one changed */
+                             * snk_pit_search_moves_owned) and the scripted opponent's (snk_pit_script_values) and the replay
+                             * recorder's (snk_pit_record_stride, snk_pit_record_slots, snk_pit_record_moves,
+                             * snk_pit_record_boards): no argument list of an older one changed */
 int snk_version(void);
 
 /* ---- engine lifetime -------------------------------------------------------------------
@@ -599,6 +600,36 @@ int snk_pit_search_moves_owned(const uint8_t *d_found, const int32_t *d_rank, in
 #define SNK_SCRIPT_HEADS 2u
 #define SNK_SCRIPT_FOOD 4u
 int snk_pit_script_values(const snk_engine *e, const int32_t *d_pairs, int m, uint32_t flags, float *d_q, void *stream);
+
+/* ---- replays of chosen games of a pit match (Game.draw game.py:281-300, called by Game.tic game.py:140-141 and 194-195) ----------
+ * snake_engine.replay.Replay: the two boards Game.tic(show=True) appends per tick, drawn by kernels into a log in device memory for
+ * a list of r recorded slots; the host fetches the log once, after the match.  A frame is int8[H*W] (cell y * W + x) at a stride of
+ * snk_pit_record_stride(H, W) = H*W rounded up to a multiple of 16 bytes; the bytes between H*W and the stride are never written.
+ * Cell codes (game.py:281-294): 0 empty, 9 food, -(id + 1) a head, id + 1 a body node.  Draw order (game.py:284-294): food first;
+ * then the heads in ascending (length, id) -- sorted() is stable and the snakes stand in id order -- so a shared cell shows the
+ * longer snake, at equal length the higher id; a head outside the board is not drawn (game.py:289-291); the bodies last, over heads.
+ * d_frames int8[r][2][stride] is one turn's slice of the log: frame [i][0] is the mid-tick board of slot d_slots[i], [i][1] its
+ * post-tick board.  d_live uint8[n_slots] and d_moves uint8[n_slots][S] are indexed by slot: the flags and the dense moves the
+ * turn's snk_engine_step_active_tape is given.  A recorded slot whose flag is 0 is not touched in either frame (its verdict is in);
+ * snk_pit_record_boards therefore runs after the step and BEFORE the verdict clears the flags.
+ * snk_pit_record_stride: the frame stride in bytes, -1 for a board outside 5x5 .. 19x19.
+ * snk_pit_record_slots: checks the host list h_slots int32[r] -- every slot inside the engine, none twice -- and copies it to
+ *   d_slots int32[r] on the stream; a bad list is refused before anything is copied.  The kernels skip a slot outside the engine.
+ * snk_pit_record_moves (game.py:90-127, drawn at :140-141), BEFORE the step: every snake alive before the tick after its move and
+ *   eat phases, the dying ones included: heading (move + dir - 1) % 4 (game.py:92), the new head, the old head joins the body, the
+ *   tail node is popped (Snake.move game.py:329-358); the first snake in id order whose new head is on a food cell grows by one
+ *   (game.py:121-127; the doubled tail lies on a cell the body already shows, so growth matters for the head order alone).  Cells
+ *   without a snake are written 0.  A live game with fewer than two snakes alive is not moved by the step: it is drawn as it stands.
+ * snk_pit_record_boards (game.py:129-138 and :194-195), AFTER the step: the food after the step (spawning included) is merged into
+ *   frame 0 -- a cell that holds a head or a body keeps it -- and frame 1 is drawn from the record: its food and surviving snakes.
+ * One wavefront per recorded game, the board built in LDS (food, heads, bodies), stored as dwords and at most three tail bytes; no
+ * atomics.  r == 0 is a no-op that accepts NULL buffers; a NULL array, a negative r or (snk_pit_record_slots) a slot outside the
+ * engine is an error before any launch or copy.                                                                                  */
+int snk_pit_record_stride(int H, int W);
+int snk_pit_record_slots(const snk_engine *e, const int32_t *h_slots, int r, int32_t *d_slots, void *stream);
+int snk_pit_record_moves(const snk_engine *e, const uint8_t *d_live, const int32_t *d_slots, int r, const uint8_t *d_moves,
+                         int8_t *d_frames, void *stream);
+int snk_pit_record_boards(const snk_engine *e, const uint8_t *d_live, const int32_t *d_slots, int r, int8_t *d_frames, void *stream);
 
 /* ---- training half: AlphaNNet.train = model.fit (alpha_nnet.py:58-59) -------------------------
  * Training-mode batch normalisation of a 128-channel channels-last float32 activation [rows = n * h * w][128] (the

@@ -1,11 +1,14 @@
 """The pit match, host loop against device loop: `MPGameRunner.run` and `MPGameRunner.run_device` on the same start boards, the
 same engine seed (so the same food spawns) and the same two nets (generation-0 Glorot weights, two seeds), 11x11 with 4 snakes.
 
-    python tools/arena_time.py [games ...] [--pairs 3] [--blocks 4] [--log profiles/arena_ab.log]
+    python tools/arena_time.py [games ...] [--pairs 3] [--blocks 4] [--log profiles/arena_ab.log] [--record K]
 
 For every game count (default 300 and 4096) the two forms alternate inside this one process, `--pairs` times; a line per
 match with its turns, seconds and ms per turn, then the medians.  The winners of the two forms are compared: they play the
-same match."""
+same match.
+--record K: instead, what a replay recorder costs: Arena.match of the same two nets without a recorder and with one on the first K
+games (Arena.record), alternating inside this one process on the same start boards, `--pairs` times; ms per turn of both, the
+medians and the added time per turn.  The recorded match's winners and frame counts are checked against the plain one's."""
 import argparse
 import os
 import statistics
@@ -24,6 +27,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--log", default=None)
+    ap.add_argument("--record", type=int, default=None, metavar="K")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -61,6 +65,50 @@ def main():
     say(f"arena_time: 11x11, 4 snakes (1 v 3), {a.blocks}-block Glorot nets (seeds 1, 2), {a.pairs} alternating pairs per size, "
         f"{torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}, "
         f"{torch.cuda.get_device_properties(0).multi_processor_count} CUs), ROCm / HIP {torch.version.hip}, torch {torch.__version__}")
+    def write_log():
+        if a.log:
+            os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+            with open(a.log, "w") as f:
+                f.write("\n".join(lines) + "\n")
+
+    def match(n, start, record):
+        from snake_engine.arena import Arena
+        arena = Arena(11, 11, 4, 1, n, seed=7)
+        if start is None:
+            start = arena.engine.export()
+        else:
+            arena.import_states(start)
+        rep = arena.record(range(min(record, n))) if record else None
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = arena.match(nets[0], nets[1], 1)
+        torch.cuda.synchronize()
+        return res, time.perf_counter() - t0, start, rep
+
+    if a.record is not None:
+        say(f"arena_time --record {a.record}: Arena.match greedy against greedy, 11x11, 4 snakes (1 v 3), {a.blocks}-block Glorot nets, "
+            f"{a.pairs} alternating pairs per size, {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), "
+            f"ROCm / HIP {torch.version.hip}, torch {torch.__version__}")
+        match(64, None, 0)                                 # first launches, plans and range-guard scales settle outside the timing
+        match(64, None, min(a.record, 64))
+        for n in a.games:
+            start, per = None, {"plain": [], "recorded": []}
+            for k in range(a.pairs):
+                won = {}
+                for form, record in (("plain", 0), ("recorded", a.record)):
+                    res, dt, start, rep = match(n, start, record)
+                    won[form] = res.winners.tolist()
+                    per[form].append(dt / res.turns * 1e3)
+                    say(f"games {n:5d} pair {k} {form:8s}: {res.turns:4d} turns, {dt:7.3f} s, {dt / res.turns * 1e3:8.3f} ms per turn")
+                    if rep is not None:
+                        ok = all(len(rep.frames(g)) == 2 * res.lengths[g] for g in rep.games.tolist())
+                        say(f"games {n:5d} pair {k} recorded {len(rep.games)} games, the log doubled {rep.grown} times, frame counts right: {ok}")
+                say(f"games {n:5d} pair {k} winners identical: {won['plain'] == won['recorded']}")
+            p, r = statistics.median(per["plain"]), statistics.median(per["recorded"])
+            say(f"games {n:5d} median ms per turn: plain {p:.3f}, recorded {r:.3f}, added {(r - p) * 1e3:.1f} us per turn")
+        write_log()
+        return
+
     _, _, _, _ = play("run_device", 64, None)              # first launches, plans and range-guard scales settle outside the timing
     _, _, _, _ = play("run", 64, None)
     for n in a.games:
@@ -75,10 +123,7 @@ def main():
             say(f"games {n:5d} pair {k} winners identical: {same}")
         h, d = statistics.median(per["run"]), statistics.median(per["run_device"])
         say(f"games {n:5d} median ms per turn: run {h:.3f}, run_device {d:.3f}, ratio {h / d:.2f}x")
-    if a.log:
-        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
-        with open(a.log, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    write_log()
 
 
 if __name__ == "__main__":

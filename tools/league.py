@@ -3,6 +3,7 @@ ratings of a round robin, 11x11.
 
     python tools/league.py [--nets 6] [--games 300] [--seats duel|1v3|ffa] [--blocks 4] [--models NAME G0 G1 ...] [--seed 1]
                            [--search B [--depth 8]] [--time] [--pairs 3] [--log profiles/league_ab.log] [--baseline [FLAGS ...]]
+                           [--replay K DIR]
 
 --nets K plays generation-0 Glorot nets of --blocks blocks, seeds 1..K; --models NAME G0 G1 ... loads NAME<G>.h5 instead (e.g.
 --models models/gen 0 15 30).  Every line-up of snake_engine.league.schedule plays --games games, all in lock step in one engine.
@@ -15,7 +16,9 @@ League.play_search against one Arena.match of two Searchers per ordered pair); t
 of the searches (Searcher.stats) and, since a searching turn is bound by them, the microseconds per evaluation.
 --baseline [FLAGS ...]: scripted owners (snake_engine.arena.Scripted, the fixed yardstick: the same opponent in every run) join the
 table and the ratings behind the nets, one per FLAGS value (bits 1 space, 2 heads, 4 food; no value: 7, the whole policy).  A
-scripted owner moves by its script under --search too.  --nets 0 --baseline 0 1 3 7 is the round robin of four flag settings."""
+scripted owner moves by its script under --search too.  --nets 0 --baseline 0 1 3 7 is the round robin of four flag settings.
+--replay K DIR (not with --time): the round robin records its first K games (League.record) and writes them as DIR/game_<g>.rep,
+the text of the reference's replay.rep: two boards per tick."""
 import argparse
 import os
 import statistics
@@ -53,6 +56,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--log", default=None)
     ap.add_argument("--baseline", nargs="*", type=int, default=None, metavar="FLAGS")
+    ap.add_argument("--replay", nargs=2, default=None, metavar=("K", "DIR"))
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -106,15 +110,22 @@ def main():
         f"torch {torch.__version__}" + (f"; every seat searches, breadth {a.search}, depth {a.depth}" if a.search else ""))
     search = dict(breadth=a.search, depth=a.depth) if a.search else None
 
-    def league_form(seed):
-        """one League.play (play_search) of every line-up -> (result, seconds, rows evaluated, the searches' net evaluations)"""
+    def league_form(seed, replay=None):
+        """one League.play (play_search) of every line-up -> (result, seconds, rows evaluated, the searches' net evaluations);
+        replay: (K, DIR), the first K games are recorded and written when the match is over"""
         Counted.rows = 0
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         league = League(11, 11, S, 1, len(owner), seed)                     # both forms pay for their engines inside the clock
         sides = searchers(nets, search, seed) if search else nets           # ... and for their searchers' tables
+        rep = league.record(range(min(int(replay[0]), len(owner)))) if replay else None
         res = league.play_search(sides, owner) if search else league.play(nets, owner)
         torch.cuda.synchronize()
+        if rep is not None:
+            os.makedirs(replay[1], exist_ok=True)
+            for g in rep.games.tolist():
+                rep.write(g, os.path.join(replay[1], f"game_{g}.rep"), append=False)
+            say(f"replay: games 0..{len(rep.games) - 1} written to {replay[1]}/game_<g>.rep")
         return res, time.perf_counter() - t0, Counted.rows, sum(s.stats["net_evals"] for s in sides if isinstance(s, Searcher)) if search else 0
 
     def arena_form(seed):
@@ -160,7 +171,7 @@ def main():
         say(f"time: median seconds: league form {ml:.3f} (min {min(per['league']):.3f}, max {max(per['league']):.3f}), arena form "
             f"{ma:.3f} (min {min(per['arena']):.3f}, max {max(per['arena']):.3f}), ratio of medians arena / league {ma / ml:.2f}x")
         return
-    res, dt, _, _ = league_form(a.seed)
+    res, dt, _, _ = league_form(a.seed, a.replay)
     t = table(res, owner, K)
     say(f"{res.turns} turns, {dt:.3f} s, {dt / res.turns * 1e3:.3f} ms per turn; wins of the row's net over the column's / draws")
     for line in format_table(names, t, ratings(t.wins, t.draws)):

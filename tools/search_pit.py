@@ -2,7 +2,7 @@
 (snake_engine.arena.Searcher) and a greedy side of the SAME net, 11x11.
 
     python tools/search_pit.py [--games 300] [--breadth 16] [--depth 8] [--blocks 4] [--weights CKPT] [--seed 1]
-                               [--time] [--pairs 2] [--log profiles/arena_search.log] [--baseline]
+                               [--time] [--pairs 2] [--log profiles/arena_search.log] [--baseline] [--replay K DIR]
 
 Strength (default): 1 v 3 with the searcher alone, 1 v 3 with the searcher's three against the greedy one, and the duel; win and
 draw rates of the searching side with their binomial 95 % intervals (Wilson), ms per turn and net evaluations per turn.
@@ -12,6 +12,8 @@ turn, and the host time DeviceMCTS._ensure took (its buffers are made again when
 --baseline: the net against the scripted opponent (snake_engine.arena.Scripted with the whole policy, the fixed yardstick) instead
 of against itself: the greedy net in the duel and in 1 v 3 both ways, then the net moving by search in the duel; the net side's
 win and draw rates with the same intervals.
+--replay K DIR: the first match the run reports (strength or --baseline) records its first K games (Arena.record) and writes them
+as DIR/game_<g>.rep, the text of the reference's replay.rep: two boards per tick.
 The lines are appended to --log behind a line that names the device."""
 import argparse
 import math
@@ -47,6 +49,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=2)
     ap.add_argument("--log", default=None)
     ap.add_argument("--baseline", action="store_true")
+    ap.add_argument("--replay", nargs=2, default=None, metavar=("K", "DIR"))
     a = ap.parse_args()
     import torch
     from snake_engine.arena import Arena, Scripted, Searcher
@@ -83,7 +86,21 @@ def main():
         return out
     DeviceMCTS._ensure = timed_ensure
 
-    def play(snakes, a_cnt, searching, breadth, seed, start=None):
+    pending = [a.replay]
+
+    def recorder(arena):
+        """the Replay of the first reported match, None for every later one"""
+        want, pending[0] = pending[0], None
+        return None if want is None else arena.record(range(min(int(want[0]), arena.game_cnt)))
+
+    def write_replay(rep):
+        if rep is not None:
+            os.makedirs(a.replay[1], exist_ok=True)
+            for g in rep.games.tolist():
+                rep.write(g, os.path.join(a.replay[1], f"game_{g}.rep"), append=False)
+            say(f"replay: games 0..{len(rep.games) - 1} of this match written to {a.replay[1]}/game_<g>.rep")
+
+    def play(snakes, a_cnt, searching, breadth, seed, start=None, record=False):
         """one match; searching: which sides move by search -> (result, seconds, net evaluations of the searchers, start boards)"""
         arena = Arena(11, 11, snakes, 1, a.games, seed)
         if start is None:
@@ -91,12 +108,14 @@ def main():
         else:
             arena.import_states(start)
         sides = [Searcher(net, breadth, a.depth, seed=seed + 11 * k) if s else net for k, s in enumerate(searching)]
+        rep = recorder(arena) if record else None
         ensure_s[0] = 0.0
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         res = arena.match(sides[0], sides[1], a_cnt)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        write_replay(rep)
         evals = sum(s.stats["net_evals"] for s in sides if isinstance(s, Searcher))
         return res, dt, evals, start
 
@@ -109,11 +128,14 @@ def main():
         for mover, breadth, ups in movers:
             for i, (name, snakes, a_cnt, who) in enumerate(ups):
                 side = net if breadth is None else Searcher(net, breadth, a.depth, seed=a.seed + 11)
+                arena = Arena(11, 11, snakes, 1, a.games, a.seed + i)
+                rep = recorder(arena)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                res = Arena(11, 11, snakes, 1, a.games, a.seed + i).match(side, script, a_cnt)
+                res = arena.match(side, script, a_cnt)
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
+                write_replay(rep)
                 wins = (res.wins_a, res.wins_b)[who]
                 (wl, wh), (dl, dh) = wilson(wins, a.games), wilson(res.draws, a.games)
                 say(f"baseline: {mover} against the script, {name}: net wins {wins / a.games:.3f} [{wl:.3f}, {wh:.3f}], draws "
@@ -136,7 +158,7 @@ def main():
             seats = [("1v3, the searcher alone", 4, 1, (True, False), 0), ("1v3, three searchers against one", 4, 1, (False, True), 1),
                      ("duel, the searcher first", 2, 1, (True, False), 0)]
             for i, (name, snakes, a_cnt, searching, who) in enumerate(seats):
-                res, dt, evals, _ = play(snakes, a_cnt, searching, breadth, a.seed + i)
+                res, dt, evals, _ = play(snakes, a_cnt, searching, breadth, a.seed + i, record=True)
                 wins = (res.wins_a, res.wins_b)[who]
                 (wl, wh), (dl, dh) = wilson(wins, a.games), wilson(res.draws, a.games)
                 say(f"strength: breadth {breadth:3d} {name}: search wins {wins / a.games:.3f} [{wl:.3f}, {wh:.3f}], draws "
