@@ -1,50 +1,50 @@
-"""Arena: whole pit matches on the device -- the reference's pit loop (pit_mp_game_runner.py:14-63) with two greedy agents
-(pit_agent.py:10-28) as a fixed sequence of launches per turn and ONE host read-back per turn.
+"""Arena: whole pit matches on the device -- the reference's pit loop (pit_mp_game_runner.py:14-63) with greedy agents
+(pit_agent.py:10-28) as a fixed sequence of launches per turn and ONE host read-back per turn.  ``League`` (snake_engine/league.py)
+plays the same turn with an owner per seat instead of two teams; the turn itself stands once, in ``_Pit._play``:
 
-A turn of ``Arena.match``:
-
-    snk_pit_rows                  (slot, snake id) of every alive snake of every open game, team A first   (:23-35)
-    the turn's read-back          the two row counts: they size the two net batches
-    snk_engine_observe            one launch over the rows                                                 (:28)
-    alice.v_device / bob.v_device rows [0, nA) and [nA, nA + nB)                                           (:34)
-    snk_pit_moves                 greedy moves into the dense move array                                   (:36-38)
-    snk_engine_step_active_tape   open games move, games whose verdict is in stay as they are              (:42)
+    the seating's lists           (slot, snake id) of every alive snake of every open game, bucketed by greedy side (:23-35);
+                                  with a searching side also the open games a searcher plays: the slots, their alive rows, and
+                                  where a seat finds its game in that list
+    the turn's read-back          the counts that size the batches, one tensor, one .tolist(); nothing left ends the match
+    the greedy sides              ``mixed_values``: snk_engine_observe over the nets' rows (:28), each net on its own slice (:34),
+                                  a Scripted side's slice scored by snk_pit_script_values; then ONE snk_pit_moves: greedy moves
+                                  into the dense move array, which it first fills with 1                              (:36-38)
+    searcher.search, end_of_turn  each searching side in order, on its games; then the seating's merge launch puts the moves a
+                                  searcher found for its own seats into the dense move array
+    snk_engine_step_active_tape   open games move, games whose verdict is in stay as they are                         (:42)
     snk_engine_rewards
-    snk_pit_verdict               winners, game lengths, the open flags                                    (:43-62)
+    the seating's verdict         winners, game lengths, the open flags                                               (:43-62)
 
 There is no per-game Python loop and nothing else comes back to the host until the match is over.  The host loop of
 ``utils.pit_mp_game_runner.MPGameRunner.run`` (four synchronising copies, ``np.nonzero`` and a Python loop over the games each
-turn) stays as the parity-pinned form; ``MPGameRunner.run_device`` is this one behind the same interface.
+turn) stays as the parity-pinned form; ``MPGameRunner.run_device`` is ``Arena.match`` behind the same interface.
 
-Either side may instead be a ``Searcher``: it moves the way ``Agent(nnet, training=False).make_moves`` moves (agent.py:25-99), by a
-``DeviceMCTS.search`` over the open games.  A turn with at least one searching side:
+The seating is three hooks of the subclass: ``_lists`` (the list launches and the read-back), ``_merge`` and ``_verdict``; a
+fourth, ``_result``, reads the match's result back.  The arena's seating is the reference's: snakes 0 .. a_cnt-1 are team A's.
 
-    snk_pit_roots                 the open slots ascending, their alive rows, each slot's rank in that list, the count G
-    snk_pit_rows                  only when one side is greedy
-    the turn's read-back          G and the two row counts, one tensor, one .tolist(); G = 0 ends the match
-    the greedy side               observe + its net on its own rows, snk_pit_moves over those rows (the array is filled with 1)
-    searcher.search, end_of_turn  team A's searcher first; each simulates all snakes of the open games with its own net and
-                                  only its own team's columns of the root moves are used
-    snk_pit_search_moves          merges them into the dense move array
-    step, rewards, verdict        as above
+    _lists    snk_pit_rows: the row list, team A first, and the two row counts {nA, nB} -- the read-back of a match without a
+              Searcher.  With one: snk_pit_roots (the open slots ascending, their alive rows, each slot's rank in that list, the
+              count G), then snk_pit_rows only when one side is greedy -- it still lists both teams, the greedy team's slice is
+              used --, and the read-back is {nA, nB, G}.  Every searching side gets all G open games; G = 0 ends the match
+    _merge    snk_pit_search_moves: only its own team's columns of a searcher's root moves are used
+    _verdict  snk_pit_verdict
 
-The arena's own read-back stays one per turn.  The search reads back on its own, and those are not the arena's: the largest root
-depth once per turn, the number of new keys once per rollout tick (it sizes the net batch), the table status after every epoch but
-the last and at the end of the turn together with the turn's sub-game tick counter; a taped (parity) search also reads its row
-counts.  A guarded net is calibrated once, on the first turn's root observations.
+A side is anything with ``v_device``, or a ``Searcher`` around one: it moves the way ``Agent(nnet, training=False).make_moves``
+moves (agent.py:25-99), by a ``DeviceMCTS.search`` that simulates all snakes of its games with its own net.  The search reads back
+on its own, and those are not the pit's: the largest root depth once per turn, the number of new keys once per rollout tick (it
+sizes the net batch), the table status after every epoch but the last and at the end of the turn together with the turn's
+sub-game tick counter; a taped (parity) search also reads its row counts.  A guarded net is calibrated once, on the first turn's
+root observations.
 
-Either side may also be a ``Scripted``: the flood-fill heuristic snake every Battlesnake project keeps as its fixed point (the
-project's own policy -- the reference has none; include/snake_engine.h states it, tests/script_ref.py restates it in plain
-Python).  It costs no weights and is the same opponent in every run.  Its rows are scored from the compact game records by
-snk_pit_script_values, and snk_pit_moves turns the scores into moves as it does a net's values; the observe launch and the net
-then run over the other side's rows only (the row list is team A first, so both are contiguous slices), and ``Scripted`` against
-``Scripted`` launches neither.  The turn's read-back stays the one it is.  A match without a ``Scripted`` issues exactly the
-launches it issued before there was one.
+Or a side is a ``Scripted``: the flood-fill heuristic snake every Battlesnake project keeps as its fixed point (the project's own
+policy -- the reference has none; include/snake_engine.h states it, tests/script_ref.py restates it in plain Python).  It costs no
+weights and is the same opponent in every run.  It counts as a greedy side; the observe launch and the nets run over the other
+sides' rows only (one observe per run of consecutive nets), and ``Scripted`` against ``Scripted`` launches neither.
 
-``Arena.record(games)`` returns a ``replay.Replay`` that the next match fills with the boards Game.tic(show=True) draws for those
-games (game.py:140-141, 194-195): snk_pit_record_moves before the step and snk_pit_record_boards after it draw them into a log on
-the device, which is copied to the host once, after the last turn (``Replay`` below; snake_engine/replay.py names it).  The turn's read-back stays the one
-it is, and a match without a recorder issues exactly the launches and read-backs it issued before there was one.
+``record(games)`` returns a ``replay.Replay`` that the next match fills with the boards Game.tic(show=True) draws for those games
+(game.py:140-141, 194-195): snk_pit_record_moves before the step and snk_pit_record_boards after it draw them into a log on the
+device, which is copied to the host once, after the last turn (``Replay`` below; snake_engine/replay.py names it).  The turn's
+read-back stays the one it is, and a match without a recorder issues no launch and no read-back for one.
 """
 from collections import namedtuple
 
@@ -145,8 +145,9 @@ class Scripted:
 
 
 def mixed_values(eng, sides, rows, pairs):
-    """the values float32[sum(rows)][3] of a row list in which side o moves the next rows[o] rows and some side is Scripted: a
-    Scripted side's slice is scored by the kernel; every run of consecutive nets shares one observe launch over its rows only"""
+    """the values float32[sum(rows)][3] of a row list in which side o (a net or a Scripted) moves the next rows[o] rows, at least
+    one row in all: a Scripted side's slice is scored by the kernel; every run of consecutive nets shares one observe launch
+    over its rows only, and each net with rows runs on its own slice"""
     parts, lo, o, K = [], 0, 0, len(sides)
     while o < K:
         if isinstance(sides[o], Scripted):
@@ -271,9 +272,17 @@ def frames_text(frames):
     return b"".join(board_text(fr) for fr in np.asarray(frames))
 
 
-class Arena:
+class _Pit:
+    """what Arena and League share: the engine and the match's buffers, the recorder, and the one turn loop.  A subclass seats
+    the sides by four hooks, each handed the `seat` its own match method made:
+        _lists(L, seat)              -> (rows, pairs, games, read, over): rows[i] rows for the i-th greedy side, one after another
+                                        in `pairs`; games: (o, slots, alive) for every searching side o that plays this turn;
+                                        read: what the turn's one read-back brought; over: nothing is left
+        _merge(L, seat, found, keep)    found[o]: the root moves of searching side o, or None; keep: some side is greedy
+        _verdict(L, seat, turn)
+        _result(seat, turns)         -> the match's result tuple; it has .lengths"""
 
-    def __init__(self, height=11, width=11, snake_cnt=4, health_dec=1, game_cnt=1, seed=None):
+    def __init__(self, height, width, snake_cnt, health_dec, game_cnt, seed):
         if seed is None:
             seed = int(np.random.randint(1 << 62))
         engine = Engine(game_cnt, height, width, snake_cnt, health_dec, 0.15, seed=seed)
@@ -288,26 +297,24 @@ class Arena:
         n, S = eng.n_slots, eng.S
         self._live = eng.new((n,), torch.uint8)
         self._pairs = eng.new((n * S, 2), torch.int32)
-        self._counts = eng.new((2,), torch.int32)
-        self._scratch = eng.new((eng.L.snk_pit_scratch_elems(n),), torch.int32)
         self._moves = eng.new((n, S), torch.uint8)
         self._done = eng.new((n,), torch.uint8)
         self._rewards = eng.new((n, S), torch.int8)
         self._winner = eng.new((n,), torch.int32)
         self._length = eng.new((n,), torch.int32)
         self._roots = None                        # the searching turn's buffers, made by the first match that searches
-        self._recorder = self._rec = None         # the Replay the next match fills / the one the running match is filling
+        self._recorder = None                     # the Replay the next match fills
 
     def record(self, games, first_turns=64):
         """games: distinct game indices in any order (an index out of range or given twice is a ValueError, before anything
-        touches the device).  Returns the Replay the next match on this arena fills; the recorder is dropped when that match
-        ends.  first_turns: the turns the log on the device is first sized for (it doubles as the match goes on)."""
+        touches the device).  Returns the Replay the next match fills; the recorder is dropped when that match ends.
+        first_turns: the turns the log on the device is first sized for (it doubles as the match goes on)."""
         self._recorder = Replay(games, self.height, self.width, self.game_cnt, first_turns)
         return self._recorder
 
     @classmethod
     def from_engine(cls, engine):
-        """an arena over the games an engine already holds (slots 0..n_slots-1), e.g. a game runner's"""
+        """a pit over the games an engine already holds (slots 0..n_slots-1), e.g. a game runner's"""
         self = cls.__new__(cls)
         self._attach(engine)
         return self
@@ -317,11 +324,80 @@ class Arena:
         self.engine.import_states(states)
         self._fresh = True
 
+    def _play(self, sides, seat, init_tape, spawn_tape, counts_log=None):
+        """one match of the checked `sides` -> the subclass's result.  init_tape: without one the match plays on the boards the
+        pit holds -- fresh ones are drawn on the device when a match has already been played on them"""
+        eng, n, S = self.engine, self.game_cnt, self.snake_cnt
+        L = eng.L                                 # looked up now: a test may have put a recording proxy there
+        live, moves = self._live, self._moves
+        greedy = [side for side in sides if not isinstance(side, Searcher)]
+        searching = len(greedy) < len(sides)
+        rec, self._recorder = self._recorder, None        # held here only: a match that raises has dropped it too
+        if init_tape is not None:
+            eng.reset(init_tape=init_tape)
+        elif not self._fresh:
+            eng.reset()
+        self._fresh = False
+        live.fill_(1)
+        self._winner.fill_(-1)
+        self._length.zero_()
+        if rec is not None:
+            rec.begin(eng)
+        turn = 0
+        while True:
+            rows, pairs, games, read, over = self._lists(L, seat)
+            if over:
+                break
+            turn += 1
+            if counts_log is not None:
+                counts_log.append(read)
+            if greedy:                            # with no row left it still fills the dense array with 1, for the merge
+                m = sum(rows)
+                q = mixed_values(eng, greedy, rows, pairs) if m else None
+                check(L.snk_pit_moves(_ptr(q), _ptr(pairs), m, n, S, _ptr(moves), _stream()))
+            if searching:
+                found = [None] * len(sides)
+                for o, slots, alive in games:     # team A's or owner 0's searcher first
+                    G = int(slots.shape[0])
+                    found[o] = sides[o].search(eng, slots, alive).contiguous()
+                    if found[o].dtype != torch.uint8 or tuple(found[o].shape) != (G, S):
+                        raise EngineError(f"search returned {found[o].dtype} {tuple(found[o].shape)} for {G} games of {S} snakes")
+                    sides[o].end_of_turn()
+                self._merge(L, seat, found, int(bool(greedy)))
+            # the dense moves are in: open games move, games whose verdict is in stay as they are, then the turn's verdict
+            tape = None
+            if spawn_tape is not None:
+                tape = torch.as_tensor(np.ascontiguousarray(spawn_tape(turn), np.int16), device=eng.device)
+                if tape.numel() != n:
+                    raise ValueError(f"spawn_tape({turn}) has {tape.numel()} entries for {n} games")
+            if rec is not None:                   # the mid-tick snakes, from the records the step is about to change
+                rec.before_step(eng, turn, live, moves)
+            check(L.snk_engine_step_active_tape(eng.h, _ptr(live), n, _ptr(moves), _ptr(tape), _ptr(self._done), None, _stream()))
+            if rec is not None:                   # by the live flags the step saw: before the verdict clears them
+                rec.after_step(eng, turn, live)
+            check(L.snk_engine_rewards(eng.h, None, n, _ptr(self._rewards), _stream()))
+            self._verdict(L, seat, turn)
+        result = self._result(seat, turn)
+        if rec is not None:
+            rec.end(turn, result.lengths)         # the log's one copy, after the last turn
+        return result
+
+
+class Arena(_Pit):
+
+    def __init__(self, height=11, width=11, snake_cnt=4, health_dec=1, game_cnt=1, seed=None):
+        super().__init__(height, width, snake_cnt, health_dec, game_cnt, seed)
+
+    def _attach(self, engine):
+        super()._attach(engine)
+        self._counts = engine.new((2,), torch.int32)
+        self._scratch = engine.new((engine.L.snk_pit_scratch_elems(engine.n_slots),), torch.int32)
+
     # ---- one match -------------------------------------------------------------------------------------------------------
     def match(self, alice, bob, alice_snake_cnt=None, init_tape=None, spawn_tape=None):
         """alice, bob: anything with v_device(planes, mask) -> float32[rows][3] on the device (AlphaNNet: its guarded forward),
-        a Searcher around one, or a Scripted; every combination is allowed.  With a Searcher the turn is the second one of the module's
-        docstring: the arena still reads back once per turn (G and the two row counts), the searches read back on their own.
+        a Searcher around one, or a Scripted; every combination is allowed.  With a Searcher the arena still reads back once per
+        turn (G and the two row counts), the searches read back on their own.
         alice_snake_cnt: snakes 0 .. alice_snake_cnt-1 are alice's (default snake_cnt // 2, pit_mp_game_runner.py:17-18).
         init_tape: uint8[game_cnt][3][snake_cnt] recorded start draws (snk_engine_reset); without one the match plays on the
         boards the arena holds -- fresh ones are drawn on the device when a match has already been played on them.
@@ -335,129 +411,52 @@ class Arena:
         for net in (alice, bob):
             if not isinstance(net, (Searcher, Scripted)) and not hasattr(net, "v_device"):
                 raise TypeError(f"{type(net).__name__} has no v_device(planes, mask): the arena evaluates on the device only")
-        if init_tape is not None:
-            eng.reset(init_tape=init_tape)
-        elif not self._fresh:
-            eng.reset()
-        self._fresh = False
-        self._live.fill_(1)
-        self._winner.fill_(-1)
-        self._length.zero_()
-        rec, self._recorder = self._recorder, None
-        if rec is not None:
-            rec.begin(eng)
-        self._rec = rec
-        try:
-            if isinstance(alice, Searcher) or isinstance(bob, Searcher):
-                turn = self._search_turns(alice, bob, a_cnt, spawn_tape)
-            else:
-                turn = self._greedy_turns(alice, bob, a_cnt, spawn_tape)
-        finally:
-            self._rec = None
-        winners = self._winner.cpu().numpy()
-        lengths = self._length.cpu().numpy()
-        if rec is not None:
-            rec.end(turn, lengths)                # the log's one copy, after the last turn
-        wins_a = int(((winners >= 0) & (winners < a_cnt)).sum())
-        wins_b = int((winners >= a_cnt).sum())
-        return ArenaResult(winners, lengths, turn, wins_a, wins_b, n - wins_a - wins_b)
-
-    def _greedy_turns(self, alice, bob, a_cnt, spawn_tape):
-        """the turns of a match between two nets (either may be a Scripted) -> turns played"""
-        eng, n, S = self.engine, self.game_cnt, self.snake_cnt
-        L = eng.L
-        live, pairs, counts, moves = self._live, self._pairs, self._counts, self._moves
-        scripted = isinstance(alice, Scripted) or isinstance(bob, Scripted)
-        turn = 0
-        while True:
-            check(L.snk_pit_rows(eng.h, _ptr(live), n, a_cnt, _ptr(pairs), _ptr(counts), _ptr(self._scratch), _stream()))
-            nA, nB = counts.tolist()              # the turn's one read-back
-            m = nA + nB
-            if m == 0:
-                break
-            turn += 1
-            if scripted:                          # the kernel scores the scripted rows; observe and net on the other side's only
-                q = mixed_values(eng, (alice, bob), (nA, nB), pairs)
-            else:
-                planes, mask, _ = eng.observe_all(pairs[:m], want_key=False)
-                q = self._values(alice, bob, planes, mask, nA, m)
-            check(L.snk_pit_moves(_ptr(q), _ptr(pairs), m, n, S, _ptr(moves), _stream()))
-            self._tick(turn, a_cnt, spawn_tape)
-        return turn
-
-    def _tick(self, turn, a_cnt, spawn_tape):
-        """the dense moves are in: open games move, games whose verdict is in stay as they are, then the turn's verdict"""
-        eng, n, live = self.engine, self.game_cnt, self._live
-        L = eng.L
-        tape = None
-        if spawn_tape is not None:
-            tape = torch.as_tensor(np.ascontiguousarray(spawn_tape(turn), np.int16), device=eng.device)
-            if tape.numel() != n:
-                raise ValueError(f"spawn_tape({turn}) has {tape.numel()} entries for {n} games")
-        rec = self._rec
-        if rec is not None:                       # the mid-tick snakes, from the records the step is about to change
-            rec.before_step(eng, turn, live, self._moves)
-        check(L.snk_engine_step_active_tape(eng.h, _ptr(live), n, _ptr(self._moves), _ptr(tape), _ptr(self._done), None, _stream()))
-        if rec is not None:                       # by the live flags the step saw: before the verdict clears them
-            rec.after_step(eng, turn, live)
-        check(L.snk_engine_rewards(eng.h, None, n, _ptr(self._rewards), _stream()))
-        check(L.snk_pit_verdict(eng.h, _ptr(self._done), _ptr(self._rewards), n, a_cnt, turn, _ptr(live), _ptr(self._winner),
-                                _ptr(self._length), _stream()))
-
-    def _search_turns(self, alice, bob, a_cnt, spawn_tape):
-        """the turns of a match in which at least one side is a Searcher -> turns played"""
-        eng, n, S = self.engine, self.game_cnt, self.snake_cnt
-        L = eng.L
-        live, pairs, moves = self._live, self._pairs, self._moves
-        if self._roots is None:
-            self._roots = (eng.new((n,), torch.int32), eng.new((n, S), torch.uint8), eng.new((n,), torch.int32),
-                           eng.new((3,), torch.int32))
-        slots, alive, rank, counts = self._roots              # counts: {nA, nB, G}
-        counts.zero_()
         greedy = [not isinstance(side, Searcher) for side in (alice, bob)]
-        turn = 0
-        while True:
+        roots = None
+        if not all(greedy):
+            if self._roots is None:
+                self._roots = (eng.new((n,), torch.int32), eng.new((n, S), torch.uint8), eng.new((n,), torch.int32),
+                               eng.new((3,), torch.int32))
+            roots = self._roots                   # slots, alive, rank, counts {nA, nB, G}
+            roots[3].zero_()
+        return self._play((alice, bob), (a_cnt, greedy, roots), init_tape, spawn_tape)
+
+    def _lists(self, L, seat):
+        eng, n, live, pairs = self.engine, self.game_cnt, self._live, self._pairs
+        a_cnt, greedy, roots = seat
+        counts = self._counts if roots is None else roots[3]
+        if roots is not None:
+            slots, alive, rank, _ = roots
             check(L.snk_pit_roots(eng.h, _ptr(live), n, _ptr(slots), _ptr(alive), _ptr(rank), _ptr(counts[2:]), _ptr(self._scratch),
                                   _stream()))
-            if any(greedy):
-                check(L.snk_pit_rows(eng.h, _ptr(live), n, a_cnt, _ptr(pairs), _ptr(counts), _ptr(self._scratch), _stream()))
-            nA, nB, G = counts.tolist()           # the turn's one read-back
-            if G == 0:
-                break
-            turn += 1
-            if any(greedy):                       # the greedy side's net on its own rows; the array is filled with 1
-                lo, hi, net = (0, nA, alice) if greedy[0] else (nA, nA + nB, bob)
-                q = None
-                if hi > lo and isinstance(net, Scripted):
-                    q = net.q_rows(eng, pairs[lo:hi])
-                elif hi > lo:
-                    planes, mask, _ = eng.observe_all(pairs[lo:hi], want_key=False)
-                    q = self._values(net, net, planes, mask, hi - lo, hi - lo)
-                check(L.snk_pit_moves(_ptr(q), _ptr(pairs[lo:hi]), hi - lo, n, S, _ptr(moves), _stream()))
-            found = [None, None]
-            for k, side in enumerate((alice, bob)):       # team A's searcher first
-                if not greedy[k]:
-                    found[k] = side.search(eng, slots[:G], alive[:G]).contiguous()
-                    if found[k].dtype != torch.uint8 or tuple(found[k].shape) != (G, S):
-                        raise EngineError(f"search returned {found[k].dtype} {tuple(found[k].shape)} for {G} games of {S} snakes")
-                    side.end_of_turn()
-            check(L.snk_pit_search_moves(_ptr(found[0]), _ptr(found[1]), _ptr(rank), _ptr(alive), n, S, a_cnt, int(any(greedy)),
-                                         _ptr(moves), _stream()))
-            self._tick(turn, a_cnt, spawn_tape)
-        return turn
+        if any(greedy):
+            check(L.snk_pit_rows(eng.h, _ptr(live), n, a_cnt, _ptr(pairs), _ptr(counts), _ptr(self._scratch), _stream()))
+        read = counts.tolist()                    # the turn's one read-back
+        nA, nB = read[:2]
+        rows = [cnt for cnt, g in zip((nA, nB), greedy) if g]
+        lo = 0 if greedy[0] else nA               # team A's rows come first
+        mine = pairs[lo:lo + sum(rows)]
+        if roots is None:
+            return rows, mine, [], read, nA + nB == 0
+        G = read[2]                               # every searching side gets all open games
+        return rows, mine, [(o, slots[:G], alive[:G]) for o in (0, 1) if not greedy[o]], read, G == 0
 
-    @staticmethod
-    def _values(alice, bob, planes, mask, nA, m):
-        """the two nets on their rows: float32[m][3], team A's rows first"""
-        parts = []
-        if nA:
-            parts.append(alice.v_device(planes[:nA], mask[:nA]))
-        if m > nA:
-            parts.append(bob.v_device(planes[nA:m], mask[nA:m]))
-        q = parts[0] if len(parts) == 1 else torch.cat(parts)
-        if q.dtype != torch.float32 or tuple(q.shape) != (m, 3) or not q.is_cuda:
-            raise EngineError(f"v_device returned {q.dtype} {tuple(q.shape)} on {q.device} for {m} rows: float32 [rows][3] on the device expected")
-        return q.contiguous()
+    def _merge(self, L, seat, found, keep):
+        a_cnt, _, (_, alive, rank, _) = seat
+        check(L.snk_pit_search_moves(_ptr(found[0]), _ptr(found[1]), _ptr(rank), _ptr(alive), self.game_cnt, self.snake_cnt, a_cnt,
+                                     keep, _ptr(self._moves), _stream()))
+
+    def _verdict(self, L, seat, turn):
+        check(L.snk_pit_verdict(self.engine.h, _ptr(self._done), _ptr(self._rewards), self.game_cnt, seat[0], turn, _ptr(self._live),
+                                _ptr(self._winner), _ptr(self._length), _stream()))
+
+    def _result(self, seat, turns):
+        a_cnt = seat[0]
+        winners = self._winner.cpu().numpy()
+        lengths = self._length.cpu().numpy()
+        wins_a = int(((winners >= 0) & (winners < a_cnt)).sum())
+        wins_b = int((winners >= a_cnt).sum())
+        return ArenaResult(winners, lengths, turns, wins_a, wins_b, self.game_cnt - wins_a - wins_b)
 
     # ---- the reference's two judges ------------------------------------------------------------------------------------------
     @staticmethod

@@ -1,54 +1,33 @@
-"""League: up to sixteen nets in ONE device pit match -- the arena's loop (snake_engine/arena.py, pit_mp_game_runner.py:14-63) with
-the team split `id < Alice_snake_cnt` replaced by a table owner[game][seat] with values 0 .. K-1.
+"""League: up to sixteen sides in ONE device pit match -- the pit's turn (snake_engine/arena.py states it, once; pit_mp_game_runner.py:
+14-63) with the team split `id < Alice_snake_cnt` replaced by a table owner[game][seat] with values 0 .. K-1.  What the table
+changes is the seating, the three hooks the turn loop calls:
 
-A turn of ``League.play``:
+    _lists    snk_pit_rows_owned: the row list bucketed by owner, owner 0's rows first, and the K row counts -- the read-back of
+              ``play``; a total of 0 ends the match.  With a Searcher (``play_search``; ``play`` itself keeps refusing one) first
+              snk_pit_roots_owned: a searcher simulates whole games, so each turn it gets the open games in which it holds a seat
+              with an alive snake -- the lists one after another in owner order, the alive rows of those games, and per seat
+              the row of the list it reads.  Then snk_pit_rows_owned only when some owner is greedy, over a second table made once
+              per match: the searching owners' bytes out of range, the greedy owners renumbered densely, so their rows are
+              contiguous.  The read-back is the greedy row counts, then the K game counts (0 for a greedy owner); all zeros ends
+              the match, and a searcher without a game is skipped, for good
+    _merge    snk_pit_search_moves_owned: the found moves, one array in owner order, into the dense move array by list row
+    _verdict  snk_pit_verdict_owned: a game is over when it is done or at most one owner has snakes left; the winner's owner
+              beside the winner
 
-    snk_pit_rows_owned            (slot, snake id) of every alive snake of every open game, owner 0's rows first      (:23-35)
-    the turn's read-back          the K row counts in one .tolist(): they size the net batches; total 0 ends the match
-    snk_engine_observe            one launch over all rows                                                            (:28)
-    nets[o].v_device              each owner with rows on its own slice, in owner order; an owner without rows is skipped (:34)
-    snk_pit_moves                 greedy moves into the dense move array                                              (:36-38)
-    snk_engine_step_active_tape   open games move, games whose verdict is in stay as they are                         (:42)
-    snk_engine_rewards
-    snk_pit_verdict_owned         a game is over when it is done or at most one owner has snakes left                 (:43-62)
-
-With two nets and owner[g][s] = (s >= a_cnt) every launch and every batch is what ``Arena.match`` issues, so the winners, lengths
-and turns are the same bit for bit.  What the table adds: a free-for-all in which every seat belongs to another net, and every
-pairing of a round robin in lock step in one engine (``schedule``, ``round_robin``), scored by ``table`` and ``ratings``.
-
-Any owner may instead be an ``arena.Searcher`` (``League.play_search``; ``play`` itself keeps refusing one): a searcher simulates
-whole games, so each turn it gets the sub-list of open games in which it holds a seat -- a game that is open, with an alive snake
-whose seat is the owner's -- and only its own seats take the moves it finds.  A turn of ``League.play_search``:
-
-    snk_pit_roots_owned           per searching owner the open games it holds a seat in, the lists one after another in owner
-                                  order, the alive rows of those games, and per seat the row of the list it reads
-    snk_pit_rows_owned            only when some owner is greedy, over a second table made once per match: the searching owners'
-                                  bytes out of range, the greedy owners renumbered densely, so their rows are contiguous
-    the turn's read-back          the greedy row counts and the K game counts, one tensor, one .tolist(); all zeros ends the match
-    the greedy owners             observe + each net on its own slice, one snk_pit_moves (the array is filled with 1)
-    searcher.search, end_of_turn  in owner order, each on its own slice of the lists; an owner without a game is skipped for good
-    snk_pit_search_moves_owned    merges the found moves into the dense move array
-    step, rewards, verdict        as above
-
-With two Searchers and the two-team table this is ``Arena.match`` with the same Searchers, and with no Searcher it is ``play``.
-The league's own read-back stays one per turn; the searches read back on their own (snake_engine/arena.py).
-
-An owner of either may be an ``arena.Scripted`` (the fixed yardstick of a table: the same opponent in every run): it counts as a
-greedy owner, its slice of the row list is scored by snk_pit_script_values, and the observe launch and the nets run over the
-other owners' rows only -- one observe per run of consecutive net owners.  A match without a ``Scripted`` issues exactly the
-launches it issued before there was one.
-
-``League.record(games)`` is ``Arena.record``: the Replay it returns is filled by the next ``play`` or ``play_search`` with the
-boards of those games (snake_engine/replay.py) -- two more launches per turn, the read-back unchanged, one copy at the end.
+With two sides and owner[g][s] = (s >= a_cnt) every launch and every batch is what ``Arena.match`` issues, with or without
+Searchers, so the winners, lengths and turns are the same bit for bit; without a Searcher ``play_search`` is ``play``.  What the
+table adds: a free-for-all in which every seat belongs to another net, and every pairing of a round robin in lock step in one
+engine (``schedule``, ``round_robin``), scored by ``table`` and ``ratings``.  An ``arena.Scripted`` owner is the fixed yardstick
+of such a table: the same opponent in every run.
 """
 from collections import namedtuple
 
 import numpy as np
 import torch
 
-from ._lib import check, EngineError
-from .arena import Replay, Scripted, Searcher, mixed_values
-from .engine import Engine, _ptr, _stream
+from ._lib import check
+from .arena import _Pit, Scripted, Searcher
+from .engine import _ptr, _stream
 
 MAX_OWNERS = 16          # SNK_PIT_MAX_OWNERS of include/snake_engine.h
 
@@ -63,51 +42,17 @@ of two owners wins + wins.T + draws); score: float64[K] = (wins[a].sum() + draws
 that met nobody"""
 
 
-class League:
+class League(_Pit):
 
     def __init__(self, height=11, width=11, snake_cnt=2, health_dec=1, game_cnt=1, seed=None):
-        if seed is None:
-            seed = int(np.random.randint(1 << 62))
-        engine = Engine(game_cnt, height, width, snake_cnt, health_dec, 0.15, seed=seed)
-        engine.reset()                            # start boards drawn on the device (Philox keyed by the seed and the game's uid)
-        self._attach(engine)
+        super().__init__(height, width, snake_cnt, health_dec, game_cnt, seed)
 
     def _attach(self, engine):
-        eng = self.engine = engine
-        self.height, self.width, self.snake_cnt = eng.H, eng.W, eng.S
-        self.health_dec, self.game_cnt = eng.health_dec, eng.n_slots
-        self._fresh = True                        # the engine holds start boards no match has played on
-        n, S = eng.n_slots, eng.S
-        self._live = eng.new((n,), torch.uint8)
-        self._pairs = eng.new((n * S, 2), torch.int32)
-        self._counts = eng.new((MAX_OWNERS,), torch.int32)
-        self._scratch = eng.new((eng.L.snk_pit_owned_scratch_elems(n, MAX_OWNERS),), torch.int32)
-        self._moves = eng.new((n, S), torch.uint8)
-        self._done = eng.new((n,), torch.uint8)
-        self._rewards = eng.new((n, S), torch.int8)
-        self._winner = eng.new((n,), torch.int32)
-        self._winner_owner = eng.new((n,), torch.int32)
-        self._length = eng.new((n,), torch.int32)
-        self._roots = None                        # the searching turn's buffers, made by the first match that searches
-        self._recorder = None                     # the Replay the next match fills
-
-    def record(self, games, first_turns=64):
-        """Arena.record: distinct game indices in any order (out of range or twice: a ValueError before anything touches the
-        device) -> the Replay the next play / play_search fills; the recorder is dropped when that match ends"""
-        self._recorder = Replay(games, self.height, self.width, self.game_cnt, first_turns)
-        return self._recorder
-
-    @classmethod
-    def from_engine(cls, engine):
-        """a league over the games an engine already holds (slots 0..n_slots-1)"""
-        self = cls.__new__(cls)
-        self._attach(engine)
-        return self
-
-    def import_states(self, states):
-        """start boards from the host (snk_game_state records), for parity runs"""
-        self.engine.import_states(states)
-        self._fresh = True
+        super()._attach(engine)
+        n = engine.n_slots
+        self._counts = engine.new((MAX_OWNERS,), torch.int32)
+        self._scratch = engine.new((engine.L.snk_pit_owned_scratch_elems(n, MAX_OWNERS),), torch.int32)
+        self._winner_owner = engine.new((n,), torch.int32)
 
     def _owner_table(self, nets, owner, searchers=False):
         """the checked table as uint8[game_cnt][snake_cnt] on the host"""
@@ -137,60 +82,7 @@ class League:
         init_tape / spawn_tape: as in Arena.match (recorded start draws; callable turn -> int16[game_cnt] recorded food spawns,
         for parity runs only).  counts_log: a list that receives the K row counts of every turn (what the turn's read-back
         brought, no further copy)."""
-        eng, n, S = self.engine, self.game_cnt, self.snake_cnt
-        nets = list(nets)
-        K = len(nets)
-        d_owner = torch.as_tensor(self._owner_table(nets, owner), device=eng.device)
-        if init_tape is not None:
-            eng.reset(init_tape=init_tape)
-        elif not self._fresh:
-            eng.reset()
-        self._fresh = False
-        self._live.fill_(1)
-        self._winner.fill_(-1)
-        self._winner_owner.fill_(-1)
-        self._length.zero_()
-        rec, self._recorder = self._recorder, None
-        if rec is not None:
-            rec.begin(eng)
-        L = eng.L
-        live, pairs, moves = self._live, self._pairs, self._moves
-        counts = self._counts[:K]
-        scripted = any(isinstance(net, Scripted) for net in nets)
-        turn = 0
-        while True:
-            check(L.snk_pit_rows_owned(eng.h, _ptr(live), n, _ptr(d_owner), K, _ptr(pairs), _ptr(counts), _ptr(self._scratch),
-                                       _stream()))
-            rows = counts.tolist()                # the turn's one read-back
-            m = sum(rows)
-            if m == 0:
-                break
-            turn += 1
-            if counts_log is not None:
-                counts_log.append(rows)
-            if scripted:                          # the kernel scores the scripted rows; observe and nets on the others' only
-                q = mixed_values(eng, nets, rows, pairs)
-            else:
-                planes, mask, _ = eng.observe_all(pairs[:m], want_key=False)
-                q = self._values(nets, rows, planes, mask)
-            check(L.snk_pit_moves(_ptr(q), _ptr(pairs), m, n, S, _ptr(moves), _stream()))
-            tape = None
-            if spawn_tape is not None:
-                tape = torch.as_tensor(np.ascontiguousarray(spawn_tape(turn), np.int16), device=eng.device)
-                if tape.numel() != n:
-                    raise ValueError(f"spawn_tape({turn}) has {tape.numel()} entries for {n} games")
-            if rec is not None:                   # the mid-tick snakes, from the records the step is about to change
-                rec.before_step(eng, turn, live, moves)
-            check(L.snk_engine_step_active_tape(eng.h, _ptr(live), n, _ptr(moves), _ptr(tape), _ptr(self._done), None, _stream()))
-            if rec is not None:                   # by the live flags the step saw: before the verdict clears them
-                rec.after_step(eng, turn, live)
-            check(L.snk_engine_rewards(eng.h, None, n, _ptr(self._rewards), _stream()))
-            check(L.snk_pit_verdict_owned(eng.h, _ptr(self._done), _ptr(self._rewards), n, _ptr(d_owner), K, turn, _ptr(live),
-                                          _ptr(self._winner), _ptr(self._winner_owner), _ptr(self._length), _stream()))
-        result = LeagueResult(self._winner.cpu().numpy(), self._winner_owner.cpu().numpy(), self._length.cpu().numpy(), turn)
-        if rec is not None:
-            rec.end(turn, result.lengths)         # the log's one copy, after the last turn
-        return result
+        return self._seated(nets, owner, False, init_tape, spawn_tape, counts_log)
 
     def play_search(self, sides, owner, init_tape=None, spawn_tape=None, counts_log=None):
         """play with any owner moving by search: sides[o] is a net with v_device, a Scripted or a Searcher around a net, in any
@@ -198,113 +90,65 @@ class League:
         transposition table, aged once a turn.  counts_log: a list that receives the whole read-back of every turn -- the row
         counts of the greedy owners in owner order, then the K counts of games per owner (0 for a greedy owner); without a Searcher
         the K row counts alone, as in play."""
+        return self._seated(sides, owner, True, init_tape, spawn_tape, counts_log)
+
+    def _seated(self, sides, owner, searchers, init_tape, spawn_tape, counts_log):
+        """the checks, which come before anything touches the device, and the match's seat"""
         eng, n, S = self.engine, self.game_cnt, self.snake_cnt
         sides = list(sides)
         K = len(sides)
-        table = self._owner_table(sides, owner, searchers=True)
+        table = self._owner_table(sides, owner, searchers)
         searching = [isinstance(side, Searcher) for side in sides]
         if len({id(side) for side, s in zip(sides, searching) if s}) != sum(searching):
             raise ValueError("the same Searcher sits twice: it owns one transposition table, aged once a turn (wrap the net twice)")
         search_mask = sum(1 << o for o in range(K) if searching[o])
-        greedy = [side for side, s in zip(sides, searching) if not s]
-        Kg = len(greedy)
-        scripted = any(isinstance(side, Scripted) for side in greedy)
-        d_owner = torch.as_tensor(table, device=eng.device)
-        d_greedy = None
-        if Kg:                                    # the greedy owners' table: searching owners out of range, the others 0..Kg-1
+        Kg = K - sum(searching)
+        d_greedy = d_owner = torch.as_tensor(table, device=eng.device)
+        if 0 < Kg < K:                            # the greedy owners' table: searching owners out of range, the others 0..Kg-1
             dense = np.full(256, 255, np.uint8)
             dense[[o for o in range(K) if not searching[o]]] = np.arange(Kg, dtype=np.uint8)
             d_greedy = torch.as_tensor(dense[table], device=eng.device)
-        if search_mask and self._roots is None:
-            self._roots = (eng.new((n * S,), torch.int32), eng.new((n * S, S), torch.uint8), eng.new((n, S), torch.int32),
-                           eng.new((2 * MAX_OWNERS,), torch.int32))
-        if init_tape is not None:
-            eng.reset(init_tape=init_tape)
-        elif not self._fresh:
-            eng.reset()
-        self._fresh = False
-        self._live.fill_(1)
-        self._winner.fill_(-1)
-        self._winner_owner.fill_(-1)
-        self._length.zero_()
-        rec, self._recorder = self._recorder, None
-        if rec is not None:
-            rec.begin(eng)
-        L = eng.L
-        live, pairs, moves = self._live, self._pairs, self._moves
         if search_mask:
-            slots, alive, rank, counts = self._roots
-            counts = counts[:Kg + K]              # {the greedy owners' rows, every owner's games}
+            if self._roots is None:
+                self._roots = (eng.new((n * S,), torch.int32), eng.new((n * S, S), torch.uint8), eng.new((n, S), torch.int32),
+                               eng.new((2 * MAX_OWNERS,), torch.int32))
+            counts = self._roots[3][:Kg + K]      # {the greedy owners' rows, every owner's games}
             counts.zero_()
         else:
-            counts = self._counts[:K]             # no searcher: the turn of play
-        turn = 0
-        while True:
-            if search_mask:
-                check(L.snk_pit_roots_owned(eng.h, _ptr(live), n, _ptr(d_owner), K, search_mask, _ptr(counts[Kg:]), _ptr(slots),
-                                            _ptr(alive), _ptr(rank), _ptr(self._scratch), _stream()))
-            if Kg:
-                check(L.snk_pit_rows_owned(eng.h, _ptr(live), n, _ptr(d_greedy), Kg, _ptr(pairs), _ptr(counts), _ptr(self._scratch),
-                                           _stream()))
-            read = counts.tolist()                # the turn's one read-back
-            if not any(read):
-                break
-            turn += 1
-            if counts_log is not None:
-                counts_log.append(read)
-            if Kg:                                # the greedy owners' nets on their own rows; the array is filled with 1
-                rows = read[:Kg]
-                m, q = sum(rows), None
-                if m and scripted:
-                    q = mixed_values(eng, greedy, rows, pairs)
-                elif m:
-                    planes, mask, _ = eng.observe_all(pairs[:m], want_key=False)
-                    q = self._values(greedy, rows, planes, mask)
-                check(L.snk_pit_moves(_ptr(q), _ptr(pairs), m, n, S, _ptr(moves), _stream()))
-            if search_mask:
-                found, lo = [], 0
-                for o in range(K):                # in owner order, each on its own slice of the lists
-                    G = read[Kg + o]
-                    if G == 0:                    # a greedy owner, or a searcher that has left every game (for good)
-                        continue
-                    f = sides[o].search(eng, slots[lo:lo + G], alive[lo:lo + G]).contiguous()
-                    if f.dtype != torch.uint8 or tuple(f.shape) != (G, S):
-                        raise EngineError(f"search returned {f.dtype} {tuple(f.shape)} for {G} games of {S} snakes")
-                    sides[o].end_of_turn()
-                    found.append(f)
-                    lo += G
-                d_found = None if not found else found[0] if len(found) == 1 else torch.cat(found)
-                check(L.snk_pit_search_moves_owned(_ptr(d_found), _ptr(rank), n, S, lo, int(Kg > 0), _ptr(moves), _stream()))
-            tape = None
-            if spawn_tape is not None:
-                tape = torch.as_tensor(np.ascontiguousarray(spawn_tape(turn), np.int16), device=eng.device)
-                if tape.numel() != n:
-                    raise ValueError(f"spawn_tape({turn}) has {tape.numel()} entries for {n} games")
-            if rec is not None:                   # the mid-tick snakes, from the records the step is about to change
-                rec.before_step(eng, turn, live, moves)
-            check(L.snk_engine_step_active_tape(eng.h, _ptr(live), n, _ptr(moves), _ptr(tape), _ptr(self._done), None, _stream()))
-            if rec is not None:                   # by the live flags the step saw: before the verdict clears them
-                rec.after_step(eng, turn, live)
-            check(L.snk_engine_rewards(eng.h, None, n, _ptr(self._rewards), _stream()))
-            check(L.snk_pit_verdict_owned(eng.h, _ptr(self._done), _ptr(self._rewards), n, _ptr(d_owner), K, turn, _ptr(live),
-                                          _ptr(self._winner), _ptr(self._winner_owner), _ptr(self._length), _stream()))
-        result = LeagueResult(self._winner.cpu().numpy(), self._winner_owner.cpu().numpy(), self._length.cpu().numpy(), turn)
-        if rec is not None:
-            rec.end(turn, result.lengths)         # the log's one copy, after the last turn
-        return result
+            counts = self._counts[:K]             # no searcher: the K row counts
+        self._winner_owner.fill_(-1)
+        return self._play(sides, (d_owner, K, d_greedy, Kg, search_mask, counts), init_tape, spawn_tape, counts_log)
 
-    @staticmethod
-    def _values(nets, rows, planes, mask):
-        """every net with rows on its own slice, in owner order: float32[m][3]"""
-        parts, lo = [], 0
-        for net, cnt in zip(nets, rows):
-            if cnt:
-                parts.append(net.v_device(planes[lo:lo + cnt], mask[lo:lo + cnt]))
-                lo += cnt
-        q = parts[0] if len(parts) == 1 else torch.cat(parts)
-        if q.dtype != torch.float32 or tuple(q.shape) != (lo, 3) or not q.is_cuda:
-            raise EngineError(f"v_device returned {q.dtype} {tuple(q.shape)} on {q.device} for {lo} rows: float32 [rows][3] on the device expected")
-        return q.contiguous()
+    def _lists(self, L, seat):
+        eng, n, live, pairs = self.engine, self.game_cnt, self._live, self._pairs
+        d_owner, K, d_greedy, Kg, search_mask, counts = seat
+        if search_mask:
+            slots, alive, rank, _ = self._roots
+            check(L.snk_pit_roots_owned(eng.h, _ptr(live), n, _ptr(d_owner), K, search_mask, _ptr(counts[Kg:]), _ptr(slots),
+                                        _ptr(alive), _ptr(rank), _ptr(self._scratch), _stream()))
+        if Kg:
+            check(L.snk_pit_rows_owned(eng.h, _ptr(live), n, _ptr(d_greedy), Kg, _ptr(pairs), _ptr(counts), _ptr(self._scratch),
+                                       _stream()))
+        read = counts.tolist()                    # the turn's one read-back
+        games, lo = [], 0
+        for o, G in enumerate(read[Kg:] if search_mask else ()):
+            if G:                                 # 0: a greedy owner, or a searcher that has left every game (for good)
+                games.append((o, slots[lo:lo + G], alive[lo:lo + G]))
+                lo += G
+        return read[:Kg], pairs[:sum(read[:Kg])], games, read, not any(read)
+
+    def _merge(self, L, seat, found, keep):
+        found = [f for f in found if f is not None]
+        d_found = None if not found else found[0] if len(found) == 1 else torch.cat(found)
+        check(L.snk_pit_search_moves_owned(_ptr(d_found), _ptr(self._roots[2]), self.game_cnt, self.snake_cnt,
+                                           sum(int(f.shape[0]) for f in found), keep, _ptr(self._moves), _stream()))
+
+    def _verdict(self, L, seat, turn):
+        check(L.snk_pit_verdict_owned(self.engine.h, _ptr(self._done), _ptr(self._rewards), self.game_cnt, _ptr(seat[0]), seat[1], turn,
+                                      _ptr(self._live), _ptr(self._winner), _ptr(self._winner_owner), _ptr(self._length), _stream()))
+
+    def _result(self, seat, turns):
+        return LeagueResult(self._winner.cpu().numpy(), self._winner_owner.cpu().numpy(), self._length.cpu().numpy(), turns)
 
 
 # ---- who sits where --------------------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@ import script_ref as SC
 import search_pit_ref as SR
 import test_replay_cpu as TC
 from conftest import golden_state, load_golden
+from pit_calls import Calls as _Calls
 
 pytestmark = pytest.mark.gpu
 
@@ -336,21 +337,6 @@ def test_league_play_search():
 
 
 # ---- launches and read-backs ---------------------------------------------------------------------------------------------------------
-class _Calls:
-    """the library behind a proxy that notes the name of every entry point called through it"""
-
-    def __init__(self, L):
-        self._L, self.names = L, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._L, name)
-
-        def call(*args):
-            self.names.append(name)
-            return fn(*args)
-        return call
-
-
 def test_launch_and_read_back_counts(monkeypatch):
     """three matches on the same start boards with the device's own food: before record was ever called, with a recorder, and
     after it.  The first and the third issue the same sequence of library calls; the second issues that sequence plus the slot
