@@ -1720,6 +1720,96 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_pit_record_boards(const uint8
     if (c < NC && mid[c] == 0 && food_bit(food, c)) mid[c] = 9;
 }
 
+// ------------------------------------------------------------------------------------------
+// the tally of a pit match (snake_engine.tally.Tally): what the tick about to be played does to every seat -- Game.tic's move, eat
+// and death phases (game.py:90-165) restated for one tick from the pre-step records and the dense moves, without changing them.
+// One wavefront per game, lane s holds snake s; a game is handled when its live flag is set and at least two snakes are alive,
+// which is when k_step / k_step_quad move it.  The cross-snake rules (who eats, who loses a head-on) are __shfl over the lanes.
+// The body test needs no board: the S new heads sit in registers, the lanes stride over each snake's ring run after the tail is
+// popped (old head included; a doubled tail keeps its cell, game.py:354-356) and note per head whether a cell equals it, then one
+// ballot per snake.  Every ring walk is bounded by the ring's size and every cell is compared with NC.  Lane s alone writes the
+// four cells [g][s]; a snake that lives keeps its fate and died cells.  No LDS, no atomics.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(BLOCK_THREADS) void k_pit_tally(const uint8_t *__restrict__ state, Layout L, const uint8_t *__restrict__ live,
+                                                            int n, const uint8_t *__restrict__ moves, int turn, int health_dec,
+                                                            int32_t *__restrict__ fate, int32_t *__restrict__ died,
+                                                            int32_t *__restrict__ eaten, int32_t *__restrict__ length)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int g = blockIdx.x * WAVES_PER_BLOCK + wv;
+    if (g >= n || !live[g]) return;                       // whole wavefronts leave: nothing below waits for another wave
+    const uint8_t *rec = state + (size_t)g * L.stride;
+    const SnakeMeta *meta = (const SnakeMeta *)(rec + L.meta_off);
+    const uint64_t *food = (const uint64_t *)(rec + L.food_off);
+    const bool act = lane < L.S;
+    SnakeMeta m = {0, 0, 0, 0, 0};
+    int mv = 1;
+    if (act) { m = meta[lane]; mv = moves[(size_t)g * L.S + lane]; }
+    const bool alive = act && m.alive && m.len >= 1;
+    if (__popcll(__ballot(alive)) < 2) return;            // k_step: a game with fewer than two snakes alive stands still
+    int head = -1, first = 0, cnt = 0;
+    if (alive) {
+        const int hc = script_ring_cell(rec, L, lane, m.tail + m.len - 1);
+        const int d = (mv + m.dir + 3) & 3;               // game.py:92
+        int y = hc / L.W, x = hc - y * L.W;
+        y += (d == 2) - (d == 0);
+        x += (d == 1) - (d == 3);
+        const bool oob = (y < 0) | (y >= L.H) | (x < 0) | (x >= L.W);
+        head = oob ? -1 : y * L.W + x;                    // -1: off board
+        first = m.tail + 1;                               // the tail node is popped, the old head joins the body
+        cnt = m.len - 1;
+    }
+    const bool hasfood = head >= 0 && food_bit(food, head);
+    bool eats = hasfood;                                  // game.py:121-127: the first snake in list order on a food cell eats
+    int heads[SNK_MAX_SNAKES];
+#pragma unroll
+    for (int o = 0; o < SNK_MAX_SNAKES; ++o) {
+        heads[o] = __shfl(head, o, 64);
+        const int fo = __shfl((int)hasfood, o, 64);
+        if (o < lane && fo && heads[o] == head) eats = false;
+    }
+    const int len1 = m.len + (int)eats;                   // game.py:126, Snake.grow
+    const int health1 = eats ? 100 : (int16_t)(m.health - health_dec);     // game.py:117-118, 125
+    uint32_t hit = 0u;                                    // bit o: this lane met a body cell that is snake o's new head
+    for (int s = 0; s < L.S; ++s) {
+        const int first_s = __shfl(first, s, 64);
+        int cnt_s = __shfl(cnt, s, 64);
+        cnt_s = cnt_s < L.cap ? cnt_s : L.cap;
+        for (int k = lane; k < cnt_s; k += 64) {
+            const int c = script_ring_cell(rec, L, s, first_s + k);
+            if (c < L.NC) {
+#pragma unroll
+                for (int o = 0; o < SNK_MAX_SNAKES; ++o) hit |= (uint32_t)(c == heads[o]) << o;
+            }
+        }
+    }
+    bool body = false;
+#pragma unroll
+    for (int o = 0; o < SNK_MAX_SNAKES; ++o) {
+        const bool any = __ballot((hit >> o) & 1u) != 0ull;
+        if (o == lane) body = any;
+    }
+    bool shared = false, lose = false;                    // game.py:156-161, the lengths after the eat phase
+#pragma unroll
+    for (int o = 0; o < SNK_MAX_SNAKES; ++o) {
+        const int lo = __shfl(len1, o, 64);
+        if (o != lane && heads[o] >= 0 && heads[o] == head) {
+            shared = true;
+            if (len1 <= lo) lose = true;
+        }
+    }
+    if (!alive) return;
+    int code = 0;                                         // game.py:147-165, an if/elif chain
+    if (head < 0) code = 1;
+    else if (body) code = 2;
+    else if (shared) { if (lose) code = 3; }              // a head-on survivor skips the starvation test
+    else if (health1 <= 0) code = 4;
+    const size_t at = (size_t)g * L.S + lane;
+    if (eats) eaten[at] += 1;
+    length[at] = len1;
+    if (code) { fate[at] = code; died[at] = turn; }
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 // square boards of 5x5 (the eight standard start cells are distinct from there on, game.py:25-29) to 19x19 (SNK_MAX_CELLS);
 // the reference's observation is a rot90 of a (2H-1)x(2W-1) canvas, so only square boards batch (game.py:257)
@@ -2084,6 +2174,19 @@ extern "C" int snk_pit_record_boards(const snk_engine *e, const uint8_t *d_live,
     const int fstride = align_up(e->L.NC, 16);
     k_pit_record_boards<<<wave_grid(r), BLOCK_THREADS, 0, (hipStream_t)stream>>>(e->d_state, e->L, e->n_slots, d_live, d_slots, r, d_frames,
                                                                                  fstride);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_tally(const snk_engine *e, const uint8_t *d_live, int n, const uint8_t *d_moves, int turn, int32_t *d_fate,
+                             int32_t *d_died, int32_t *d_food, int32_t *d_length, void *stream)
+{
+    SNK_REQUIRE(n >= 0, "snk_pit_tally: n=%d", n);
+    if (n == 0) return 0;
+    SNK_REQUIRE(e && d_live && d_moves && d_fate && d_died && d_food && d_length, "snk_pit_tally: NULL argument");
+    SNK_REQUIRE(n <= e->n_slots, "snk_pit_tally: n=%d exceeds %d slots", n, e->n_slots);
+    k_pit_tally<<<wave_grid(n), BLOCK_THREADS, 0, (hipStream_t)stream>>>(e->d_state, e->L, d_live, n, d_moves, turn, e->health_dec, d_fate,
+                                                                         d_died, d_food, d_length);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -129,6 +129,7 @@ PROTOTYPES = {
     "snk_pit_record_slots": (i32, [vp, vp, i32, vp, vp]),
     "snk_pit_record_moves": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "snk_pit_record_boards": (i32, [vp, vp, vp, i32, vp, vp]),
+    "snk_pit_tally": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     "snk_head_f32": (i32, [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "snk_bn_train_partials": (i32, []),
     "snk_conv3x3_f16s_input_scale": (i32, [vp, C.c_long, vp, vp, vp]),

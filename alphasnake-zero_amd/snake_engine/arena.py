@@ -45,6 +45,12 @@ sides' rows only (one observe per run of consecutive nets), and ``Scripted`` aga
 (game.py:140-141, 194-195): snk_pit_record_moves before the step and snk_pit_record_boards after it draw them into a log on the
 device, which is copied to the host once, after the last turn (``Replay`` below; snake_engine/replay.py names it).  The turn's
 read-back stays the one it is, and a match without a recorder issues no launch and no read-back for one.
+
+``tally()`` returns a ``tally.Tally`` that the next match fills with every seat's fate: which death it died (wall, body, head-on,
+starved) and on which turn, how much it ate and how long it grew.  snk_pit_tally, one launch per turn before the step, beside the
+recorder's, writes them into one array on the device, which is copied to the host once, after the last turn (``Tally`` below;
+snake_engine/tally.py names it).  A fifth hook, ``_owners``, gives the owner of every seat, for ``Tally.by_owner``.  A match without
+a tally issues no launch and no read-back for one.
 """
 from collections import namedtuple
 
@@ -272,6 +278,120 @@ def frames_text(frames):
     return b"".join(board_text(fr) for fr in np.asarray(frames))
 
 
+# ---- the tally of a match (snake_engine/tally.py is the module a user imports; the code stands here for the reason above) -------
+FATES = ("alive", "wall", "body", "head", "starved")       # the codes snk_pit_tally writes; 0: alive when the verdict came in
+
+TallyRows = namedtuple("TallyRows", "seats fates food length turns")
+TallyRows.__doc__ = """one entry per side (Arena: team A, team B; League: every owner of the match).  seats: int64[K] seats the side
+held; fates: int64[K][5] of them per fate, in the order of FATES; food: int64[K] food eaten; length: float64[K] mean final length
+(a dead seat's: the length it died with); turns: float64[K] mean turns lived -- the turn a seat died on, or its game's length for a
+seat alive at the verdict.  The means of a side without a seat are NaN."""
+
+
+def fate_code(fate):
+    """a name of FATES or its code -> the code"""
+    if isinstance(fate, str):
+        if fate not in FATES:
+            raise ValueError(f"fate {fate!r}: one of {FATES}")
+        return FATES.index(fate)
+    if isinstance(fate, (bool, np.bool_)) or int(fate) != fate or not 0 <= int(fate) < len(FATES):
+        raise ValueError(f"fate {fate!r}: a code 0..{len(FATES) - 1} or one of {FATES}")
+    return int(fate)
+
+
+class Tally:
+    """every seat's fate in one match: fate, died, food, length, all int32[game_cnt][snake_cnt], there once that match is over.
+    fate: a code of FATES; died: the turn the seat died on, 0 for a seat alive at the verdict; food: food eaten; length: the final
+    length, of a dead seat the one it died with (eating on the last tick included)."""
+
+    def __init__(self, game_cnt, snake_cnt):
+        self.game_cnt, self.snake_cnt = int(game_cnt), int(snake_cnt)
+        self.fate = self.died = self.food = self.length = None
+        self.owners = self.lengths = None       # uint8[game_cnt][snake_cnt], int32[game_cnt] (the result's verdict turns)
+        self.n_owners = 0
+        self._dev = None
+
+    @classmethod
+    def from_arrays(cls, fate, died, food, length, owners, n_owners, lengths):
+        """a Tally of arrays that are on the host already"""
+        fate = np.asarray(fate)
+        self = cls(*fate.shape)
+        self._set(np.stack([np.asarray(a, np.int32) for a in (fate, died, food, length)]), owners, n_owners, lengths)
+        return self
+
+    def _set(self, arrays, owners, n_owners, lengths):
+        n, S = self.game_cnt, self.snake_cnt
+        owners, lengths = np.asarray(owners, np.uint8), np.asarray(lengths, np.int32)
+        if arrays.shape != (4, n, S) or owners.shape != (n, S) or lengths.shape != (n,):
+            raise ValueError(f"tally arrays {arrays.shape}, owners {owners.shape}, lengths {lengths.shape} for {n} games of {S} snakes")
+        if owners.size and int(owners.max()) >= int(n_owners):
+            raise ValueError(f"owner {int(owners.max())} of a table of {n_owners} owners")
+        self.fate, self.died, self.food, self.length = arrays
+        self.owners, self.n_owners, self.lengths = owners, int(n_owners), lengths
+
+    # ---- the match's side ------------------------------------------------------------------------------------------------
+    def begin(self, engine):
+        """the four arrays as one allocation int32[4][n][S] on the device, zeroed"""
+        self.fate = self.died = self.food = self.length = self.owners = self.lengths = None
+        self._dev = engine.new((4, self.game_cnt, self.snake_cnt), torch.int32, 0)
+
+    def before_step(self, engine, turn, live, moves):
+        d = self._dev
+        check(engine.L.snk_pit_tally(engine.h, _ptr(live), self.game_cnt, _ptr(moves), turn, _ptr(d[0]), _ptr(d[1]), _ptr(d[2]),
+                                     _ptr(d[3]), _stream()))
+
+    def end(self, owners, n_owners, lengths):
+        """the one copy of the arrays, after the last turn; lengths: the result's verdict turns (on the host)"""
+        dev, self._dev = self._dev, None
+        self._set(dev.cpu().numpy(), owners, n_owners, lengths)
+
+    # ---- the reader's side -----------------------------------------------------------------------------------------------
+    def _filled(self):
+        if self.fate is None:
+            raise RuntimeError("the match this Tally counts has not been played")
+
+    def by_owner(self):
+        """TallyRows: one entry per side"""
+        self._filled()
+        K = self.n_owners
+        own = self.owners.reshape(-1).astype(np.int64)
+        fate = self.fate.reshape(-1).astype(np.int64)
+        lived = np.where(self.fate == 0, self.lengths[:, None], self.died).reshape(-1)
+        seats = np.bincount(own, minlength=K)
+        fates = np.bincount(own * len(FATES) + fate, minlength=K * len(FATES)).reshape(K, len(FATES))
+        food = np.bincount(own, weights=self.food.reshape(-1), minlength=K).astype(np.int64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            length = np.bincount(own, weights=self.length.reshape(-1), minlength=K) / seats
+            turns = np.bincount(own, weights=lived, minlength=K) / seats
+        return TallyRows(seats, fates, food, length, turns)
+
+    def games(self, owner=None, fate=None):
+        """the indices, ascending, of the games in which a seat (of that owner) met that fate (a name of FATES or its code): what
+        one hands to record() when the match is replayed from the same seed.  Without a fate: the games the owner sat in"""
+        self._filled()
+        hit = np.ones(self.fate.shape, bool)
+        if owner is not None:
+            if not 0 <= int(owner) < self.n_owners:
+                raise ValueError(f"owner {owner} outside 0..{self.n_owners - 1}")
+            hit &= self.owners == int(owner)
+        if fate is not None:
+            hit &= self.fate == fate_code(fate)
+        return np.flatnonzero(hit.any(axis=1))
+
+    def text(self, names=None):
+        """the table of by_owner as text, a line per side; names: the sides' names (default "0", "1", ...)"""
+        rows = self.by_owner()
+        names = [str(o) for o in range(self.n_owners)] if names is None else [str(v) for v in names]
+        if len(names) != self.n_owners:
+            raise ValueError(f"{len(names)} names for {self.n_owners} sides")
+        wide = max([len(v) for v in names] + [4])
+        out = f"{'side':<{wide}} {'seats':>7}" + "".join(f" {f:>8}" for f in FATES) + f" {'food':>8} {'length':>8} {'turns':>8}\n"
+        for o, name in enumerate(names):
+            out += (f"{name:<{wide}} {rows.seats[o]:>7d}" + "".join(f" {int(c):>8d}" for c in rows.fates[o])
+                    + f" {rows.food[o]:>8d} {rows.length[o]:>8.2f} {rows.turns[o]:>8.1f}\n")
+        return out
+
+
 class _Pit:
     """what Arena and League share: the engine and the match's buffers, the recorder, and the one turn loop.  A subclass seats
     the sides by four hooks, each handed the `seat` its own match method made:
@@ -280,7 +400,8 @@ class _Pit:
                                         read: what the turn's one read-back brought; over: nothing is left
         _merge(L, seat, found, keep)    found[o]: the root moves of searching side o, or None; keep: some side is greedy
         _verdict(L, seat, turn)
-        _result(seat, turns)         -> the match's result tuple; it has .lengths"""
+        _result(seat, turns)         -> the match's result tuple; it has .lengths
+        _owners(seat)                -> the owner of every seat, uint8[game_cnt][snake_cnt] on the host (asked for by a tally only)"""
 
     def __init__(self, height, width, snake_cnt, health_dec, game_cnt, seed):
         if seed is None:
@@ -304,6 +425,7 @@ class _Pit:
         self._length = eng.new((n,), torch.int32)
         self._roots = None                        # the searching turn's buffers, made by the first match that searches
         self._recorder = None                     # the Replay the next match fills
+        self._tallier = None                      # the Tally the next match fills
 
     def record(self, games, first_turns=64):
         """games: distinct game indices in any order (an index out of range or given twice is a ValueError, before anything
@@ -311,6 +433,11 @@ class _Pit:
         first_turns: the turns the log on the device is first sized for (it doubles as the match goes on)."""
         self._recorder = Replay(games, self.height, self.width, self.game_cnt, first_turns)
         return self._recorder
+
+    def tally(self):
+        """the Tally the next match fills with every seat's fate; it is dropped when that match ends"""
+        self._tallier = Tally(self.game_cnt, self.snake_cnt)
+        return self._tallier
 
     @classmethod
     def from_engine(cls, engine):
@@ -333,6 +460,7 @@ class _Pit:
         greedy = [side for side in sides if not isinstance(side, Searcher)]
         searching = len(greedy) < len(sides)
         rec, self._recorder = self._recorder, None        # held here only: a match that raises has dropped it too
+        tal, self._tallier = self._tallier, None
         if init_tape is not None:
             eng.reset(init_tape=init_tape)
         elif not self._fresh:
@@ -343,6 +471,8 @@ class _Pit:
         self._length.zero_()
         if rec is not None:
             rec.begin(eng)
+        if tal is not None:
+            tal.begin(eng)
         turn = 0
         while True:
             rows, pairs, games, read, over = self._lists(L, seat)
@@ -372,6 +502,8 @@ class _Pit:
                     raise ValueError(f"spawn_tape({turn}) has {tape.numel()} entries for {n} games")
             if rec is not None:                   # the mid-tick snakes, from the records the step is about to change
                 rec.before_step(eng, turn, live, moves)
+            if tal is not None:                   # every seat's fate on this tick, from the same records
+                tal.before_step(eng, turn, live, moves)
             check(L.snk_engine_step_active_tape(eng.h, _ptr(live), n, _ptr(moves), _ptr(tape), _ptr(self._done), None, _stream()))
             if rec is not None:                   # by the live flags the step saw: before the verdict clears them
                 rec.after_step(eng, turn, live)
@@ -380,6 +512,8 @@ class _Pit:
         result = self._result(seat, turn)
         if rec is not None:
             rec.end(turn, result.lengths)         # the log's one copy, after the last turn
+        if tal is not None:
+            tal.end(self._owners(seat), len(sides), result.lengths)       # the tally's one copy
         return result
 
 
@@ -457,6 +591,9 @@ class Arena(_Pit):
         wins_a = int(((winners >= 0) & (winners < a_cnt)).sum())
         wins_b = int((winners >= a_cnt).sum())
         return ArenaResult(winners, lengths, turns, wins_a, wins_b, self.game_cnt - wins_a - wins_b)
+
+    def _owners(self, seat):
+        return np.repeat((np.arange(self.snake_cnt) >= seat[0]).astype(np.uint8)[None, :], self.game_cnt, axis=0)
 
     # ---- the reference's two judges ------------------------------------------------------------------------------------------
     @staticmethod

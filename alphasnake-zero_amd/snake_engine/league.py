@@ -13,6 +13,7 @@ changes is the seating, the three hooks the turn loop calls:
     _merge    snk_pit_search_moves_owned: the found moves, one array in owner order, into the dense move array by list row
     _verdict  snk_pit_verdict_owned: a game is over when it is done or at most one owner has snakes left; the winner's owner
               beside the winner
+    _owners   the table itself: ``tally()`` (arena.py) counts every seat's fate, and ``Tally.by_owner`` has a row per owner
 
 With two sides and owner[g][s] = (s >= a_cnt) every launch and every batch is what ``Arena.match`` issues, with or without
 Searchers, so the winners, lengths and turns are the same bit for bit; without a Searcher ``play_search`` is ``play``.  What the
@@ -117,11 +118,11 @@ class League(_Pit):
         else:
             counts = self._counts[:K]             # no searcher: the K row counts
         self._winner_owner.fill_(-1)
-        return self._play(sides, (d_owner, K, d_greedy, Kg, search_mask, counts), init_tape, spawn_tape, counts_log)
+        return self._play(sides, (d_owner, K, d_greedy, Kg, search_mask, counts, table), init_tape, spawn_tape, counts_log)
 
     def _lists(self, L, seat):
         eng, n, live, pairs = self.engine, self.game_cnt, self._live, self._pairs
-        d_owner, K, d_greedy, Kg, search_mask, counts = seat
+        d_owner, K, d_greedy, Kg, search_mask, counts, _ = seat
         if search_mask:
             slots, alive, rank, _ = self._roots
             check(L.snk_pit_roots_owned(eng.h, _ptr(live), n, _ptr(d_owner), K, search_mask, _ptr(counts[Kg:]), _ptr(slots),
@@ -146,6 +147,9 @@ class League(_Pit):
     def _verdict(self, L, seat, turn):
         check(L.snk_pit_verdict_owned(self.engine.h, _ptr(self._done), _ptr(self._rewards), self.game_cnt, _ptr(seat[0]), seat[1], turn,
                                       _ptr(self._live), _ptr(self._winner), _ptr(self._winner_owner), _ptr(self._length), _stream()))
+
+    def _owners(self, seat):
+        return seat[6]                            # the checked table, still on the host
 
     def _result(self, seat, turns):
         return LeagueResult(self._winner.cpu().numpy(), self._winner_owner.cpu().numpy(), self._length.cpu().numpy(), turns)

@@ -60,7 +60,7 @@ const char *snk_last_error(void);
                              * snk_pit_rows_owned, snk_pit_verdict_owned) and the searching league's (snk_pit_roots_owned,
                              * snk_pit_search_moves_owned) and the scripted opponent's (snk_pit_script_values) and the replay
                              * recorder's (snk_pit_record_stride, snk_pit_record_slots, snk_pit_record_moves,
-                             * snk_pit_record_boards): no argument list of an older one changed */
+                             * snk_pit_record_boards) and the tally's (snk_pit_tally): no argument list of an older one changed */
 int snk_version(void);
 
 /* ---- engine lifetime -------------------------------------------------------------------
@@ -630,6 +630,33 @@ int snk_pit_record_slots(const snk_engine *e, const int32_t *h_slots, int r, int
 int snk_pit_record_moves(const snk_engine *e, const uint8_t *d_live, const int32_t *d_slots, int r, const uint8_t *d_moves,
                          int8_t *d_frames, void *stream);
 int snk_pit_record_boards(const snk_engine *e, const uint8_t *d_live, const int32_t *d_slots, int r, int8_t *d_frames, void *stream);
+
+/* ---- the tally of a pit match: every seat's fate (Game.tic game.py:90-165 for one tick, read only) ------------------------------
+ * snake_engine.tally.Tally: how each seat's game went -- which death it died and on which turn, how much it ate, how long it grew.
+ * The engine's counters[6] are per game; when two snakes die on one tick from different causes they cannot say which seat died how.
+ * snk_pit_tally is launched BEFORE the turn's snk_engine_step_active_tape, where snk_pit_record_moves stands, with the flags
+ * d_live uint8[n] and the dense moves d_moves uint8[n][S] the step is given, and restates the tick from the records the step is
+ * about to change.  It handles a game g < n whose flag is set and that has at least two snakes alive -- the games the step moves.
+ * For every snake s alive before the tick:
+ *   heading (move + dir + 3) & 3 (game.py:92), the new head cell (Snake.move game.py:329-343); a head outside the board is off board;
+ *   the body cells of the tick: of every snake alive before it, the nodes after the tail node is popped, the old head included
+ *     (game.py:109-114); a doubled tail keeps its cell (game.py:354-356);
+ *   eats: of the snakes whose new head is on a food cell the first in id order (game.py:121-127); len' = len + eats,
+ *     health' = 100 if eats, else health - health_dec (game.py:117-118, 125-126);
+ *   the fate, an if/elif chain in the reference's order (game.py:147-165):
+ *     1 wall     the new head is off board
+ *     2 body     the new head is a body cell
+ *     3 head-on  another snake t alive before the tick has the same new head, and len'_t >= len'_s
+ *     4 starved  health' <= 0 -- not tested for a snake that shared its head cell and survived (the elif at game.py:156)
+ *     otherwise it lives.
+ * Writes, all int32[n][S] indexed [slot][snake id]: d_food[g][s] += eats; d_length[g][s] = len'; for a snake that dies
+ * d_fate[g][s] = its code and d_died[g][s] = turn; a snake that lives keeps its d_fate and d_died cells.  The caller zeroes the four
+ * arrays before the match, so a fate of 0 reads "alive when the game's verdict came in".  Cells of closed games, of games that stand
+ * still, of dead snakes and rows past n are not written.  One wavefront per game, lane s holds snake s, every cell has one writer;
+ * no LDS, no atomics.  n == 0 is a no-op that accepts NULL buffers; a NULL array, n < 0 or n > n_slots is an error before any
+ * launch.                                                                                                                         */
+int snk_pit_tally(const snk_engine *e, const uint8_t *d_live, int n, const uint8_t *d_moves, int turn, int32_t *d_fate, int32_t *d_died,
+                  int32_t *d_food, int32_t *d_length, void *stream);
 
 /* ---- training half: AlphaNNet.train = model.fit (alpha_nnet.py:58-59) -------------------------
  * Training-mode batch normalisation of a 128-channel channels-last float32 activation [rows = n * h * w][128] (the

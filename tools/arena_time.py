@@ -1,14 +1,17 @@
 """The pit match, host loop against device loop: `MPGameRunner.run` and `MPGameRunner.run_device` on the same start boards, the
 same engine seed (so the same food spawns) and the same two nets (generation-0 Glorot weights, two seeds), 11x11 with 4 snakes.
 
-    python tools/arena_time.py [games ...] [--pairs 3] [--blocks 4] [--log profiles/arena_ab.log] [--record K]
+    python tools/arena_time.py [games ...] [--pairs 3] [--blocks 4] [--log profiles/arena_ab.log] [--record K | --tally]
 
 For every game count (default 300 and 4096) the two forms alternate inside this one process, `--pairs` times; a line per
 match with its turns, seconds and ms per turn, then the medians.  The winners of the two forms are compared: they play the
 same match.
 --record K: instead, what a replay recorder costs: Arena.match of the same two nets without a recorder and with one on the first K
 games (Arena.record), alternating inside this one process on the same start boards, `--pairs` times; ms per turn of both, the
-medians and the added time per turn.  The recorded match's winners and frame counts are checked against the plain one's."""
+medians and the added time per turn.  The recorded match's winners and frame counts are checked against the plain one's.
+--tally: the same for a tally (Arena.tally, snk_pit_tally: one more launch per turn over all games): without and with one,
+alternating; the tallied match's winners and its deaths against the plain one's; then the kernel alone beside the step kernel, by
+events, on the start boards (profiles/tally_ab.log)."""
 import argparse
 import os
 import statistics
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--log", default=None)
     ap.add_argument("--record", type=int, default=None, metavar="K")
+    ap.add_argument("--tally", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -71,7 +75,7 @@ def main():
             with open(a.log, "w") as f:
                 f.write("\n".join(lines) + "\n")
 
-    def match(n, start, record):
+    def match(n, start, record, tally=False):
         from snake_engine.arena import Arena
         arena = Arena(11, 11, 4, 1, n, seed=7)
         if start is None:
@@ -79,11 +83,69 @@ def main():
         else:
             arena.import_states(start)
         rep = arena.record(range(min(record, n))) if record else None
+        if tally:
+            rep = arena.tally()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         res = arena.match(nets[0], nets[1], 1)
         torch.cuda.synchronize()
         return res, time.perf_counter() - t0, start, rep
+
+    if a.tally:
+        from snake_engine._lib import check
+        from snake_engine.arena import Arena
+        say(f"arena_time --tally: Arena.match greedy against greedy, 11x11, 4 snakes (1 v 3), {a.blocks}-block Glorot nets, "
+            f"{a.pairs} alternating pairs per size, {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), "
+            f"ROCm / HIP {torch.version.hip}, torch {torch.__version__}")
+        match(64, None, 0)                                 # first launches, plans and range-guard scales settle outside the timing
+        match(64, None, 0, True)
+        for n in a.games:
+            start, per = None, {"plain": [], "tallied": []}
+            for k in range(a.pairs):
+                won = {}
+                for form in ("plain", "tallied"):
+                    res, dt, start, tal = match(n, start, 0, form == "tallied")
+                    won[form] = res.winners.tolist()
+                    per[form].append(dt / res.turns * 1e3)
+                    say(f"games {n:5d} pair {k} {form:8s}: {res.turns:4d} turns, {dt:7.3f} s, {dt / res.turns * 1e3:8.3f} ms per turn")
+                    if tal is not None:
+                        dead = int((tal.fate > 0).sum())
+                        ok = dead + int((res.winners >= 0).sum()) <= 4 * n and int(tal.died.max()) == res.turns
+                        say(f"games {n:5d} pair {k} tallied {dead} deaths, the last on the last turn and none too many: {ok}")
+                say(f"games {n:5d} pair {k} winners identical: {won['plain'] == won['tallied']}")
+            p, r = statistics.median(per["plain"]), statistics.median(per["tallied"])
+            say(f"games {n:5d} median ms per turn: plain {p:.3f}, tallied {r:.3f}, added {(r - p) * 1e3:.1f} us per turn")
+            # the kernel alone beside the step kernel, by events, on start boards (the tally changes nothing, the step is undone
+            # by importing the boards again between its launches)
+            arena = Arena(11, 11, 4, 1, n, seed=7)
+            eng, L = arena.engine, arena.engine.L
+            boards = eng.export()
+            live = torch.ones((n,), dtype=torch.uint8, device="cuda")
+            moves = torch.ones((n, 4), dtype=torch.uint8, device="cuda")
+            out = torch.zeros((4, n, 4), dtype=torch.int32, device="cuda")
+            done = torch.zeros((n,), dtype=torch.uint8, device="cuda")
+            us = {"snk_pit_tally": [], "snk_engine_step_active_tape": []}
+            for i in range(24):
+                for name in us:
+                    eng.import_states(boards)
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    if name == "snk_pit_tally":
+                        check(L.snk_pit_tally(eng.h, live.data_ptr(), n, moves.data_ptr(), 1, out[0].data_ptr(), out[1].data_ptr(),
+                                              out[2].data_ptr(), out[3].data_ptr(), torch.cuda.current_stream().cuda_stream))
+                    else:
+                        check(L.snk_engine_step_active_tape(eng.h, live.data_ptr(), n, moves.data_ptr(), None, done.data_ptr(), None,
+                                                            torch.cuda.current_stream().cuda_stream))
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if i >= 4:
+                        us[name].append(e0.elapsed_time(e1) * 1e3)
+            t, st = statistics.median(us["snk_pit_tally"]), statistics.median(us["snk_engine_step_active_tape"])
+            say(f"games {n:5d} one launch on the start boards, by events, median of 20: snk_pit_tally {t:.1f} us, "
+                f"snk_engine_step_active_tape {st:.1f} us")
+        write_log()
+        return
 
     if a.record is not None:
         say(f"arena_time --record {a.record}: Arena.match greedy against greedy, 11x11, 4 snakes (1 v 3), {a.blocks}-block Glorot nets, "

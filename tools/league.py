@@ -3,7 +3,7 @@ ratings of a round robin, 11x11.
 
     python tools/league.py [--nets 6] [--games 300] [--seats duel|1v3|ffa] [--blocks 4] [--models NAME G0 G1 ...] [--seed 1]
                            [--search B [--depth 8]] [--time] [--pairs 3] [--log profiles/league_ab.log] [--baseline [FLAGS ...]]
-                           [--replay K DIR]
+                           [--replay K DIR] [--tally]
 
 --nets K plays generation-0 Glorot nets of --blocks blocks, seeds 1..K; --models NAME G0 G1 ... loads NAME<G>.h5 instead (e.g.
 --models models/gen 0 15 30).  Every line-up of snake_engine.league.schedule plays --games games, all in lock step in one engine.
@@ -18,7 +18,10 @@ of the searches (Searcher.stats) and, since a searching turn is bound by them, t
 table and the ratings behind the nets, one per FLAGS value (bits 1 space, 2 heads, 4 food; no value: 7, the whole policy).  A
 scripted owner moves by its script under --search too.  --nets 0 --baseline 0 1 3 7 is the round robin of four flag settings.
 --replay K DIR (not with --time): the round robin records its first K games (League.record) and writes them as DIR/game_<g>.rep,
-the text of the reference's replay.rep: two boards per tick."""
+the text of the reference's replay.rep: two boards per tick.
+--tally (not with --time): the round robin also counts every seat's fate on the device (League.tally) and the table is printed
+behind the cross table: per net the seats, how many were alive at the verdict, hit a wall, ran into a body, lost a head-on or
+starved, food eaten, mean final length and mean turns lived."""
 import argparse
 import os
 import statistics
@@ -57,6 +60,7 @@ def main():
     ap.add_argument("--log", default=None)
     ap.add_argument("--baseline", nargs="*", type=int, default=None, metavar="FLAGS")
     ap.add_argument("--replay", nargs=2, default=None, metavar=("K", "DIR"))
+    ap.add_argument("--tally", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -110,15 +114,20 @@ def main():
         f"torch {torch.__version__}" + (f"; every seat searches, breadth {a.search}, depth {a.depth}" if a.search else ""))
     search = dict(breadth=a.search, depth=a.depth) if a.search else None
 
-    def league_form(seed, replay=None):
+    tallies = []
+
+    def league_form(seed, replay=None, tally=False):
         """one League.play (play_search) of every line-up -> (result, seconds, rows evaluated, the searches' net evaluations);
-        replay: (K, DIR), the first K games are recorded and written when the match is over"""
+        replay: (K, DIR), the first K games are recorded and written when the match is over; tally: the match's Tally is left in
+        `tallies`"""
         Counted.rows = 0
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         league = League(11, 11, S, 1, len(owner), seed)                     # both forms pay for their engines inside the clock
         sides = searchers(nets, search, seed) if search else nets           # ... and for their searchers' tables
         rep = league.record(range(min(int(replay[0]), len(owner)))) if replay else None
+        if tally:
+            tallies.append(league.tally())
         res = league.play_search(sides, owner) if search else league.play(nets, owner)
         torch.cuda.synchronize()
         if rep is not None:
@@ -171,11 +180,13 @@ def main():
         say(f"time: median seconds: league form {ml:.3f} (min {min(per['league']):.3f}, max {max(per['league']):.3f}), arena form "
             f"{ma:.3f} (min {min(per['arena']):.3f}, max {max(per['arena']):.3f}), ratio of medians arena / league {ma / ml:.2f}x")
         return
-    res, dt, _, _ = league_form(a.seed, a.replay)
+    res, dt, _, _ = league_form(a.seed, a.replay, a.tally)
     t = table(res, owner, K)
     say(f"{res.turns} turns, {dt:.3f} s, {dt / res.turns * 1e3:.3f} ms per turn; wins of the row's net over the column's / draws")
     for line in format_table(names, t, ratings(t.wins, t.draws)):
         say(line)
+    for tal in tallies:
+        say("every seat's fate:\n" + tal.text(names).rstrip("\n"))
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 (snake_engine.arena.Searcher) and a greedy side of the SAME net, 11x11.
 
     python tools/search_pit.py [--games 300] [--breadth 16] [--depth 8] [--blocks 4] [--weights CKPT] [--seed 1]
-                               [--time] [--pairs 2] [--log profiles/arena_search.log] [--baseline] [--replay K DIR]
+                               [--time] [--pairs 2] [--log profiles/arena_search.log] [--baseline] [--replay K DIR] [--tally]
 
 Strength (default): 1 v 3 with the searcher alone, 1 v 3 with the searcher's three against the greedy one, and the duel; win and
 draw rates of the searching side with their binomial 95 % intervals (Wilson), ms per turn and net evaluations per turn.
@@ -14,6 +14,9 @@ of against itself: the greedy net in the duel and in 1 v 3 both ways, then the n
 win and draw rates with the same intervals.
 --replay K DIR: the first match the run reports (strength or --baseline) records its first K games (Arena.record) and writes them
 as DIR/game_<g>.rep, the text of the reference's replay.rep: two boards per tick.
+--tally: the first match the run reports also counts every seat's fate on the device (Arena.tally) and prints the table: per side
+the seats, how many were alive at the verdict, hit a wall, ran into a body, lost a head-on or starved, food eaten, mean final
+length and mean turns lived.
 The lines are appended to --log behind a line that names the device."""
 import argparse
 import math
@@ -50,6 +53,7 @@ def main():
     ap.add_argument("--log", default=None)
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--replay", nargs=2, default=None, metavar=("K", "DIR"))
+    ap.add_argument("--tally", action="store_true")
     a = ap.parse_args()
     import torch
     from snake_engine.arena import Arena, Scripted, Searcher
@@ -100,6 +104,17 @@ def main():
                 rep.write(g, os.path.join(a.replay[1], f"game_{g}.rep"), append=False)
             say(f"replay: games 0..{len(rep.games) - 1} of this match written to {a.replay[1]}/game_<g>.rep")
 
+    counting = [a.tally]
+
+    def tallier(arena):
+        """the Tally of the first reported match, None for every later one"""
+        want, counting[0] = counting[0], False
+        return arena.tally() if want else None
+
+    def write_tally(tal, names):
+        if tal is not None:
+            say("tally of this match:\n" + tal.text(names).rstrip("\n"))
+
     def play(snakes, a_cnt, searching, breadth, seed, start=None, record=False):
         """one match; searching: which sides move by search -> (result, seconds, net evaluations of the searchers, start boards)"""
         arena = Arena(11, 11, snakes, 1, a.games, seed)
@@ -109,6 +124,7 @@ def main():
             arena.import_states(start)
         sides = [Searcher(net, breadth, a.depth, seed=seed + 11 * k) if s else net for k, s in enumerate(searching)]
         rep = recorder(arena) if record else None
+        tal = tallier(arena) if record else None
         ensure_s[0] = 0.0
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -116,6 +132,7 @@ def main():
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         write_replay(rep)
+        write_tally(tal, ["search" if s else "greedy" for s in searching])
         evals = sum(s.stats["net_evals"] for s in sides if isinstance(s, Searcher))
         return res, dt, evals, start
 
@@ -129,13 +146,14 @@ def main():
             for i, (name, snakes, a_cnt, who) in enumerate(ups):
                 side = net if breadth is None else Searcher(net, breadth, a.depth, seed=a.seed + 11)
                 arena = Arena(11, 11, snakes, 1, a.games, a.seed + i)
-                rep = recorder(arena)
+                rep, tal = recorder(arena), tallier(arena)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 res = arena.match(side, script, a_cnt)
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
                 write_replay(rep)
+                write_tally(tal, ["net", "script"])
                 wins = (res.wins_a, res.wins_b)[who]
                 (wl, wh), (dl, dh) = wilson(wins, a.games), wilson(res.draws, a.games)
                 say(f"baseline: {mover} against the script, {name}: net wins {wins / a.games:.3f} [{wl:.3f}, {wh:.3f}], draws "
