@@ -1584,6 +1584,197 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_pit_script(const uint8_t *__r
 }
 
 // ------------------------------------------------------------------------------------------
+// the lookahead opponent of the pit (snake_engine.arena.Lookahead, snk_pit_look_values): the scripted policy one tick deep.  The
+// policy is the project's own; include/snake_engine.h states it and tests/look_ref.py restates it in plain Python.  A row (slot g,
+// snake s) of a game with A = 2..4 snakes alive is scored over the 3^A children of its game: copies made by k_clone, stepped once
+// by the step kernels on a sub-engine without food spawning, and scored by k_pit_script -- launched by the entry point through
+// snk_engine_clone, snk_engine_step_active and snk_pit_script_values.  What is new:
+//   k_look_count / k_cmp_scan / k_look_groups   the plan's scan over the rows (the three launches of k_pit_roots_*: tile sums, one
+//                                               block scanning them, the scatter): rows of one slot that stand next to each other
+//                                               form a group and share one set of children; per group its source slot and the
+//                                               alive bits of that slot
+//   k_look_fan                                  the plan's fan-out, a thread per child and per leaf: the children's active flags and
+//                                               dense moves, and the leaf pair list (sub slot, s) the script kernel scores
+//   k_look_reduce                               a quad per row, lane a scores own move a: the worst reply over the children in
+//                                               which s's digit is a, or minus the ways to die
+// Every cell of every array has one writer, nothing is read back, and there are no atomics.  All per-thread state is scalar: no
+// array is indexed by a run-time value.
+// ------------------------------------------------------------------------------------------
+#define LK_MAX_LEAVES (1 << 28)                  // m * F: a quad of lanes per leaf row of the script kernel stays inside an int
+#define LK_WIN 16777216.0f                       // 2^24: above every plain score
+
+__host__ __device__ static inline int look_pow3(int k) { int p = 1; for (int i = 0; i < k; ++i) p *= 3; return p; }
+
+// scratch, in int32 elements from its start; every part starts at a multiple of four elements (16 bytes)
+struct LookScratch {
+    long tile_sums;     // int32[tiles] + the group count
+    long row_group;     // int32[m]       the group of every row
+    long grp_src;       // int32[m]       a group's source slot (a valid slot for every group < n_groups)
+    long grp_bits;      // int32[m]       bit s = snake s of the source slot is alive; 0: the group is not looked ahead
+    long active;        // uint8[m * F]   a child's flag for the step
+    long moves;         // uint8[m * F][S]
+    long leaf_pairs;    // int32[m * F][2]
+    long leaf_q;        // float[m * F][3]
+    long fb_q;          // float[m][3]    the plain scores of the rows themselves
+    long total;
+};
+
+static LookScratch look_scratch(long m, int S, int F)
+{
+    auto up4 = [](long v) { return (v + 3) / 4 * 4; };
+    LookScratch P;
+    long at = 0;
+    P.tile_sums = at;  at += up4((m + PIT_TILE - 1) / PIT_TILE + 1);
+    P.row_group = at;  at += up4(m);
+    P.grp_src = at;    at += up4(m);
+    P.grp_bits = at;   at += up4(m);
+    P.active = at;     at += up4((m * F + 3) / 4);
+    P.moves = at;      at += up4((m * F * S + 3) / 4);
+    P.leaf_pairs = at; at += up4(2 * m * F);
+    P.leaf_q = at;     at += up4(3 * m * F);
+    P.fb_q = at;       at += up4(3 * m);
+    P.total = at;
+    return P;
+}
+
+// row i starts a group when it is row 0 or names another slot than row i - 1
+__device__ static inline bool look_starts(const int32_t *__restrict__ pairs, int i)
+{
+    return i == 0 || pairs[2 * (size_t)i] != pairs[2 * (size_t)i - 2];
+}
+
+// groups that start in the block's PIT_TILE rows: tile_sums[b]
+__global__ __launch_bounds__(CMP_THREADS) void k_look_count(const int32_t *__restrict__ pairs, int m, int32_t *__restrict__ tile_sums)
+{
+    __shared__ int sh[8];
+    const int base = blockIdx.x * PIT_TILE + threadIdx.x * PIT_ITEMS;
+    int c = 0;
+    for (int q = 0; q < PIT_ITEMS; ++q) { const int i = base + q; if (i < m && look_starts(pairs, i)) ++c; }
+    int total;
+    block_exclusive_scan_256(c, &total, sh);
+    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
+}
+
+// row_group[i] = the group of row i (any size: the reduce compares it with n_groups); for a group g < n_groups the row that starts
+// it writes its source slot and alive bits -- slot 0 and no bits for a slot outside the engine --, and the groups from the count
+// up to n_groups, which no row starts, get slot 0 and no bits from the thread whose rows have their numbers (n_groups <= m)
+__global__ __launch_bounds__(CMP_THREADS) void k_look_groups(const uint8_t *__restrict__ state, Layout L, int n_slots,
+                                                            const int32_t *__restrict__ pairs, int m, const int32_t *__restrict__ tile_offs,
+                                                            const int32_t *__restrict__ count, int n_groups,
+                                                            int32_t *__restrict__ row_group, int32_t *__restrict__ grp_src,
+                                                            int32_t *__restrict__ grp_bits)
+{
+    __shared__ int sh[8];
+    const int base = blockIdx.x * PIT_TILE + threadIdx.x * PIT_ITEMS;
+    int c = 0;
+    for (int q = 0; q < PIT_ITEMS; ++q) { const int i = base + q; if (i < m && look_starts(pairs, i)) ++c; }
+    int total;
+    int run = tile_offs[blockIdx.x] + block_exclusive_scan_256(c, &total, sh);        // groups started before this thread's rows
+    const int groups = *count;
+    for (int q = 0; q < PIT_ITEMS; ++q) {
+        const int i = base + q;
+        if (i >= m) break;
+        const bool starts = look_starts(pairs, i);
+        if (starts) ++run;
+        const int g = run - 1;
+        row_group[i] = g;
+        if (starts && g < n_groups) {
+            const int slot = pairs[2 * (size_t)i];
+            const bool valid = slot >= 0 && slot < n_slots;
+            uint32_t bits = 0u;
+            if (valid) {
+                const SnakeMeta *meta = (const SnakeMeta *)(state + (size_t)slot * L.stride + L.meta_off);
+                for (int s = 0; s < L.S; ++s) bits |= (meta[s].alive ? 1u : 0u) << s;
+            }
+            grp_src[g] = valid ? slot : 0;
+            grp_bits[g] = (int32_t)bits;
+        }
+        if (i >= groups && i < n_groups) { grp_src[i] = 0; grp_bits[i] = 0; }
+    }
+}
+
+// thread t < n_groups * F is child j = t % F of group t / F: active when the group's game has A = 2..4 snakes alive and
+// j < 3^A; its k-th alive snake moves (j / 3^k) % 3, every other entry is 1.  Thread t < m * F is leaf j of row t / F: the pair
+// (sub slot of child j of the row's group, s) when the row is looked ahead and the child is active, else (-1, -1), which the
+// script kernel scores -1, -1, -1 without walking anything
+__global__ __launch_bounds__(CMP_THREADS) void k_look_fan(int m, int F, int S, int n_groups, const int32_t *__restrict__ pairs,
+                                                         const int32_t *__restrict__ row_group, const int32_t *__restrict__ grp_bits,
+                                                         uint8_t *__restrict__ active, uint8_t *__restrict__ moves,
+                                                         int32_t *__restrict__ leaf_pairs)
+{
+    const int t = blockIdx.x * CMP_THREADS + threadIdx.x;
+    const int g = t / F, j = t - g * F;                   // as a child: group and index; as a leaf: row and index
+    if (g < n_groups) {
+        const uint32_t bits = (uint32_t)grp_bits[g];
+        const int A = __popc(bits);
+        const bool act = A >= 2 && A <= 4 && j < look_pow3(A);
+        active[t] = act ? 1 : 0;
+        int d = j;
+        for (int s = 0; s < S; ++s) {
+            int mv = 1;
+            if (act && ((bits >> s) & 1u)) { mv = d % 3; d /= 3; }
+            moves[(size_t)t * S + s] = (uint8_t)mv;
+        }
+    }
+    if (g < m) {
+        const int s = pairs[2 * (size_t)g + 1], grp = row_group[g];
+        bool look = false;
+        if (grp < n_groups && s >= 0 && s < S) {
+            const uint32_t bits = (uint32_t)grp_bits[grp];
+            const int A = __popc(bits);
+            look = ((bits >> s) & 1u) && A >= 2 && A <= 4 && j < look_pow3(A);
+        }
+        leaf_pairs[2 * (size_t)t] = look ? grp * F + j : -1;
+        leaf_pairs[2 * (size_t)t + 1] = look ? s : -1;
+    }
+}
+
+// a quad of lanes per row, lane a < 3 scores own move a.  A row whose group lies beyond the sub-engine: -1.  A row that is not
+// looked ahead (a dead or out-of-range pair, A < 2, A > 4): its plain score.  Otherwise over the 3^(A-1) children whose digit of
+// s is a: the smallest leaf value when s lives in all of them, else -2 - (the children in which s is dead); a leaf is 2^24 when s
+// alone is left, else the largest of s's three plain scores on the child
+__global__ __launch_bounds__(CMP_THREADS) void k_look_reduce(const uint8_t *__restrict__ sub_state, Layout L, int m, int F, int n_groups,
+                                                            const int32_t *__restrict__ pairs, const int32_t *__restrict__ row_group,
+                                                            const int32_t *__restrict__ grp_bits, const float *__restrict__ leaf_q,
+                                                            const float *__restrict__ fb_q, float *__restrict__ q)
+{
+    const int t = blockIdx.x * CMP_THREADS + threadIdx.x;
+    const int row = t >> 2, a = t & 3;
+    if (row >= m || a >= 3) return;
+    const int s = pairs[2 * (size_t)row + 1], grp = row_group[row];
+    float out = -1.0f;
+    if (grp < n_groups) {
+        const uint32_t bits = (uint32_t)grp_bits[grp];
+        const int A = __popc(bits);
+        const bool look = s >= 0 && s < L.S && ((bits >> s) & 1u) && A >= 2 && A <= 4;
+        if (!look) {
+            out = fb_q[3 * (size_t)row + a];
+        } else {
+            const int p = look_pow3(__popc(bits & ((1u << s) - 1u)));        // the weight of s's digit
+            const int replies = look_pow3(A - 1);
+            const uint32_t others = bits & ~(1u << s);
+            int dead = 0;
+            float worst = LK_WIN;
+            for (int i = 0; i < replies; ++i) {
+                const int hi = i / p, j = hi * 3 * p + a * p + (i - hi * p);
+                const SnakeMeta *meta = (const SnakeMeta *)(sub_state + ((size_t)grp * F + j) * L.stride + L.meta_off);
+                if (!meta[s].alive) { ++dead; continue; }
+                bool alone = true;
+                for (uint32_t b = others; b; b &= b - 1u) alone &= !meta[__ffs((int)b) - 1].alive;
+                float leaf = LK_WIN;
+                if (!alone) {
+                    const float *z = leaf_q + 3 * ((size_t)row * F + j);
+                    leaf = fmaxf(z[0], fmaxf(z[1], z[2]));
+                }
+                worst = fminf(worst, leaf);
+            }
+            out = dead ? (float)(-2 - dead) : worst;
+        }
+    }
+    q[3 * (size_t)row + a] = out;
+}
+
+// ------------------------------------------------------------------------------------------
 // replays of chosen games of a pit match (snake_engine.replay.Replay): the two boards Game.tic(show=True) appends per tick
 // (Game.draw game.py:281-300, called at game.py:140-141 and 194-195) for a list of recorded slots, drawn into a log in HBM.
 // One wavefront per recorded game.  Lane s holds snake s: where its head is drawn, the length it is sorted by, and the run of
@@ -2123,6 +2314,68 @@ extern "C" int snk_pit_script_values(const snk_engine *e, const int32_t *d_pairs
     else if (L.FW == 2) k_pit_script<2><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
     else k_pit_script<6><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
 #undef SCRIPT_ARGS
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_look_fanout(int S)
+{
+    if (S < 2 || S > SNK_MAX_SNAKES) return -1;
+    return look_pow3(S < 4 ? S : 4);
+}
+
+extern "C" long snk_pit_look_scratch_elems(int m, int S)
+{
+    const int F = snk_pit_look_fanout(S);
+    if (m < 0 || F < 0 || (long long)m * F > LK_MAX_LEAVES) return -1;
+    return look_scratch(m, S, F).total;
+}
+
+extern "C" int snk_pit_look_values(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags,
+                                   int32_t *d_scratch, float *d_q, void *stream)
+{
+    SNK_REQUIRE(e != nullptr && sub != nullptr, "snk_pit_look_values: engine is NULL");
+    SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
+                "snk_pit_look_values: unknown flag bits in 0x%x", flags);
+    SNK_REQUIRE(m >= 0, "snk_pit_look_values: m=%d", m);
+    SNK_REQUIRE(sub != e, "snk_pit_look_values: the sub-engine is the engine itself");
+    SNK_REQUIRE(e->L.H == sub->L.H && e->L.W == sub->L.W && e->L.S == sub->L.S, "snk_pit_look_values: geometry mismatch");
+    SNK_REQUIRE(e->device == sub->device, "snk_pit_look_values: the engines are on devices %d and %d", e->device, sub->device);
+    SNK_REQUIRE(sub->food_chance == 0.0 && sub->health_dec == e->health_dec,
+                "snk_pit_look_values: the sub-engine must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)",
+                sub->food_chance, e->health_dec, sub->health_dec);
+    if (m == 0) return 0;
+    SNK_REQUIRE(d_pairs && d_scratch && d_q, "snk_pit_look_values: NULL argument");
+    const Layout L = e->L;
+    const int F = snk_pit_look_fanout(L.S);
+    SNK_REQUIRE((long long)m * F <= LK_MAX_LEAVES, "snk_pit_look_values: m=%d rows of fanout %d exceed %d leaves", m, F, LK_MAX_LEAVES);
+    const int need = m < e->n_slots ? m : e->n_slots;
+    SNK_REQUIRE((long long)need * F <= sub->n_slots, "snk_pit_look_values: %d groups of fanout %d exceed the sub-engine's %d slots", need,
+                F, sub->n_slots);
+    const int n_groups = m < sub->n_slots / F ? m : sub->n_slots / F;
+    const LookScratch P = look_scratch(m, L.S, F);
+    int32_t *tile_sums = d_scratch + P.tile_sums, *row_group = d_scratch + P.row_group;
+    int32_t *grp_src = d_scratch + P.grp_src, *grp_bits = d_scratch + P.grp_bits, *leaf_pairs = d_scratch + P.leaf_pairs;
+    uint8_t *active = (uint8_t *)(d_scratch + P.active), *moves = (uint8_t *)(d_scratch + P.moves);
+    float *leaf_q = (float *)(d_scratch + P.leaf_q), *fb_q = (float *)(d_scratch + P.fb_q);
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = (m + PIT_TILE - 1) / PIT_TILE;
+    int32_t *count = tile_sums + tiles;
+    k_look_count<<<tiles, CMP_THREADS, 0, st>>>(d_pairs, m, tile_sums);
+    k_cmp_scan<<<1, CMP_THREADS, 0, st>>>(tile_sums, tiles, count);
+    k_look_groups<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, L, e->n_slots, d_pairs, m, tile_sums, count, n_groups, row_group, grp_src,
+                                                grp_bits);
+    k_look_fan<<<(m * F + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(m, F, L.S, n_groups, d_pairs, row_group, grp_bits, active,
+                                                                           moves, leaf_pairs);
+    SNK_CHECK_HIP(hipGetLastError());
+    // the children: Game.subgame of every group's slot F times, one tick of the active ones, s's plain scores on each
+    int rc = snk_engine_clone(e, grp_src, n_groups, sub, nullptr, F, stream);
+    if (rc == 0) rc = snk_engine_step_active(sub, active, n_groups * F, moves, nullptr, nullptr, stream);
+    if (rc == 0) rc = snk_pit_script_values(sub, leaf_pairs, m * F, flags, leaf_q, stream);
+    if (rc == 0) rc = snk_pit_script_values(e, d_pairs, m, flags, fb_q, stream);
+    if (rc != 0) return rc;
+    k_look_reduce<<<(4 * m + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(sub->d_state, L, m, F, n_groups, d_pairs, row_group,
+                                                                              grp_bits, leaf_q, fb_q, d_q);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

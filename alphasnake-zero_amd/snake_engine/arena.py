@@ -40,6 +40,9 @@ Or a side is a ``Scripted``: the flood-fill heuristic snake every Battlesnake pr
 policy -- the reference has none; include/snake_engine.h states it, tests/script_ref.py restates it in plain Python).  It costs no
 weights and is the same opponent in every run.  It counts as a greedy side; the observe launch and the nets run over the other
 sides' rows only (one observe per run of consecutive nets), and ``Scripted`` against ``Scripted`` launches neither.
+``Lookahead`` is a ``Scripted`` one tick deep, the second fixed point above the first: snk_pit_look_values plays every joint move
+of the up to four snakes alive on copies of the game in a sub-engine the side owns, scores the copies with the plain script and
+folds them into three scores per row on the device -- launches only, so the turn's read-back stays the one it is.
 
 ``record(games)`` returns a ``replay.Replay`` that the next match fills with the boards Game.tic(show=True) draws for those games
 (game.py:140-141, 194-195): snk_pit_record_moves before the step and snk_pit_record_boards after it draw them into a log on the
@@ -147,6 +150,55 @@ class Scripted:
         m = int(pairs.shape[0])
         q = engine.new((m, 3), torch.float32)
         check(engine.L.snk_pit_script_values(engine.h, _ptr(pairs), m, self.flags, _ptr(q), _stream()))
+        return q
+
+
+LOOK_SLOT_BUDGET = 4096 * 4 * 81     # rows times fanout of one snk_pit_look_values call: a 4 096-game 11x11x4 match, every seat
+
+
+class Lookahead(Scripted):
+    """The scripted policy one tick deep (include/snake_engine.h states it): every joint move of the up to four snakes alive is
+    played on a copy of the game, the copies are scored by the plain script, and a move scores what the worst reply leaves --
+    or, when a reply can kill, minus the number of ways to die.  The same flags and refusals as Scripted, and it sits wherever a
+    Scripted can (mixed_values asks isinstance(side, Scripted)); a Searcher around it is a TypeError.  It owns a sub-engine
+    without food spawning for the copies and the scratch of snk_pit_look_values, made at first use, remade when the geometry or
+    the device changes, and grown when more rows arrive; the sub-engine holds min(rows, games) * fanout slots and a call takes
+    at most LOOK_SLOT_BUDGET // fanout rows, so it never exceeds LOOK_SLOT_BUDGET slots."""
+
+    def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD):
+        super().__init__(flags)
+        self._sub = self._scratch = None
+
+    def _buffers(self, engine, rows, F):
+        """the sub-engine and the scratch for a call of `rows` rows"""
+        sub = self._sub
+        key = (engine.H, engine.W, engine.S, engine.health_dec, engine.device)
+        if sub is None or (sub.H, sub.W, sub.S, sub.health_dec, sub.device) != key:
+            sub = self._scratch = None
+        slots = min(rows, engine.n_slots) * F
+        if sub is None or sub.n_slots < slots:
+            if sub is not None:
+                sub.close()
+            sub = Engine(slots, engine.H, engine.W, engine.S, engine.health_dec, 0, seed=0, device=engine.device.index)
+        elems = engine.L.snk_pit_look_scratch_elems(rows, engine.S)
+        if elems < 0:
+            raise EngineError(f"no lookahead scratch for {rows} rows of {engine.S} snakes")
+        if self._scratch is None or self._scratch.numel() < elems:
+            self._scratch = engine.new((elems,), torch.int32)
+        self._sub = sub
+        return sub, self._scratch
+
+    def q_rows(self, engine, pairs):
+        """pairs int32[rows][2] (slot, snake id) on the device -> the three move scores float32[rows][3] on the device"""
+        m = int(pairs.shape[0])
+        q = engine.new((m, 3), torch.float32)
+        F = engine.L.snk_pit_look_fanout(engine.S)
+        per = max(LOOK_SLOT_BUDGET // F, 1)           # a boundary inside a game is harmless: the game is cloned again
+        for lo in range(0, m, per):
+            cnt = min(per, m - lo)
+            sub, scratch = self._buffers(engine, cnt, F)
+            check(engine.L.snk_pit_look_values(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, _ptr(scratch),
+                                               _ptr(q[lo:lo + cnt]), _stream()))
         return q
 
 

@@ -60,7 +60,9 @@ const char *snk_last_error(void);
                              * snk_pit_rows_owned, snk_pit_verdict_owned) and the searching league's (snk_pit_roots_owned,
                              * snk_pit_search_moves_owned) and the scripted opponent's (snk_pit_script_values) and the replay
                              * recorder's (snk_pit_record_stride, snk_pit_record_slots, snk_pit_record_moves,
-                             * snk_pit_record_boards) and the tally's (snk_pit_tally): no argument list of an older one changed */
+                             * snk_pit_record_boards) and the tally's (snk_pit_tally) and the lookahead opponent's
+                             * (snk_pit_look_fanout, snk_pit_look_scratch_elems, snk_pit_look_values): no argument list of an
+                             * older one changed */
 int snk_version(void);
 
 /* ---- engine lifetime -------------------------------------------------------------------
@@ -600,6 +602,44 @@ int snk_pit_search_moves_owned(const uint8_t *d_found, const int32_t *d_rank, in
 #define SNK_SCRIPT_HEADS 2u
 #define SNK_SCRIPT_FOOD 4u
 int snk_pit_script_values(const snk_engine *e, const int32_t *d_pairs, int m, uint32_t flags, float *d_q, void *stream);
+
+/* ---- the lookahead opponent: the scripted policy one tick deep, a second fixed yardstick (the project's own, as above) -----------
+ * snake_engine.arena.Lookahead sits wherever a Scripted can; tests/look_ref.py is the statement in plain Python.  Integers only.
+ * For row (slot g, snake s), s alive, in a game with A snakes alive (ids ascending: k = 0 .. A-1), and F = 3^min(S, 4):
+ *   fallback  A < 2 (the step does not move such a game) or A > 4 (the fanout is too large): the row gets exactly what
+ *             snk_pit_script_values gives it with the same flags
+ *   children  child j, 0 <= j < 3^A: a copy of the game as snk_engine_clone makes it (Game.subgame game.py:266-276), stepped once
+ *             as snk_engine_step_active steps it on an engine whose food spawn chance is 0; the k-th alive snake makes relative
+ *             move (j / 3^k) % 3, the move entries of dead snakes are 1
+ *   leaf      the value of s in child c: DEAD when s is not alive in c; WIN = 2^24 when s is alive and no other snake is;
+ *             otherwise the largest of s's three plain script scores on c with the same flags (-1 .. 2^24 - 1)
+ *   score     of own move a, over the 3^(A-1) children in which s's digit is a: when s is alive in all of them the smallest leaf
+ *             value -- the worst reply; teammates count as repliers, the policy is seat-selfish as the plain one is --, otherwise
+ *             -2 - (the number of those children in which s is dead), -3 .. -29: a move that can be punished ranks below every
+ *             move that cannot, and of two that can the one with fewer ways to die ranks higher
+ * Every value lies in [-29, 2^24] and is exact as float32; snk_pit_moves turns the scores into a move with its strict
+ * comparisons, and that tie order is part of the policy.  A pair that names a dead snake, or a slot outside 0..n_slots-1 or a
+ * snake id outside 0..S-1, gets -1, -1, -1.
+ * Rows of one slot that stand next to each other form a group and share one set of children; a new group starts at row 0 and
+ * wherever the slot differs from the previous row's, so the lists of snk_pit_rows / snk_pit_rows_owned and any contiguous slice
+ * of them have one group per game and team or owner, and a list that repeats a slot later only clones it again.  Group i uses
+ * slots i*F .. i*F + F-1 of `sub`.  The number of groups is known on the device only: THE ROWS OF A GROUP WHOSE INDEX IS
+ * sub's n_slots / F OR MORE GET -1, -1, -1 (that cannot be reported without a read-back); a list with at most one group per slot
+ * of e never has one, since the call refuses a sub-engine of fewer than min(m, n_slots of e) * F slots.
+ * snk_pit_look_fanout(S): F, -1 for S outside 2..8.  snk_pit_look_scratch_elems(m, S): the int32 elements of d_scratch for m rows,
+ *   -1 for m < 0, an S outside 2..8 or m * F above 2^28.
+ * snk_pit_look_values: sub has e's geometry, device and health_dec, spawns no food (chance 0) and is not e; its records are
+ *   overwritten, e's are only read.  Launches only, all on `stream`: the plan (a block scan over the rows in three launches, no
+ *   atomics: each row's group, each group's source slot -- a group past the last one points at slot 0 and is inactive --, then per
+ *   child its active flag and dense moves uint8[groups * F][S], and the leaf pair list), snk_engine_clone, snk_engine_step_active
+ *   and snk_pit_script_values on sub, snk_pit_script_values on e for the fallback rows, and the reduce (a quad of lanes per row).
+ *   No host synchronisation, no read-back, every output cell has one writer.  d_q float32[m][3], nothing past row m is written.
+ *   m == 0 is a no-op that accepts NULL buffers; a NULL array, m < 0, a flag bit outside the three, m * F above 2^28, a geometry,
+ *   device or health_dec mismatch, a sub-engine that spawns food or is too small is an error before any launch.                */
+int snk_pit_look_fanout(int S);
+long snk_pit_look_scratch_elems(int m, int S);
+int snk_pit_look_values(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int32_t *d_scratch,
+                        float *d_q, void *stream);
 
 /* ---- replays of chosen games of a pit match (Game.draw game.py:281-300, called by Game.tic game.py:140-141 and 194-195) ----------
  * snake_engine.replay.Replay: the two boards Game.tic(show=True) appends per tick, drawn by kernels into a log in device memory for

@@ -16,7 +16,9 @@ League.play_search against one Arena.match of two Searchers per ordered pair); t
 of the searches (Searcher.stats) and, since a searching turn is bound by them, the microseconds per evaluation.
 --baseline [FLAGS ...]: scripted owners (snake_engine.arena.Scripted, the fixed yardstick: the same opponent in every run) join the
 table and the ratings behind the nets, one per FLAGS value (bits 1 space, 2 heads, 4 food; no value: 7, the whole policy).  A
-scripted owner moves by its script under --search too.  --nets 0 --baseline 0 1 3 7 is the round robin of four flag settings.
+value look or lookN is the lookahead yardstick (snake_engine.arena.Lookahead: the script one tick deep) with flags 7 or N.  A
+scripted owner moves by its script under --search too.  --nets 0 --baseline 0 1 3 7 is the round robin of four flag settings,
+--nets 0 --baseline 0 1 3 7 look the same with the lookahead in it.
 --replay K DIR (not with --time): the round robin records its first K games (League.record) and writes them as DIR/game_<g>.rep,
 the text of the reference's replay.rep: two boards per tick.
 --tally (not with --time): the round robin also counts every seat's fate on the device (League.tally) and the table is printed
@@ -58,13 +60,13 @@ def main():
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--log", default=None)
-    ap.add_argument("--baseline", nargs="*", type=int, default=None, metavar="FLAGS")
+    ap.add_argument("--baseline", nargs="*", default=None, metavar="FLAGS")
     ap.add_argument("--replay", nargs=2, default=None, metavar=("K", "DIR"))
     ap.add_argument("--tally", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import torch
-    from snake_engine.arena import Arena, Scripted, Searcher
+    from snake_engine.arena import Arena, Lookahead, Scripted, Searcher
     from snake_engine.league import SEATS, League, ratings, schedule, searchers, table
     from snake_engine.net import glorot_uniform_weights
     from utils.alpha_nnet import AlphaNNet
@@ -102,10 +104,14 @@ def main():
     if not a.search:                                # a searcher talks to its net's range guard directly: no wrapper in between
         nets = [Counted(net) for net in nets]
     if a.baseline is not None:
-        for flags in a.baseline or [7]:
-            names.append(f"script{flags}")
-            nets.append(Scripted(flags))
-        what += f" and {len(a.baseline or [7])} scripted owners"
+        for flags in a.baseline or ["7"]:
+            if flags.startswith("look"):            # look, look5: the lookahead yardstick
+                names.append(f"look{int(flags[4:] or 7)}")
+                nets.append(Lookahead(int(flags[4:] or 7)))
+            else:
+                names.append(f"script{int(flags)}")
+                nets.append(Scripted(int(flags)))
+        what += f" and {len(a.baseline or ['7'])} scripted owners"
     K, S = len(nets), SEATS[a.seats]
     owner = schedule(K, a.games, a.seats)
     prop = torch.cuda.get_device_properties(0)

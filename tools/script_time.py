@@ -4,9 +4,11 @@
 
 kernel: HIP-event time of one snk_pit_script_values launch over the first 16 384 alive rows of 11x11x4 boards and the first 4 096
 of 19x19x8 boards, both taken from games the script itself has played for 20 turns (mid-game bodies, some snakes dead), beside the
-observe launch plus a --blocks-block forward over the same rows; medians of --reps launches after one that is not timed.
-match: ms per turn of Arena.match(Scripted, Scripted) beside greedy net against greedy net (1 v 3, 11x11), alternating inside this
-one process, --pairs times; a host clock around a match that ends in a device synchronise."""
+observe launch plus a --blocks-block forward over the same rows; medians of --reps launches after one that is not timed.  Beside it
+one snk_pit_look_values call (snake_engine.arena.Lookahead: its plan, the clone, step and script launches on the sub-engine and
+the reduce) over the same rows.
+match: ms per turn of Arena.match(Scripted, Scripted) beside Lookahead against Lookahead and greedy net against greedy net (1 v 3,
+11x11), alternating inside this one process, --pairs times; a host clock around a match that ends in a device synchronise."""
 import argparse
 import os
 import statistics
@@ -30,7 +32,7 @@ def main():
     import torch
     from snake_engine import Engine
     from snake_engine._lib import check
-    from snake_engine.arena import Arena, Scripted
+    from snake_engine.arena import Arena, Lookahead, Scripted
     from snake_engine.engine import _ptr, _stream
     from snake_engine.net import glorot_uniform_weights
     from utils.alpha_nnet import AlphaNNet
@@ -45,7 +47,7 @@ def main():
     prop = torch.cuda.get_device_properties(0)
     say(f"script_time: {torch.cuda.get_device_name(0)} ({prop.gcnArchName}, {prop.multi_processor_count} CUs), ROCm / HIP "
         f"{torch.version.hip}, torch {torch.__version__}")
-    script = Scripted()
+    script, look = Scripted(), Lookahead()
 
     def events(fn):
         fn()
@@ -80,19 +82,25 @@ def main():
             return net.v_device(planes, mask)
         forward()
         k = events(lambda: script.q_rows(eng, pairs))
+        look.q_rows(eng, pairs)                      # the sub-engine and the scratch are made outside the timing
+        la = events(lambda: look.q_rows(eng, pairs))
         o = events(lambda: eng.observe_all(pairs, want_key=False))
         f = events(forward)
         say(f"kernel: {hw}x{hw}x{S}, {rows} rows of {n} games after 20 scripted turns ({m} alive rows): snk_pit_script_values "
             f"{k[0]:.1f} us (min {k[1]:.1f}, max {k[2]:.1f}); observe alone {o[0]:.1f} us; observe + {a.blocks}-block forward "
             f"{f[0]:.1f} us (min {f[1]:.1f}, max {f[2]:.1f}); ratio {f[0] / k[0]:.1f}x")
+        say(f"kernel: {hw}x{hw}x{S}, the same {rows} rows: snk_pit_look_values {la[0]:.1f} us (min {la[1]:.1f}, max {la[2]:.1f}), "
+            f"{la[0] / k[0]:.1f}x snk_pit_script_values; sub-engine of {look._sub.n_slots} slots")
 
     nets = [AlphaNNet(input_shape=(21, 21, 3), _weights=glorot_uniform_weights((21, 21, 3), a.blocks, seed=s)) for s in (1, 2)]
     Arena(11, 11, 4, 1, 64, 99).match(nets[0], nets[1], 1)             # first launches, plans and range-guard scales settle outside the timing
     Arena(11, 11, 4, 1, 64, 99).match(script, Scripted(), 1)
+    looks = (Lookahead(), Lookahead())
     for n in a.games:
-        per = {"script v script": [], "net v net": []}
+        Arena(11, 11, 4, 1, n, 99).match(looks[0], looks[1], 1)        # their sub-engines grow to this size outside the timing
+        per = {"script v script": [], "look v look": [], "net v net": []}
         for k in range(a.pairs):
-            for name, sides in (("script v script", (script, Scripted())), ("net v net", nets)):
+            for name, sides in (("script v script", (script, Scripted())), ("look v look", looks), ("net v net", nets)):
                 arena = Arena(11, 11, 4, 1, n, seed=7)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -102,8 +110,9 @@ def main():
                 per[name].append(dt / res.turns * 1e3)
                 say(f"match: games {n:5d} pair {k} {name}: {res.turns:4d} turns, {dt:7.3f} s, {dt / res.turns * 1e3:7.3f} ms per turn, "
                     f"wins {res.wins_a}-{res.wins_b}, draws {res.draws}")
-        s, g = statistics.median(per["script v script"]), statistics.median(per["net v net"])
-        say(f"match: games {n:5d} median ms per turn: script v script {s:.3f}, net v net {g:.3f}, ratio {g / s:.2f}x")
+        s, g, lk = (statistics.median(per[k]) for k in ("script v script", "net v net", "look v look"))
+        say(f"match: games {n:5d} median ms per turn: script v script {s:.3f}, look v look {lk:.3f}, net v net {g:.3f}; net / script "
+            f"{g / s:.2f}x, look / script {lk / s:.2f}x")
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 (snake_engine.arena.Searcher) and a greedy side of the SAME net, 11x11.
 
     python tools/search_pit.py [--games 300] [--breadth 16] [--depth 8] [--blocks 4] [--weights CKPT] [--seed 1]
-                               [--time] [--pairs 2] [--log profiles/arena_search.log] [--baseline] [--replay K DIR] [--tally]
+                               [--time] [--pairs 2] [--log profiles/arena_search.log] [--baseline [script|look]] [--replay K DIR] [--tally]
 
 Strength (default): 1 v 3 with the searcher alone, 1 v 3 with the searcher's three against the greedy one, and the duel; win and
 draw rates of the searching side with their binomial 95 % intervals (Wilson), ms per turn and net evaluations per turn.
@@ -11,7 +11,8 @@ one process, `--pairs` times; ms per turn (host clock around a match that ends i
 turn, and the host time DeviceMCTS._ensure took (its buffers are made again whenever the number of open games changes).
 --baseline: the net against the scripted opponent (snake_engine.arena.Scripted with the whole policy, the fixed yardstick) instead
 of against itself: the greedy net in the duel and in 1 v 3 both ways, then the net moving by search in the duel; the net side's
-win and draw rates with the same intervals.
+win and draw rates with the same intervals.  --baseline look: the same against the lookahead yardstick
+(snake_engine.arena.Lookahead: the script one tick deep).
 --replay K DIR: the first match the run reports (strength or --baseline) records its first K games (Arena.record) and writes them
 as DIR/game_<g>.rep, the text of the reference's replay.rep: two boards per tick.
 --tally: the first match the run reports also counts every seat's fate on the device (Arena.tally) and prints the table: per side
@@ -51,12 +52,12 @@ def main():
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--pairs", type=int, default=2)
     ap.add_argument("--log", default=None)
-    ap.add_argument("--baseline", action="store_true")
+    ap.add_argument("--baseline", nargs="?", const="script", choices=("script", "look"), default=None)
     ap.add_argument("--replay", nargs=2, default=None, metavar=("K", "DIR"))
     ap.add_argument("--tally", action="store_true")
     a = ap.parse_args()
     import torch
-    from snake_engine.arena import Arena, Scripted, Searcher
+    from snake_engine.arena import Arena, Lookahead, Scripted, Searcher
     from snake_engine.mcts import DeviceMCTS
     from snake_engine.net import glorot_uniform_weights
     from utils.alpha_nnet import AlphaNNet
@@ -139,8 +140,8 @@ def main():
     play(4, 1, (True, False), 8, 99)                       # first launches, plans and range-guard scales settle outside the timing
     play(4, 1, (False, False), 8, 99)
     if a.baseline:
-        script = Scripted()
-        lineups = [("duel, the net first", 2, 1, 0), ("1v3, the net alone", 4, 1, 0), ("1v3, three of the net against the script", 4, 3, 0)]
+        script, who_b = (Lookahead(), "lookahead") if a.baseline == "look" else (Scripted(), "script")
+        lineups = [("duel, the net first", 2, 1, 0), ("1v3, the net alone", 4, 1, 0), (f"1v3, three of the net against the {who_b}", 4, 3, 0)]
         movers = [("greedy net", None, lineups)] + [(f"search breadth {b:3d}", b, lineups[:1]) for b in a.breadth]
         for mover, breadth, ups in movers:
             for i, (name, snakes, a_cnt, who) in enumerate(ups):
@@ -153,11 +154,11 @@ def main():
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
                 write_replay(rep)
-                write_tally(tal, ["net", "script"])
+                write_tally(tal, ["net", who_b])
                 wins = (res.wins_a, res.wins_b)[who]
                 (wl, wh), (dl, dh) = wilson(wins, a.games), wilson(res.draws, a.games)
-                say(f"baseline: {mover} against the script, {name}: net wins {wins / a.games:.3f} [{wl:.3f}, {wh:.3f}], draws "
-                    f"{res.draws / a.games:.3f} [{dl:.3f}, {dh:.3f}], script wins {(a.games - wins - res.draws) / a.games:.3f}; "
+                say(f"baseline: {mover} against the {who_b}, {name}: net wins {wins / a.games:.3f} [{wl:.3f}, {wh:.3f}], draws "
+                    f"{res.draws / a.games:.3f} [{dl:.3f}, {dh:.3f}], {who_b} wins {(a.games - wins - res.draws) / a.games:.3f}; "
                     f"{res.turns} turns, {dt / res.turns * 1e3:.3f} ms per turn")
     elif a.time:
         forms = [("greedy v greedy", (False, False)), ("search v greedy", (True, False)), ("search v search", (True, True))]
