@@ -1775,6 +1775,192 @@ __global__ __launch_bounds__(CMP_THREADS) void k_look_reduce(const uint8_t *__re
 }
 
 // ------------------------------------------------------------------------------------------
+// the deep opponent of the pit (snake_engine.arena.Deep, snk_pit_deep_values): the scripted policy `depth` ticks deep, a paranoid
+// fixed-depth search over the lookahead's children.  include/snake_engine.h states the policy, tests/deep_ref.py restates it in
+// plain Python.  Depth 1 IS snk_pit_look_values (the entry point calls it).  From depth 2 on the rows are grouped by the
+// lookahead's scan (k_look_count / k_cmp_scan / k_look_groups), and the tree of a group stands in one sub-engine per level:
+// node c of level k (slot c of subs[k-1]) is child c % F of node c / F of level k - 1; level 0 is the group's game.  What is new:
+//   k_deep_fan      a thread per node of a level, after the level above has been stepped: the node is active when its parent is
+//                   and has 2..4 snakes alive and the node's index is below 3^alive; its dense moves are the digits of that index
+//   k_deep_leaves   a thread per (row, node of the last level): the pair (slot, s) the script kernel scores, (-1, -1) where the
+//                   node is not active -- the only list that is per row; clones, flags and moves are per node, shared by the rows
+//   k_deep_reduce   a quad of lanes per (row, node of the level above), lane a scores own move a over the node's children in
+//                   which s's digit is a; the largest of the three goes to the level above, the three of level 0 are the result
+// k_clone, the step kernels and k_pit_script do the rest, launched through their entry points.  Every cell of every array has one
+// writer, nothing is read back, there are no atomics, and all per-thread state is scalar.  A node that is not active holds a
+// stale record; no kernel reads it: the reduce visits the children of an active node with 2..4 alive only, and only the first
+// 3^alive of them, which are the active ones.  Every node index is compared with its sub-engine's n_slots before it is used.
+// ------------------------------------------------------------------------------------------
+#define DP_MAX_DEPTH 4
+#define DP_MAX_FANOUT 6561                       // F^depth: 3^8
+
+struct DeepScratch {
+    long tile_sums, row_group, grp_src, grp_bits;     // as LookScratch
+    long fb_q;                      // float[m][3]          the plain scores of the rows themselves
+    long active[DP_MAX_DEPTH];      // uint8[m * F^k]       level k's flags for the step
+    long moves[DP_MAX_DEPTH];       // uint8[m * F^k][S]
+    long best[DP_MAX_DEPTH];        // float[m * F^k]       per (row, node of level k < depth): the best of s's three scores there
+    long leaf_pairs;                // int32[m * F^depth][2]
+    long leaf_q;                    // float[m * F^depth][3]
+    long total;
+};
+
+static DeepScratch deep_scratch(long m, int S, int F, int depth)
+{
+    auto up4 = [](long v) { return (v + 3) / 4 * 4; };
+    DeepScratch P;
+    memset(&P, 0, sizeof(P));
+    long at = 0, n = m;
+    P.tile_sums = at;  at += up4((m + PIT_TILE - 1) / PIT_TILE + 1);
+    P.row_group = at;  at += up4(m);
+    P.grp_src = at;    at += up4(m);
+    P.grp_bits = at;   at += up4(m);
+    P.fb_q = at;       at += up4(3 * m);
+    for (int k = 0; k < depth; ++k) {
+        n *= F;
+        P.active[k] = at;  at += up4((n + 3) / 4);
+        P.moves[k] = at;   at += up4((n * S + 3) / 4);
+        if (k + 1 < depth) { P.best[k] = at;  at += up4(n); }
+    }
+    P.leaf_pairs = at; at += up4(2 * n);
+    P.leaf_q = at;     at += up4(3 * n);
+    P.total = at;
+    if (depth == 1) { const long look = look_scratch(m, S, F).total; if (look > P.total) P.total = look; }
+    return P;
+}
+
+// bit s = snake s of a record is alive
+__device__ static inline uint32_t deep_alive_bits(const uint8_t *__restrict__ state, const Layout &L, int slot)
+{
+    const SnakeMeta *meta = (const SnakeMeta *)(state + (size_t)slot * L.stride + L.meta_off);
+    uint32_t bits = 0u;
+    for (int s = 0; s < L.S; ++s) bits |= (meta[s].alive ? 1u : 0u) << s;
+    return bits;
+}
+
+// thread t < n_nodes is node t of a level: child j = t % F of parent p = t / F.  par_state == nullptr: level 1, the parent is
+// group p and grp_bits[p] its alive bits (0 for a group that is not looked ahead).  Otherwise the parent is slot p of the
+// sub-engine above, after its step: a parent that was not active, or in which the game is over, has no children
+__global__ __launch_bounds__(CMP_THREADS) void k_deep_fan(int n_nodes, int F, const int32_t *__restrict__ grp_bits,
+                                                         const uint8_t *__restrict__ par_state, Layout L, int par_slots,
+                                                         const uint8_t *__restrict__ par_active, uint8_t *__restrict__ active,
+                                                         uint8_t *__restrict__ moves)
+{
+    const int t = blockIdx.x * CMP_THREADS + threadIdx.x;
+    if (t >= n_nodes) return;
+    const int p = t / F, j = t - p * F;
+    uint32_t bits = 0u;
+    if (par_state == nullptr) bits = (uint32_t)grp_bits[p];
+    else if (p < par_slots && par_active[p]) bits = deep_alive_bits(par_state, L, p);
+    const int A = __popc(bits);
+    const bool act = A >= 2 && A <= 4 && j < look_pow3(A);
+    active[t] = act ? 1 : 0;
+    int d = j;
+    for (int s = 0; s < L.S; ++s) {
+        int mv = 1;
+        if (act && ((bits >> s) & 1u)) { mv = d % 3; d /= 3; }
+        moves[(size_t)t * L.S + s] = (uint8_t)mv;
+    }
+}
+
+// thread t < m * FD is node l = t % FD of the last level of the tree of row t / FD: the pair (its slot, s) when the row is
+// searched and the node active, else (-1, -1), which the script kernel scores -1, -1, -1 without walking anything
+__global__ __launch_bounds__(CMP_THREADS) void k_deep_leaves(int m, int FD, int S, int n_groups, int leaf_slots,
+                                                            const int32_t *__restrict__ pairs, const int32_t *__restrict__ row_group,
+                                                            const int32_t *__restrict__ grp_bits, const uint8_t *__restrict__ active,
+                                                            int32_t *__restrict__ leaf_pairs)
+{
+    const int t = blockIdx.x * CMP_THREADS + threadIdx.x;
+    const int row = t / FD, l = t - row * FD;
+    if (row >= m) return;
+    const int s = pairs[2 * (size_t)row + 1], grp = row_group[row];
+    bool ok = false;
+    int node = -1;
+    if (grp < n_groups && s >= 0 && s < S && (((uint32_t)grp_bits[grp] >> s) & 1u)) {
+        node = grp * FD + l;                              // n_groups * FD <= leaf_slots <= 2^28
+        ok = node < leaf_slots && active[node];
+    }
+    leaf_pairs[2 * (size_t)t] = ok ? node : -1;
+    leaf_pairs[2 * (size_t)t + 1] = ok ? s : -1;
+}
+
+// the fold of level k into level k - 1.  A quad of lanes per (row, parent), P = F^(k-1) parents per row; lane a < 3 scores own
+// move a at the parent over the 3^(A-1) children in which s's digit is a: the smallest child value when s lives in all of them,
+// else -2 - (the children in which s is dead) - penalty, penalty = 32 * (the ticks below this level).  A child's value is 2^24
+// when s alone is left in it, else what the level below stored for (row, child) -- at the last level (leaf_q != nullptr) the
+// largest of s's three plain scores.  A parent is folded when it is active, s is alive in it and 2..4 snakes are.
+//   P > 1 (par_state != nullptr): the largest of the three scores goes to best_out[row * P + parent], 0 for a parent not folded
+//         (nothing reads that cell); the quad's lanes exchange their scores by two shuffles, which every lane of the wave runs
+//   P == 1: the parent is the row's game.  q[row][a] = the score; the row's plain score fb_q when the row is not searched (a dead
+//         or out-of-range pair, A < 2, A > 4); -1 when the row's group lies beyond the sub-engines
+__global__ __launch_bounds__(CMP_THREADS) void k_deep_reduce(const uint8_t *__restrict__ par_state, int par_slots,
+                                                            const uint8_t *__restrict__ par_active,
+                                                            const uint8_t *__restrict__ cur_state, int cur_slots, Layout L, int m, int F,
+                                                            int P, int n_groups, float penalty, const int32_t *__restrict__ pairs,
+                                                            const int32_t *__restrict__ row_group, const int32_t *__restrict__ grp_bits,
+                                                            const float *__restrict__ best_in, const float *__restrict__ leaf_q,
+                                                            const float *__restrict__ fb_q, float *__restrict__ best_out,
+                                                            float *__restrict__ q)
+{
+    const int t = blockIdx.x * CMP_THREADS + threadIdx.x;
+    const int quad = t >> 2, a = t & 3;
+    const int row = quad / P, pi = quad - row * P;
+    const bool in = row < m;
+    float val = -3.0e38f;
+    bool fold = false, served = false;
+    if (in) {
+        const int s = pairs[2 * (size_t)row + 1], grp = row_group[row];
+        served = grp < n_groups;
+        uint32_t bits = 0u;
+        int par = grp;                                    // the parent's node index: n_groups * P <= par_slots <= 2^28
+        if (served) {
+            if (par_state == nullptr) bits = (uint32_t)grp_bits[grp];
+            else {
+                par = grp * P + pi;
+                if (par < par_slots && par_active[par]) bits = deep_alive_bits(par_state, L, par);
+            }
+        }
+        const int A = __popc(bits);
+        fold = s >= 0 && s < L.S && ((bits >> s) & 1u) && A >= 2 && A <= 4;
+        if (fold && a < 3) {
+            const int p = look_pow3(__popc(bits & ((1u << s) - 1u)));        // the weight of s's digit
+            const int replies = look_pow3(A - 1);
+            const uint32_t others = bits & ~(1u << s);
+            const size_t mine = ((size_t)row * P + pi) * F;                  // the row's own index of the parent's child 0
+            int dead = 0;
+            float worst = LK_WIN;
+            for (int i = 0; i < replies; ++i) {
+                const int hi = i / p, j = hi * 3 * p + a * p + (i - hi * p);
+                const long long node = (long long)par * F + j;
+                if (node >= cur_slots) { ++dead; continue; }                 // never: the entry point sized the sub-engines
+                const SnakeMeta *meta = (const SnakeMeta *)(cur_state + (size_t)node * L.stride + L.meta_off);
+                if (!meta[s].alive) { ++dead; continue; }
+                bool alone = true;
+                for (uint32_t b = others; b; b &= b - 1u) alone &= !meta[__ffs((int)b) - 1].alive;
+                float leaf = LK_WIN;
+                if (!alone) {
+                    if (leaf_q) {
+                        const float *z = leaf_q + 3 * (mine + j);
+                        leaf = fmaxf(z[0], fmaxf(z[1], z[2]));
+                    } else {
+                        leaf = best_in[mine + j];
+                    }
+                }
+                worst = fminf(worst, leaf);
+            }
+            val = dead ? (float)(-2 - dead) - penalty : worst;
+        }
+    }
+    if (par_state != nullptr) {
+        float best = fmaxf(val, __shfl_xor(val, 1, 64));
+        best = fmaxf(best, __shfl_xor(best, 2, 64));
+        if (in && a == 0) best_out[(size_t)row * P + pi] = fold ? best : 0.0f;
+    } else if (in && a < 3) {
+        q[3 * (size_t)row + a] = !served ? -1.0f : fold ? val : fb_q[3 * (size_t)row + a];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // replays of chosen games of a pit match (snake_engine.replay.Replay): the two boards Game.tic(show=True) appends per tick
 // (Game.draw game.py:281-300, called at game.py:140-141 and 194-195) for a list of recorded slots, drawn into a log in HBM.
 // One wavefront per recorded game.  Lane s holds snake s: where its head is drawn, the length it is sorted by, and the run of
@@ -2376,6 +2562,108 @@ extern "C" int snk_pit_look_values(const snk_engine *e, snk_engine *sub, const i
     if (rc != 0) return rc;
     k_look_reduce<<<(4 * m + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(sub->d_state, L, m, F, n_groups, d_pairs, row_group,
                                                                               grp_bits, leaf_q, fb_q, d_q);
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_deep_fanout(int S, int depth)
+{
+    const int F = snk_pit_look_fanout(S);
+    if (F < 0 || depth < 1) return -1;
+    long p = 1;
+    for (int k = 0; k < depth; ++k) { p *= F; if (p > DP_MAX_FANOUT) return -1; }
+    return (int)p;
+}
+
+extern "C" long snk_pit_deep_scratch_elems(int m, int S, int depth)
+{
+    const int FD = snk_pit_deep_fanout(S, depth);
+    if (m < 0 || FD < 0 || (long long)m * FD > LK_MAX_LEAVES) return -1;
+    return deep_scratch(m, S, snk_pit_look_fanout(S), depth).total;
+}
+
+extern "C" int snk_pit_deep_values(const snk_engine *e, snk_engine *const *subs, int depth, const int32_t *d_pairs, int m,
+                                   uint32_t flags, int32_t *d_scratch, float *d_q, void *stream)
+{
+    SNK_REQUIRE(e != nullptr && subs != nullptr, "snk_pit_deep_values: engine is NULL");
+    SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
+                "snk_pit_deep_values: unknown flag bits in 0x%x", flags);
+    SNK_REQUIRE(m >= 0, "snk_pit_deep_values: m=%d", m);
+    const Layout L = e->L;
+    const int F = snk_pit_look_fanout(L.S), FD = snk_pit_deep_fanout(L.S, depth);
+    SNK_REQUIRE(FD > 0, "snk_pit_deep_values: depth %d with %d snakes (fanout %d) is outside 1 .. the depth at which it reaches %d", depth,
+                L.S, F, DP_MAX_FANOUT);
+    for (int k = 0; k < depth; ++k) {
+        const snk_engine *sub = subs[k];
+        SNK_REQUIRE(sub != nullptr, "snk_pit_deep_values: sub-engine %d is NULL", k);
+        SNK_REQUIRE(sub != e, "snk_pit_deep_values: sub-engine %d is the engine itself", k);
+        for (int o = 0; o < k; ++o) SNK_REQUIRE(sub != subs[o], "snk_pit_deep_values: sub-engines %d and %d are the same", o, k);
+        SNK_REQUIRE(L.H == sub->L.H && L.W == sub->L.W && L.S == sub->L.S, "snk_pit_deep_values: geometry mismatch of sub-engine %d", k);
+        SNK_REQUIRE(e->device == sub->device, "snk_pit_deep_values: the engine and sub-engine %d are on devices %d and %d", k, e->device,
+                    sub->device);
+        SNK_REQUIRE(sub->food_chance == 0.0 && sub->health_dec == e->health_dec,
+                    "snk_pit_deep_values: sub-engine %d must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)", k,
+                    sub->food_chance, e->health_dec, sub->health_dec);
+    }
+    if (m == 0) return 0;
+    SNK_REQUIRE(d_pairs && d_scratch && d_q, "snk_pit_deep_values: NULL argument");
+    SNK_REQUIRE((long long)m * FD <= LK_MAX_LEAVES, "snk_pit_deep_values: m=%d rows of fanout %d exceed %d leaves", m, FD, LK_MAX_LEAVES);
+    const int need = m < e->n_slots ? m : e->n_slots;
+    int n_groups = m;                                     // the groups every level can hold
+    {
+        long long pw = 1;
+        for (int k = 0; k < depth; ++k) {
+            pw *= F;
+            SNK_REQUIRE(need * pw <= subs[k]->n_slots, "snk_pit_deep_values: %d groups of fanout %lld exceed sub-engine %d's %d slots", need,
+                        pw, k, subs[k]->n_slots);
+            if (subs[k]->n_slots / pw < n_groups) n_groups = (int)(subs[k]->n_slots / pw);
+        }
+    }
+    if (depth == 1) return snk_pit_look_values(e, subs[0], d_pairs, m, flags, d_scratch, d_q, stream);
+    const DeepScratch P = deep_scratch(m, L.S, F, depth);
+    int32_t *tile_sums = d_scratch + P.tile_sums, *row_group = d_scratch + P.row_group;
+    int32_t *grp_src = d_scratch + P.grp_src, *grp_bits = d_scratch + P.grp_bits, *leaf_pairs = d_scratch + P.leaf_pairs;
+    float *leaf_q = (float *)(d_scratch + P.leaf_q), *fb_q = (float *)(d_scratch + P.fb_q);
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = (m + PIT_TILE - 1) / PIT_TILE;
+    int32_t *count = tile_sums + tiles;
+    k_look_count<<<tiles, CMP_THREADS, 0, st>>>(d_pairs, m, tile_sums);
+    k_cmp_scan<<<1, CMP_THREADS, 0, st>>>(tile_sums, tiles, count);
+    k_look_groups<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, L, e->n_slots, d_pairs, m, tile_sums, count, n_groups, row_group, grp_src,
+                                                grp_bits);
+    SNK_CHECK_HIP(hipGetLastError());
+    int rc = snk_pit_script_values(e, d_pairs, m, flags, fb_q, stream);
+    // level by level: the nodes' flags and moves from the stepped level above, Game.subgame of every node above F times, one tick
+    int nodes = n_groups;                                 // of the level above
+    for (int k = 0; k < depth && rc == 0; ++k) {
+        uint8_t *active = (uint8_t *)(d_scratch + P.active[k]), *moves = (uint8_t *)(d_scratch + P.moves[k]);
+        const snk_engine *par = k ? subs[k - 1] : nullptr;
+        k_deep_fan<<<(nodes * F + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(
+            nodes * F, F, grp_bits, par ? par->d_state : nullptr, L, par ? par->n_slots : 0,
+            k ? (const uint8_t *)(d_scratch + P.active[k - 1]) : nullptr, active, moves);
+        SNK_CHECK_HIP(hipGetLastError());
+        rc = k ? snk_engine_clone(par, nullptr, nodes, subs[k], nullptr, F, stream)
+               : snk_engine_clone(e, grp_src, nodes, subs[k], nullptr, F, stream);
+        nodes *= F;
+        if (rc == 0) rc = snk_engine_step_active(subs[k], active, nodes, moves, nullptr, nullptr, stream);
+    }
+    if (rc != 0) return rc;
+    k_deep_leaves<<<(m * FD + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(
+        m, FD, L.S, n_groups, subs[depth - 1]->n_slots, d_pairs, row_group, grp_bits, (const uint8_t *)(d_scratch + P.active[depth - 1]),
+        leaf_pairs);
+    SNK_CHECK_HIP(hipGetLastError());
+    rc = snk_pit_script_values(subs[depth - 1], leaf_pairs, m * FD, flags, leaf_q, stream);
+    if (rc != 0) return rc;
+    // the fold, from the last level up: level k + 1 (subs[k]) into level k
+    int per = FD / F;                                     // parents per row: F^k
+    for (int k = depth - 1; k >= 0; --k, per /= F) {
+        const snk_engine *par = k ? subs[k - 1] : nullptr;
+        k_deep_reduce<<<(int)((4LL * m * per + CMP_THREADS - 1) / CMP_THREADS), CMP_THREADS, 0, st>>>(
+            par ? par->d_state : nullptr, par ? par->n_slots : 0, k ? (const uint8_t *)(d_scratch + P.active[k - 1]) : nullptr,
+            subs[k]->d_state, subs[k]->n_slots, L, m, F, per, n_groups, 32.0f * (float)(depth - 1 - k), d_pairs, row_group, grp_bits,
+            k + 1 < depth ? (const float *)(d_scratch + P.best[k]) : nullptr, k + 1 < depth ? nullptr : leaf_q, fb_q,
+            k ? (float *)(d_scratch + P.best[k - 1]) : nullptr, d_q);
+    }
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -43,6 +43,8 @@ sides' rows only (one observe per run of consecutive nets), and ``Scripted`` aga
 ``Lookahead`` is a ``Scripted`` one tick deep, the second fixed point above the first: snk_pit_look_values plays every joint move
 of the up to four snakes alive on copies of the game in a sub-engine the side owns, scores the copies with the plain script and
 folds them into three scores per row on the device -- launches only, so the turn's read-back stays the one it is.
+``Deep`` is the same search several ticks deep, the third fixed point: snk_pit_deep_values keeps one sub-engine per tick, the
+children of a game shared by all its rows at every level, and folds the levels from the last one up -- launches only as well.
 
 ``record(games)`` returns a ``replay.Replay`` that the next match fills with the boards Game.tic(show=True) draws for those games
 (game.py:140-141, 194-195): snk_pit_record_moves before the step and snk_pit_record_boards after it draw them into a log on the
@@ -199,6 +201,67 @@ class Lookahead(Scripted):
             sub, scratch = self._buffers(engine, cnt, F)
             check(engine.L.snk_pit_look_values(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, _ptr(scratch),
                                                _ptr(q[lo:lo + cnt]), _stream()))
+        return q
+
+
+DEEP_BYTE_BUDGET = 1 << 30           # bytes of records in the sub-engines of one snk_pit_deep_values call, all levels together
+
+
+class Deep(Scripted):
+    """The scripted policy `depth` ticks deep (include/snake_engine.h states it): a fixed-depth paranoid search over the
+    lookahead's children.  A move scores what the worst replies of the next `depth` ticks leave; a move that can be punished now
+    ranks below every move that can only be punished later.  Deep(depth=1) is Lookahead bit for bit.  The same flags and refusals
+    as Scripted, and it sits wherever a Scripted can; a Searcher around it is a TypeError.  It owns `depth` sub-engines without
+    food spawning (level k holds min(rows, games) * fanout^k slots) and the scratch of snk_pit_deep_values, made at first use,
+    remade when the geometry or the device changes, and grown when more rows arrive.  A call takes as many rows as keep the
+    sub-engines' records within DEEP_BYTE_BUDGET bytes, at least one; a depth the board's snake count cannot have
+    (snk_pit_deep_fanout) is refused at first use."""
+
+    def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD, depth=2):
+        super().__init__(flags)
+        depth = int(depth)
+        if depth < 1:
+            raise ValueError(f"Deep depth {depth}: at least 1")
+        self.depth = depth
+        self._subs = self._scratch = self._handles = None
+
+    def _buffers(self, engine, rows, F):
+        """the sub-engines, the array of their handles and the scratch for a call of `rows` rows"""
+        subs = self._subs
+        key = (engine.H, engine.W, engine.S, engine.health_dec, engine.device)
+        if subs is not None and (subs[0].H, subs[0].W, subs[0].S, subs[0].health_dec, subs[0].device) != key:
+            for sub in subs:
+                sub.close()
+            subs = self._scratch = None
+        groups = min(rows, engine.n_slots)
+        if subs is None or subs[0].n_slots < groups * F:
+            for sub in subs or ():
+                sub.close()
+            subs = [Engine(groups * F ** k, engine.H, engine.W, engine.S, engine.health_dec, 0, seed=0, device=engine.device.index)
+                    for k in range(1, self.depth + 1)]
+            self._handles = torch.tensor([sub.h.value for sub in subs], dtype=torch.int64)       # snk_engine *[depth], on the host
+        elems = engine.L.snk_pit_deep_scratch_elems(rows, engine.S, self.depth)
+        if elems < 0:
+            raise EngineError(f"no deep scratch for {rows} rows of {engine.S} snakes at depth {self.depth}")
+        if self._scratch is None or self._scratch.numel() < elems:
+            self._scratch = engine.new((elems,), torch.int32)
+        self._subs = subs
+        return subs, self._handles, self._scratch
+
+    def q_rows(self, engine, pairs):
+        """pairs int32[rows][2] (slot, snake id) on the device -> the three move scores float32[rows][3] on the device"""
+        m = int(pairs.shape[0])
+        F, FD = engine.L.snk_pit_look_fanout(engine.S), engine.L.snk_pit_deep_fanout(engine.S, self.depth)
+        if FD < 0:
+            raise EngineError(f"Deep depth {self.depth} is too deep for {engine.S} snakes (fanout {F} a tick, at most 6561 in all)")
+        q = engine.new((m, 3), torch.float32)
+        per_row = engine.slot_bytes * sum(F ** k for k in range(1, self.depth + 1))
+        per = max(DEEP_BYTE_BUDGET // per_row, 1)     # a boundary inside a game is harmless: the game is cloned again
+        for lo in range(0, m, per):
+            cnt = min(per, m - lo)
+            subs, handles, scratch = self._buffers(engine, cnt, F)
+            check(engine.L.snk_pit_deep_values(engine.h, _ptr(handles), self.depth, _ptr(pairs[lo:lo + cnt]), cnt, self.flags,
+                                               _ptr(scratch), _ptr(q[lo:lo + cnt]), _stream()))
         return q
 
 

@@ -61,7 +61,8 @@ const char *snk_last_error(void);
                              * snk_pit_search_moves_owned) and the scripted opponent's (snk_pit_script_values) and the replay
                              * recorder's (snk_pit_record_stride, snk_pit_record_slots, snk_pit_record_moves,
                              * snk_pit_record_boards) and the tally's (snk_pit_tally) and the lookahead opponent's
-                             * (snk_pit_look_fanout, snk_pit_look_scratch_elems, snk_pit_look_values): no argument list of an
+                             * (snk_pit_look_fanout, snk_pit_look_scratch_elems, snk_pit_look_values) and the deep opponent's
+                             * (snk_pit_deep_fanout, snk_pit_deep_scratch_elems, snk_pit_deep_values): no argument list of an
                              * older one changed */
 int snk_version(void);
 
@@ -640,6 +641,51 @@ int snk_pit_look_fanout(int S);
 long snk_pit_look_scratch_elems(int m, int S);
 int snk_pit_look_values(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int32_t *d_scratch,
                         float *d_q, void *stream);
+
+/* ---- the deep opponent: the scripted policy several ticks deep, a third fixed yardstick (the project's own, as above) -----------
+ * snake_engine.arena.Deep(flags, depth) sits wherever a Scripted can; tests/deep_ref.py is the statement in plain Python.  Integers
+ * only.  A fixed-depth paranoid search over the lookahead's children: with F = snk_pit_look_fanout(S), for row (slot g, snake s),
+ * s alive, in a game with A snakes alive, V_k is the three scores of a search k ticks deep:
+ *   fallback  A < 2 or A > 4: exactly what snk_pit_script_values gives the row with the same flags, at every depth
+ *   V_1       exactly the three scores of snk_pit_look_values
+ *   V_k       k >= 2, children as above (3^A copies stepped once without food spawning, the i-th alive snake's digit (j / 3^i) % 3):
+ *     leaf_k(c)  DEAD when s is not alive in c; WIN = 2^24 when s is alive in c and no other snake is; otherwise the largest of
+ *                the three V_{k-1}(c, s, .) -- c has 2 .. A snakes alive, so the fallback is met at the root only
+ *     score      of own move a, over the 3^(A-1) children in which s's digit is a: the smallest leaf_k when s lives in all of
+ *                them, otherwise -2 - dead - 32 * (k - 1), dead = the number of those children in which s is dead
+ * V_k lies in [-32 (k-1) - 29, 2^24] and is exact as float32.  A move that can be punished now ranks below every move that can
+ * only be punished later, and of moves punishable at the same tick the one with fewer ways to die ranks higher.  snk_pit_moves
+ * turns the scores into a move with its strict comparisons, and that tie order is part of the policy.  A pair that names a dead
+ * snake, or a slot outside 0..n_slots-1 or a snake id outside 0..S-1, gets -1, -1, -1.
+ * snk_pit_deep_fanout(S, depth): F^depth; -1 for S outside 2..8, depth < 1 or F^depth > 6561 (depth <= 4 at S = 2, <= 2 from S = 3).
+ * snk_pit_deep_scratch_elems(m, S, depth): the int32 elements of d_scratch; -1 on those refusals, for m < 0 or m * F^depth above
+ *   2^28.  At depth 1 it is at least snk_pit_look_scratch_elems(m, S).
+ * snk_pit_deep_values: subs[k-1] holds level k of the trees, k = 1 .. depth; every sub-engine has e's geometry, device and
+ *   health_dec, spawns no food, and is neither e nor another of them; their records are overwritten, e's are only read.  Rows are
+ *   grouped as in snk_pit_look_values and the rows of a group share their children at EVERY level: node c of level k is slot c
+ *   of subs[k-1], child c % F of node c / F of level k-1, and level 0 is group i = the game itself, so level k of group i
+ *   occupies slots i*F^k .. of subs[k-1].  THE ROWS OF A GROUP WHOSE INDEX IS min over k of (n_slots of subs[k-1]) / F^k OR MORE
+ *   GET -1, -1, -1, as above; the call refuses sub-engines of fewer than min(m, n_slots of e) * F^k slots.  depth == 1 calls
+ *   snk_pit_look_values(e, subs[0], ...) and is therefore that call bit for bit.  From depth 2, launches only, all on `stream`:
+ *   the lookahead's scan (groups, source slots, alive bits), snk_pit_script_values on e for the fallback rows; per level the
+ *   fan (a thread per node: active when its parent is active, has 2..4 snakes alive after its step and the node's index is
+ *   below 3^alive -- so a child in which the game is over, or past the last group, has no children --, and its dense moves),
+ *   snk_engine_clone of every node of the level above F times (the list is per node, never per row: a team of three in a 1 v 3
+ *   clones 81 + 6561 records per game) and snk_engine_step_active; then the leaf pairs (the one per-row list), the plain scores
+ *   of the last level, and the fold from the last level up, a quad of lanes per (row, node of the level above), which keeps one
+ *   float per (row, node).  A node that is not active is never read.  No host synchronisation, no read-back, no atomics, one
+ *   writer per cell; every node index is compared with its sub-engine's n_slots before use.  d_q float32[m][3], nothing past row
+ *   m is written.  m == 0 is a no-op that accepts NULL buffers (the engines are still checked); NULL, m < 0, a flag bit outside
+ *   the three, a depth snk_pit_deep_fanout refuses, m * F^depth above 2^28, a mismatch, a repeated, food-spawning or too small
+ *   sub-engine is an error before any launch.
+ * What the kernels are held to: they are latency- and traffic-bound integer kernels without LDS and without per-thread arrays
+ *   (all state scalar, no scratch, no spills), one thread per node or a quad per (row, node), 256 threads a block, so occupancy
+ *   is bounded by registers alone; the fold reads one 4-byte alive flag per (child, snake) from the records and one float per
+ *   child, and the records of a level are written once by the clone and once by the step.                                       */
+int snk_pit_deep_fanout(int S, int depth);
+long snk_pit_deep_scratch_elems(int m, int S, int depth);
+int snk_pit_deep_values(const snk_engine *e, snk_engine *const *subs, int depth, const int32_t *d_pairs, int m, uint32_t flags,
+                        int32_t *d_scratch, float *d_q, void *stream);
 
 /* ---- replays of chosen games of a pit match (Game.draw game.py:281-300, called by Game.tic game.py:140-141 and 194-195) ----------
  * snake_engine.replay.Replay: the two boards Game.tic(show=True) appends per tick, drawn by kernels into a log in device memory for

@@ -18,7 +18,8 @@ of the searches (Searcher.stats) and, since a searching turn is bound by them, t
 table and the ratings behind the nets, one per FLAGS value (bits 1 space, 2 heads, 4 food; no value: 7, the whole policy).  A
 value look or lookN is the lookahead yardstick (snake_engine.arena.Lookahead: the script one tick deep) with flags 7 or N.  A
 scripted owner moves by its script under --search too.  --nets 0 --baseline 0 1 3 7 is the round robin of four flag settings,
---nets 0 --baseline 0 1 3 7 look the same with the lookahead in it.
+--nets 0 --baseline 0 1 3 7 look the same with the lookahead in it.  deep2, deep3, deep4 (a flags digit may follow, as in look5)
+are the deep yardstick (snake_engine.arena.Deep: the script that many ticks deep); the board's snake count limits the depth.
 --replay K DIR (not with --time): the round robin records its first K games (League.record) and writes them as DIR/game_<g>.rep,
 the text of the reference's replay.rep: two boards per tick.
 --tally (not with --time): the round robin also counts every seat's fate on the device (League.tally) and the table is printed
@@ -66,7 +67,7 @@ def main():
     a = ap.parse_args()
     import numpy as np
     import torch
-    from snake_engine.arena import Arena, Lookahead, Scripted, Searcher
+    from snake_engine.arena import Arena, Deep, Lookahead, Scripted, Searcher
     from snake_engine.league import SEATS, League, ratings, schedule, searchers, table
     from snake_engine.net import glorot_uniform_weights
     from utils.alpha_nnet import AlphaNNet
@@ -105,7 +106,10 @@ def main():
         nets = [Counted(net) for net in nets]
     if a.baseline is not None:
         for flags in a.baseline or ["7"]:
-            if flags.startswith("look"):            # look, look5: the lookahead yardstick
+            if flags.startswith("deep"):            # deep2, deep3, deep4; deep25: the deep yardstick, depth 2, flags 5
+                names.append(f"deep{int(flags[4])}_{int(flags[5:] or 7)}")
+                nets.append(Deep(int(flags[5:] or 7), int(flags[4])))
+            elif flags.startswith("look"):            # look, look5: the lookahead yardstick
                 names.append(f"look{int(flags[4:] or 7)}")
                 nets.append(Lookahead(int(flags[4:] or 7)))
             else:

@@ -32,7 +32,7 @@ def main():
     import torch
     from snake_engine import Engine
     from snake_engine._lib import check
-    from snake_engine.arena import Arena, Lookahead, Scripted
+    from snake_engine.arena import Arena, Deep, Lookahead, Scripted
     from snake_engine.engine import _ptr, _stream
     from snake_engine.net import glorot_uniform_weights
     from utils.alpha_nnet import AlphaNNet
@@ -47,7 +47,7 @@ def main():
     prop = torch.cuda.get_device_properties(0)
     say(f"script_time: {torch.cuda.get_device_name(0)} ({prop.gcnArchName}, {prop.multi_processor_count} CUs), ROCm / HIP "
         f"{torch.version.hip}, torch {torch.__version__}")
-    script, look = Scripted(), Lookahead()
+    script, look, deep = Scripted(), Lookahead(), Deep(depth=2)
 
     def events(fn):
         fn()
@@ -91,16 +91,22 @@ def main():
             f"{f[0]:.1f} us (min {f[1]:.1f}, max {f[2]:.1f}); ratio {f[0] / k[0]:.1f}x")
         say(f"kernel: {hw}x{hw}x{S}, the same {rows} rows: snk_pit_look_values {la[0]:.1f} us (min {la[1]:.1f}, max {la[2]:.1f}), "
             f"{la[0] / k[0]:.1f}x snk_pit_script_values; sub-engine of {look._sub.n_slots} slots")
+        deep.q_rows(eng, pairs)                      # the sub-engines and the scratch are made outside the timing
+        d = events(lambda: deep.q_rows(eng, pairs))
+        say(f"kernel: {hw}x{hw}x{S}, the same {rows} rows: Deep(depth=2), snk_pit_deep_values in chunks of {deep._subs[0].n_slots // 81} "
+            f"rows, {d[0]:.1f} us (min {d[1]:.1f}, max {d[2]:.1f}), {d[0] / la[0]:.1f}x snk_pit_look_values; sub-engines of "
+            f"{[sub.n_slots for sub in deep._subs]} slots, {sum(sub.n_slots * sub.slot_bytes for sub in deep._subs) / 2 ** 20:.0f} MiB")
 
     nets = [AlphaNNet(input_shape=(21, 21, 3), _weights=glorot_uniform_weights((21, 21, 3), a.blocks, seed=s)) for s in (1, 2)]
     Arena(11, 11, 4, 1, 64, 99).match(nets[0], nets[1], 1)             # first launches, plans and range-guard scales settle outside the timing
     Arena(11, 11, 4, 1, 64, 99).match(script, Scripted(), 1)
-    looks = (Lookahead(), Lookahead())
+    looks, deeps = (Lookahead(), Lookahead()), (Deep(depth=2), Deep(depth=2))
     for n in a.games:
         Arena(11, 11, 4, 1, n, 99).match(looks[0], looks[1], 1)        # their sub-engines grow to this size outside the timing
-        per = {"script v script": [], "look v look": [], "net v net": []}
+        per = {"script v script": [], "look v look": [], "deep v deep": [], "net v net": []}
         for k in range(a.pairs):
-            for name, sides in (("script v script", (script, Scripted())), ("look v look", looks), ("net v net", nets)):
+            for name, sides in (("script v script", (script, Scripted())), ("look v look", looks), ("deep v deep", deeps),
+                                ("net v net", nets)):
                 arena = Arena(11, 11, 4, 1, n, seed=7)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -112,7 +118,7 @@ def main():
                     f"wins {res.wins_a}-{res.wins_b}, draws {res.draws}")
         s, g, lk = (statistics.median(per[k]) for k in ("script v script", "net v net", "look v look"))
         say(f"match: games {n:5d} median ms per turn: script v script {s:.3f}, look v look {lk:.3f}, net v net {g:.3f}; net / script "
-            f"{g / s:.2f}x, look / script {lk / s:.2f}x")
+            f"{g / s:.2f}x, look / script {lk / s:.2f}x; deep v deep (depth 2) {statistics.median(per['deep v deep']):.3f}")
 
 
 if __name__ == "__main__":
