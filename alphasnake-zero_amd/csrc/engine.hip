@@ -1961,6 +1961,167 @@ __global__ __launch_bounds__(CMP_THREADS) void k_deep_reduce(const uint8_t *__re
 }
 
 // ------------------------------------------------------------------------------------------
+// the playout opponent of the pit (snake_engine.arena.Playout, snk_pit_playout_values): flat Monte-Carlo over the scripted policy.
+// include/snake_engine.h states the policy, tests/playout_ref.py restates it in plain Python.  Every unblocked move a of a row
+// (slot g, snake s) is played out P times for T ticks on copies of the game: clone c = (row * 3 + a) * P + p is slot c of the
+// sub-engine.  k_clone, the step kernels and k_pit_script do the copying, the ticks and the plain scores, launched through their
+// entry points.  What is new:
+//   k_play_plan   a thread per clone: its source slot, whether it is played at all (the pair in range, s alive, two or more
+//                 snakes alive, the move not blocked), and the S pairs (c, t) the script kernel scores on it before every tick --
+//                 (-1, -1) for a clone that is not played, which the script kernel scores without walking anything
+//   k_play_pick   a thread per clone, before each tick: settles the clone when s died in the tick before or stands alone, else
+//                 writes the clone's flag for the step and its dense moves -- s's own move a at tick 0, otherwise each alive
+//                 snake's playout move from its three plain scores and one Philox draw
+//   k_play_fold   a quad of lanes per row, lane a sums the values of its P clones into the score of move a
+// Every cell of every array has one writer per launch, nothing is read back, there are no atomics and no LDS, and all per-thread
+// state is scalar.  A clone that is not played holds a copy of slot 0 (the clone launch's size is fixed on the host) and is never
+// read; a clone that is settled is not stepped again.  Every slot and clone index is compared with its engine's n_slots first.
+// ------------------------------------------------------------------------------------------
+#define PL_MAX_PLAYOUTS 64
+#define PL_MAX_HORIZON 64
+#define PL_MAX_EXPLORE 256
+#define PL_TAG 0x504C4159u                       // counter word 3 of every playout draw
+#define PL_SKIP (-2)                             // a clone's fate: not played
+#define PL_RUN (-1)                              //                 still running; 0 .. 2T: its value
+
+// scratch, in int32 elements from its start; every part starts at a multiple of four elements (16 bytes); n = 3 * P * m clones
+struct PlayScratch {
+    long fb_q;          // float[m][3]       the plain scores of the rows themselves
+    long src;           // int32[n]          a clone's source slot (slot 0 for a clone that is not played)
+    long fate;          // int32[n]          PL_SKIP, PL_RUN or the clone's value
+    long active;        // uint8[n]          a clone's flag for the step
+    long moves;         // uint8[n][S]
+    long pairs;         // int32[n * S][2]   the fixed list (clone, snake) the script kernel scores before every tick
+    long q;             // float[n * S][3]   the tick's plain scores
+    long total;
+};
+
+static PlayScratch play_scratch(long m, int S, int P)
+{
+    auto up4 = [](long v) { return (v + 3) / 4 * 4; };
+    PlayScratch Z;
+    const long n = m * 3 * P;
+    long at = 0;
+    Z.fb_q = at;    at += up4(3 * m);
+    Z.src = at;     at += up4(n);
+    Z.fate = at;    at += up4(n);
+    Z.active = at;  at += up4((n + 3) / 4);
+    Z.moves = at;   at += up4((n * S + 3) / 4);
+    Z.pairs = at;   at += up4(2 * n * S);
+    Z.q = at;       at += up4(3 * n * S);
+    Z.total = at;
+    return Z;
+}
+
+// the value of a clone whose alive bits after the step of tick i are `bits`: i when s is dead, 2T when s stands alone, else PL_RUN
+__device__ static inline int play_settle(uint32_t bits, int s, int i, int T)
+{
+    if (!((bits >> s) & 1u)) return i;
+    return (bits & ~(1u << s)) ? PL_RUN : 2 * T;
+}
+
+// thread c < n is clone c: playout c % P of move (c / P) % 3 of row c / (3 * P)
+__global__ __launch_bounds__(CMP_THREADS) void k_play_plan(const uint8_t *__restrict__ state, Layout L, int n_slots, int sub_slots,
+                                                          const int32_t *__restrict__ pairs, int n, int P,
+                                                          const float *__restrict__ fb_q, int32_t *__restrict__ src,
+                                                          int32_t *__restrict__ fate, uint8_t *__restrict__ active,
+                                                          uint8_t *__restrict__ moves, int32_t *__restrict__ cl_pairs)
+{
+    const int c = blockIdx.x * CMP_THREADS + threadIdx.x;
+    if (c >= n) return;
+    const int row = c / (3 * P), a = (c - row * 3 * P) / P;
+    const int g = pairs[2 * (size_t)row], s = pairs[2 * (size_t)row + 1];
+    bool play = false;
+    if (g >= 0 && g < n_slots && s >= 0 && s < L.S && c < sub_slots) {
+        const uint32_t bits = deep_alive_bits(state, L, g);
+        play = ((bits >> s) & 1u) && __popc(bits) >= 2 && fb_q[3 * (size_t)row + a] != -1.0f;
+    }
+    src[c] = play ? g : 0;
+    fate[c] = play ? PL_RUN : PL_SKIP;
+    active[c] = 0;
+    for (int t = 0; t < L.S; ++t) {
+        const size_t at = (size_t)c * L.S + t;
+        moves[at] = 1;
+        cl_pairs[2 * at] = play ? c : -1;
+        cl_pairs[2 * at + 1] = play ? t : -1;
+    }
+}
+
+// thread c < n is clone c before the step of tick `tick`; cq holds the plain scores of every (clone, snake) as the clone stands.
+// A clone that is not running is not stepped.  A running one is settled when s died in the step before or stands alone; otherwise
+// s makes move a at tick 0, and every other alive snake -- s too from tick 1 on -- its playout move: the move k_pit_moves picks
+// from its three scores, or, when (r[0] & 255) < eps, the (r[1] % open)-th of its unblocked moves in ascending order
+__global__ __launch_bounds__(CMP_THREADS) void k_play_pick(const uint8_t *__restrict__ sub_state, Layout L, int n, int P, int T, int tick,
+                                                          int eps, uint32_t k0, uint32_t k1, const int32_t *__restrict__ pairs,
+                                                          const float *__restrict__ cq, int32_t *__restrict__ fate,
+                                                          uint8_t *__restrict__ active, uint8_t *__restrict__ moves)
+{
+    const int c = blockIdx.x * CMP_THREADS + threadIdx.x;
+    if (c >= n) return;
+    if (fate[c] != PL_RUN) { active[c] = 0; return; }
+    const int row = c / (3 * P), a = (c - row * 3 * P) / P, p = c - (row * 3 + a) * P;
+    const int g = pairs[2 * (size_t)row], s = pairs[2 * (size_t)row + 1];          // in range: the plan played the clone
+    const uint32_t bits = deep_alive_bits(sub_state, L, c);                        // c < the sub-engine's n_slots, as above
+    if (tick > 0) {
+        const int v = play_settle(bits, s, tick - 1, T);
+        if (v != PL_RUN) { fate[c] = v; active[c] = 0; return; }
+    }
+    active[c] = 1;
+    for (int t = 0; t < L.S; ++t) {
+        int mv = 1;
+        if ((bits >> t) & 1u) {
+            if (tick == 0 && t == s) {
+                mv = a;
+            } else {
+                const float *z = cq + 3 * ((size_t)c * L.S + t);
+                const float q0 = z[0], q1 = z[1], q2 = z[2];
+                mv = q0 > q1 ? (q0 > q2 ? 0 : 2) : (q1 > q2 ? 1 : 2);
+                const int o0 = q0 != -1.0f, o1 = q1 != -1.0f, open = o0 + o1 + (q2 != -1.0f);
+                uint32_t r[4];
+                philox4x32((uint32_t)g, (uint32_t)(s | a << 4 | t << 8), (uint32_t)(p | tick << 8), PL_TAG, k0, k1, r);
+                if ((int)(r[0] & 255u) < eps && open > 0) {
+                    const int k = (int)(r[1] % (uint32_t)open);
+                    mv = (o0 && k == 0) ? 0 : (o1 && k == o0) ? 1 : 2;
+                }
+            }
+        }
+        moves[(size_t)c * L.S + t] = (uint8_t)mv;
+    }
+}
+
+// a quad of lanes per row, lane a < 3 scores move a: the row's plain score when its clones were not played (a dead or out-of-range
+// pair, fewer than two snakes alive, or the move blocked: -1), else 4 * (the sum of its P clones' values) + (the other moves whose
+// plain score is smaller).  A clone still running after the last step is worth T - 1 when s died in it, 2T when s is left alone, T
+// otherwise
+__global__ __launch_bounds__(CMP_THREADS) void k_play_fold(const uint8_t *__restrict__ sub_state, Layout L, int m, int P, int T,
+                                                          const int32_t *__restrict__ pairs, const float *__restrict__ fb_q,
+                                                          const int32_t *__restrict__ fate, float *__restrict__ q)
+{
+    const int t = blockIdx.x * CMP_THREADS + threadIdx.x;
+    const int row = t >> 2, a = t & 3;
+    if (row >= m || a >= 3) return;
+    const int s = pairs[2 * (size_t)row + 1];
+    const int base = (row * 3 + a) * P;
+    const float z0 = fb_q[3 * (size_t)row], z1 = fb_q[3 * (size_t)row + 1], z2 = fb_q[3 * (size_t)row + 2];
+    const float mine = a == 0 ? z0 : a == 1 ? z1 : z2;
+    float out = mine;
+    if (fate[base] != PL_SKIP) {
+        int sum = 0;
+        for (int p = 0; p < P; ++p) {
+            int v = fate[base + p];
+            if (v == PL_RUN) {
+                v = play_settle(deep_alive_bits(sub_state, L, base + p), s, T - 1, T);
+                if (v == PL_RUN) v = T;
+            }
+            sum += v;
+        }
+        const int below = (a != 0 && z0 < mine) + (a != 1 && z1 < mine) + (a != 2 && z2 < mine);
+        out = (float)(4 * sum + below);
+    }
+    q[3 * (size_t)row + a] = out;
+}
+
+// ------------------------------------------------------------------------------------------
 // replays of chosen games of a pit match (snake_engine.replay.Replay): the two boards Game.tic(show=True) appends per tick
 // (Game.draw game.py:281-300, called at game.py:140-141 and 194-195) for a list of recorded slots, drawn into a log in HBM.
 // One wavefront per recorded game.  Lane s holds snake s: where its head is drawn, the length it is sorted by, and the run of
@@ -2664,6 +2825,66 @@ extern "C" int snk_pit_deep_values(const snk_engine *e, snk_engine *const *subs,
             k + 1 < depth ? (const float *)(d_scratch + P.best[k]) : nullptr, k + 1 < depth ? nullptr : leaf_q, fb_q,
             k ? (float *)(d_scratch + P.best[k - 1]) : nullptr, d_q);
     }
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_playout_clones(int P) { return P < 1 || P > PL_MAX_PLAYOUTS ? -1 : 3 * P; }
+
+extern "C" long snk_pit_playout_scratch_elems(int m, int S, int P)
+{
+    if (m < 0 || S < 2 || S > SNK_MAX_SNAKES || snk_pit_playout_clones(P) < 0 || (long long)m * 3 * P * S > LK_MAX_LEAVES) return -1;
+    return play_scratch(m, S, P).total;
+}
+
+extern "C" int snk_pit_playout_values(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int P, int T,
+                                      int eps, uint64_t seed, int32_t *d_scratch, float *d_q, void *stream)
+{
+    SNK_REQUIRE(e != nullptr && sub != nullptr, "snk_pit_playout_values: engine is NULL");
+    SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
+                "snk_pit_playout_values: unknown flag bits in 0x%x", flags);
+    SNK_REQUIRE(m >= 0, "snk_pit_playout_values: m=%d", m);
+    SNK_REQUIRE(P >= 1 && P <= PL_MAX_PLAYOUTS, "snk_pit_playout_values: playouts P=%d outside 1..%d", P, PL_MAX_PLAYOUTS);
+    SNK_REQUIRE(T >= 1 && T <= PL_MAX_HORIZON, "snk_pit_playout_values: horizon T=%d outside 1..%d", T, PL_MAX_HORIZON);
+    SNK_REQUIRE(eps >= 0 && eps <= PL_MAX_EXPLORE, "snk_pit_playout_values: explore eps=%d outside 0..%d", eps, PL_MAX_EXPLORE);
+    SNK_REQUIRE(sub != e, "snk_pit_playout_values: the sub-engine is the engine itself");
+    SNK_REQUIRE(e->L.H == sub->L.H && e->L.W == sub->L.W && e->L.S == sub->L.S, "snk_pit_playout_values: geometry mismatch");
+    SNK_REQUIRE(e->device == sub->device, "snk_pit_playout_values: the engines are on devices %d and %d", e->device, sub->device);
+    SNK_REQUIRE(sub->food_chance == 0.0 && sub->health_dec == e->health_dec,
+                "snk_pit_playout_values: the sub-engine must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)",
+                sub->food_chance, e->health_dec, sub->health_dec);
+    const Layout L = e->L;
+    SNK_REQUIRE((long long)m * 3 * P * L.S <= LK_MAX_LEAVES, "snk_pit_playout_values: m=%d rows of %d clones and %d snakes exceed %d", m,
+                3 * P, L.S, LK_MAX_LEAVES);
+    SNK_REQUIRE((long long)m * 3 * P <= sub->n_slots, "snk_pit_playout_values: %d rows of %d clones exceed the sub-engine's %d slots", m,
+                3 * P, sub->n_slots);
+    if (m == 0) return 0;
+    SNK_REQUIRE(d_pairs && d_scratch && d_q, "snk_pit_playout_values: NULL argument");
+    const int n = m * 3 * P;                              // the clones
+    const PlayScratch Z = play_scratch(m, L.S, P);
+    float *fb_q = (float *)(d_scratch + Z.fb_q), *cq = (float *)(d_scratch + Z.q);
+    int32_t *src = d_scratch + Z.src, *fate = d_scratch + Z.fate, *cl_pairs = d_scratch + Z.pairs;
+    uint8_t *active = (uint8_t *)(d_scratch + Z.active), *moves = (uint8_t *)(d_scratch + Z.moves);
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = (n + CMP_THREADS - 1) / CMP_THREADS;
+    // the rows' own plain scores (the fallback, the blocked moves, the tie-break), the plan, Game.subgame of every played clone
+    int rc = snk_pit_script_values(e, d_pairs, m, flags, fb_q, stream);
+    if (rc != 0) return rc;
+    k_play_plan<<<grid, CMP_THREADS, 0, st>>>(e->d_state, L, e->n_slots, sub->n_slots, d_pairs, n, P, fb_q, src, fate, active, moves,
+                                             cl_pairs);
+    SNK_CHECK_HIP(hipGetLastError());
+    rc = snk_engine_clone(e, src, n, sub, nullptr, 1, stream);
+    // T ticks: every alive snake's plain scores on every clone, the moves, the step of the clones still running
+    for (int i = 0; i < T && rc == 0; ++i) {
+        rc = snk_pit_script_values(sub, cl_pairs, n * L.S, flags, cq, stream);
+        if (rc != 0) break;
+        k_play_pick<<<grid, CMP_THREADS, 0, st>>>(sub->d_state, L, n, P, T, i, eps, (uint32_t)seed, (uint32_t)(seed >> 32), d_pairs, cq,
+                                                 fate, active, moves);
+        SNK_CHECK_HIP(hipGetLastError());
+        rc = snk_engine_step_active(sub, active, n, moves, nullptr, nullptr, stream);
+    }
+    if (rc != 0) return rc;
+    k_play_fold<<<(4 * m + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(sub->d_state, L, m, P, T, d_pairs, fb_q, fate, d_q);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -45,6 +45,9 @@ of the up to four snakes alive on copies of the game in a sub-engine the side ow
 folds them into three scores per row on the device -- launches only, so the turn's read-back stays the one it is.
 ``Deep`` is the same search several ticks deep, the third fixed point: snk_pit_deep_values keeps one sub-engine per tick, the
 children of a game shared by all its rows at every level, and folds the levels from the last one up -- launches only as well.
+``Playout`` is flat Monte-Carlo over the same script, the fourth fixed point and the one without a limit on the snakes alive:
+snk_pit_playout_values plays every unblocked move out a few times for several ticks on copies of the game and scores how long the
+snake survives -- launches only again.
 
 ``record(games)`` returns a ``replay.Replay`` that the next match fills with the boards Game.tic(show=True) draws for those games
 (game.py:140-141, 194-195): snk_pit_record_moves before the step and snk_pit_record_boards after it draw them into a log on the
@@ -262,6 +265,67 @@ class Deep(Scripted):
             subs, handles, scratch = self._buffers(engine, cnt, F)
             check(engine.L.snk_pit_deep_values(engine.h, _ptr(handles), self.depth, _ptr(pairs[lo:lo + cnt]), cnt, self.flags,
                                                _ptr(scratch), _ptr(q[lo:lo + cnt]), _stream()))
+        return q
+
+
+PLAYOUT_SLOT_BUDGET = 1 << 18        # clones (rows times 3 * playouts) of one snk_pit_playout_values call: 296 MiB of 11x11x4 records
+
+
+class Playout(Scripted):
+    """Flat Monte-Carlo over the scripted policy (include/snake_engine.h states it): every unblocked move is played out
+    `playouts` times for `horizon` ticks on copies of the game, every snake following the plain script, or with probability
+    `explore` / 256 a uniformly drawn unblocked move, and the move scores how long the snake survives; the plain script breaks the
+    ties.  The cost is rows * 3 * playouts clones whatever the number of snakes alive, so unlike Lookahead and Deep it does not
+    fall back to the plain script above four snakes, and its horizon is a parameter.  The draws are counter-based (Philox keyed by
+    seed, slot and snake), so the same position and seed give the same move in every run and in every row order.  The defaults
+    (8 playouts, 8 ticks, explore 64) are a starting point, not tuned values.  The same flags and refusals as Scripted, and it
+    sits wherever a Scripted can; a Searcher around it is a TypeError.  It owns a sub-engine without food spawning for the
+    clones and the scratch of snk_pit_playout_values, made at first use, remade when the geometry or the device changes, and
+    grown when more rows arrive; a call takes at most PLAYOUT_SLOT_BUDGET // (3 * playouts) rows, at least one."""
+
+    def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD, playouts=8, horizon=8, explore=64, seed=0):
+        super().__init__(flags)
+        playouts, horizon, explore, seed = int(playouts), int(horizon), int(explore), int(seed)
+        if not 1 <= playouts <= 64:
+            raise ValueError(f"Playout playouts {playouts}: 1 .. 64")
+        if not 1 <= horizon <= 64:
+            raise ValueError(f"Playout horizon {horizon}: 1 .. 64")
+        if not 0 <= explore <= 256:
+            raise ValueError(f"Playout explore {explore}: 0 .. 256")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"Playout seed {seed}: 64 bits")
+        self.playouts, self.horizon, self.explore, self.seed = playouts, horizon, explore, seed
+        self._sub = self._scratch = None
+
+    def _buffers(self, engine, rows):
+        """the sub-engine and the scratch for a call of `rows` rows"""
+        sub = self._sub
+        key = (engine.H, engine.W, engine.S, engine.health_dec, engine.device)
+        if sub is None or (sub.H, sub.W, sub.S, sub.health_dec, sub.device) != key:
+            sub = self._scratch = None
+        slots = rows * 3 * self.playouts
+        if sub is None or sub.n_slots < slots:
+            if sub is not None:
+                sub.close()
+            sub = Engine(slots, engine.H, engine.W, engine.S, engine.health_dec, 0, seed=0, device=engine.device.index)
+        elems = engine.L.snk_pit_playout_scratch_elems(rows, engine.S, self.playouts)
+        if elems < 0:
+            raise EngineError(f"no playout scratch for {rows} rows of {engine.S} snakes and {self.playouts} playouts")
+        if self._scratch is None or self._scratch.numel() < elems:
+            self._scratch = engine.new((elems,), torch.int32)
+        self._sub = sub
+        return sub, self._scratch
+
+    def q_rows(self, engine, pairs):
+        """pairs int32[rows][2] (slot, snake id) on the device -> the three move scores float32[rows][3] on the device"""
+        m = int(pairs.shape[0])
+        q = engine.new((m, 3), torch.float32)
+        per = max(PLAYOUT_SLOT_BUDGET // (3 * self.playouts), 1)      # a cut anywhere changes nothing: the draws are keyed by slot and snake
+        for lo in range(0, m, per):
+            cnt = min(per, m - lo)
+            sub, scratch = self._buffers(engine, cnt)
+            check(engine.L.snk_pit_playout_values(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, self.playouts, self.horizon,
+                                                  self.explore, self.seed, _ptr(scratch), _ptr(q[lo:lo + cnt]), _stream()))
         return q
 
 

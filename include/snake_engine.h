@@ -62,8 +62,9 @@ const char *snk_last_error(void);
                              * recorder's (snk_pit_record_stride, snk_pit_record_slots, snk_pit_record_moves,
                              * snk_pit_record_boards) and the tally's (snk_pit_tally) and the lookahead opponent's
                              * (snk_pit_look_fanout, snk_pit_look_scratch_elems, snk_pit_look_values) and the deep opponent's
-                             * (snk_pit_deep_fanout, snk_pit_deep_scratch_elems, snk_pit_deep_values): no argument list of an
-                             * older one changed */
+                             * (snk_pit_deep_fanout, snk_pit_deep_scratch_elems, snk_pit_deep_values) and the playout opponent's
+                             * (snk_pit_playout_clones, snk_pit_playout_scratch_elems, snk_pit_playout_values): no argument list of
+                             * an older one changed */
 int snk_version(void);
 
 /* ---- engine lifetime -------------------------------------------------------------------
@@ -686,6 +687,56 @@ int snk_pit_deep_fanout(int S, int depth);
 long snk_pit_deep_scratch_elems(int m, int S, int depth);
 int snk_pit_deep_values(const snk_engine *e, snk_engine *const *subs, int depth, const int32_t *d_pairs, int m, uint32_t flags,
                         int32_t *d_scratch, float *d_q, void *stream);
+
+/* ---- the playout opponent: flat Monte-Carlo over the scripted policy, a fourth fixed yardstick (the project's own, as above) -----
+ * snake_engine.arena.Playout(flags, playouts, horizon, explore, seed) sits wherever a Scripted can; tests/playout_ref.py is the
+ * statement in plain Python.  Integers only.  Its cost is rows x 3 x playouts clones whatever the number of snakes alive, so it
+ * has no upper limit on A, and its horizon is a parameter.  Parameters: flags as above; P playouts, 1..64; T the horizon in
+ * ticks, 1..64; eps the exploration, 0..256; a 64-bit seed.  For row (slot g, snake s), s alive, in a game with A snakes alive:
+ *   fallback  A < 2 (the step does not move such a game): exactly what snk_pit_script_values gives the row with the same flags
+ *   plain(a)  the row's three plain script scores on the game itself; a move with plain(a) = -1 (blocked) scores -1 and is not
+ *             played out
+ *   playout   (a, p), p = 0 .. P-1: a copy of the game as snk_engine_clone makes it, stepped as snk_engine_step_active steps it on
+ *             an engine whose food spawn chance is 0, for ticks i = 0 .. T-1.  At tick 0 s makes relative move a; every other
+ *             alive snake at tick 0, and every alive snake (s too) at later ticks, makes its playout move; the move entries of
+ *             dead snakes are 1
+ *   move      of snake t at tick i: q = t's three plain script scores on the clone as it stands, same flags;
+ *             r = philox4x32(c0 = g, c1 = s | a << 4 | t << 8, c2 = p | i << 8, c3 = 0x504C4159, k0 = seed & 0xffffffff,
+ *             k1 = seed >> 32); with n = the number of moves with q != -1: when (r[0] & 255) < eps and n > 0 the (r[1] % n)-th of
+ *             those moves in ascending order, otherwise the move snk_pit_moves picks from q (strict comparisons: of equal best
+ *             scores the later move wins, all equal gives 2).  The key holds the slot and the snake, never the row index: a row's
+ *             scores do not depend on where it stands in the list, on how a list is cut into calls, or on the turn
+ *   value     v of a playout: i when s is not alive after the step of tick i; 2T when at any point s is alive and no other snake
+ *             is; T otherwise (s alive after tick T-1 with company).  A clone in which s is dead or alone is not stepped again
+ *   score     4 * (the sum of v over the P playouts) + (the number of moves b != a with plain(b) < plain(a)): the plain script
+ *             breaks the ties between moves that survive equally, so the opponent still goes for food
+ * A score lies in 0 .. 8TP + 2 <= 32 770, is exact as float32 and above the -1 of a blocked move; snk_pit_moves turns the scores
+ * into a move with its strict comparisons, and that tie order is part of the policy.  A pair that names a dead snake, or a slot
+ * outside 0..n_slots-1 or a snake id outside 0..S-1, gets -1, -1, -1.
+ * snk_pit_playout_clones(P): 3 * P, the clones of a row; -1 for P outside 1..64.
+ * snk_pit_playout_scratch_elems(m, S, P): the int32 elements of d_scratch; -1 for m < 0, S outside 2..8, a refused P, or
+ *   m * 3 * P * S above 2^28.
+ * snk_pit_playout_values: sub has e's geometry, device and health_dec, spawns no food (chance 0), is not e and has at least
+ *   m * 3 * P slots; its records are overwritten, e's are only read.  The clone of row r, move a, playout p is slot
+ *   (r * 3 + a) * P + p of sub.  Launches only, all on `stream`: snk_pit_script_values on e for the rows themselves; the plan (a
+ *   thread per clone: its source slot and whether it is played at all -- the pair in range, s alive, A >= 2, the move not blocked
+ *   --, and the fixed list of (clone, snake) pairs the script kernel scores before every tick, (-1, -1) for a clone that is not
+ *   played); snk_engine_clone (a clone that is not played receives a copy of slot 0, since the launch's size is fixed on the
+ *   host, and is never read); then T times snk_pit_script_values on sub, the pick (a thread per clone: it settles the clone when
+ *   s died in the step before or stands alone, one int32 per clone remembers which; otherwise the clone's flag for the step and
+ *   its dense moves uint8[clones][S]) and snk_engine_step_active; then the fold, a quad of lanes per row, lane a sums its P
+ *   clones.  No host synchronisation, no read-back, no atomics, one writer per cell; every slot and clone index is compared with
+ *   its engine's n_slots before use.  d_q float32[m][3], nothing past row m is written.  m == 0 is a no-op that accepts NULL
+ *   buffers (the engines and the parameters are still checked).  A NULL array, m < 0, a flag bit outside the three, P, T or eps
+ *   out of range, m * 3 * P * S above 2^28, a sub-engine that is e, differs in geometry, device or health_dec, spawns food or
+ *   has fewer than m * 3 * P slots is an error before any launch.
+ * What the kernels are held to: what the deep kernels are -- no LDS, no per-thread arrays indexed at run time (all state scalar,
+ *   no scratch, no spills), a thread per clone or a quad per row, 256 threads a block.  The script scores of a tick go through
+ *   memory (3 floats per clone and snake, written by k_pit_script and read by the pick).                                       */
+int snk_pit_playout_clones(int P);
+long snk_pit_playout_scratch_elems(int m, int S, int P);
+int snk_pit_playout_values(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int P, int T, int eps,
+                           uint64_t seed, int32_t *d_scratch, float *d_q, void *stream);
 
 /* ---- replays of chosen games of a pit match (Game.draw game.py:281-300, called by Game.tic game.py:140-141 and 194-195) ----------
  * snake_engine.replay.Replay: the two boards Game.tic(show=True) appends per tick, drawn by kernels into a log in device memory for

@@ -20,6 +20,8 @@ value look or lookN is the lookahead yardstick (snake_engine.arena.Lookahead: th
 scripted owner moves by its script under --search too.  --nets 0 --baseline 0 1 3 7 is the round robin of four flag settings,
 --nets 0 --baseline 0 1 3 7 look the same with the lookahead in it.  deep2, deep3, deep4 (a flags digit may follow, as in look5)
 are the deep yardstick (snake_engine.arena.Deep: the script that many ticks deep); the board's snake count limits the depth.
+play and playPxT (play8x16: 8 playouts of 16 ticks) are the playout yardstick (snake_engine.arena.Playout: flat Monte-Carlo over
+the script, with its defaults or P playouts and horizon T).
 --replay K DIR (not with --time): the round robin records its first K games (League.record) and writes them as DIR/game_<g>.rep,
 the text of the reference's replay.rep: two boards per tick.
 --tally (not with --time): the round robin also counts every seat's fate on the device (League.tally) and the table is printed
@@ -67,7 +69,8 @@ def main():
     a = ap.parse_args()
     import numpy as np
     import torch
-    from snake_engine.arena import Arena, Deep, Lookahead, Scripted, Searcher
+    import playout_names
+    from snake_engine.arena import Arena, Deep, Lookahead, Playout, Scripted, Searcher
     from snake_engine.league import SEATS, League, ratings, schedule, searchers, table
     from snake_engine.net import glorot_uniform_weights
     from utils.alpha_nnet import AlphaNNet
@@ -106,7 +109,10 @@ def main():
         nets = [Counted(net) for net in nets]
     if a.baseline is not None:
         for flags in a.baseline or ["7"]:
-            if flags.startswith("deep"):            # deep2, deep3, deep4; deep25: the deep yardstick, depth 2, flags 5
+            if playout_names.parse(flags) is not None:            # play, play8x16: the playout yardstick
+                names.append(flags)
+                nets.append(Playout(**playout_names.parse(flags)))
+            elif flags.startswith("deep"):            # deep2, deep3, deep4; deep25: the deep yardstick, depth 2, flags 5
                 names.append(f"deep{int(flags[4])}_{int(flags[5:] or 7)}")
                 nets.append(Deep(int(flags[5:] or 7), int(flags[4])))
             elif flags.startswith("look"):            # look, look5: the lookahead yardstick

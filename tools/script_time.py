@@ -6,8 +6,10 @@ kernel: HIP-event time of one snk_pit_script_values launch over the first 16 384
 of 19x19x8 boards, both taken from games the script itself has played for 20 turns (mid-game bodies, some snakes dead), beside the
 observe launch plus a --blocks-block forward over the same rows; medians of --reps launches after one that is not timed.  Beside it
 one snk_pit_look_values call (snake_engine.arena.Lookahead: its plan, the clone, step and script launches on the sub-engine and
-the reduce) over the same rows.
-match: ms per turn of Arena.match(Scripted, Scripted) beside Lookahead against Lookahead and greedy net against greedy net (1 v 3,
+the reduce) over the same rows, one Deep(depth=2) and one Playout() with its defaults (snake_engine.arena.Playout,
+snk_pit_playout_values: 3 + 3 * horizon + 1 launches a call).
+match: ms per turn of Arena.match(Scripted, Scripted) beside Lookahead against Lookahead, Deep against Deep, Playout against
+Playout and greedy net against greedy net (1 v 3,
 11x11), alternating inside this one process, --pairs times; a host clock around a match that ends in a device synchronise."""
 import argparse
 import os
@@ -32,7 +34,8 @@ def main():
     import torch
     from snake_engine import Engine
     from snake_engine._lib import check
-    from snake_engine.arena import Arena, Deep, Lookahead, Scripted
+    from snake_engine import arena as arena_mod
+    from snake_engine.arena import Arena, Deep, Lookahead, Playout, Scripted
     from snake_engine.engine import _ptr, _stream
     from snake_engine.net import glorot_uniform_weights
     from utils.alpha_nnet import AlphaNNet
@@ -47,7 +50,7 @@ def main():
     prop = torch.cuda.get_device_properties(0)
     say(f"script_time: {torch.cuda.get_device_name(0)} ({prop.gcnArchName}, {prop.multi_processor_count} CUs), ROCm / HIP "
         f"{torch.version.hip}, torch {torch.__version__}")
-    script, look, deep = Scripted(), Lookahead(), Deep(depth=2)
+    script, look, deep, play = Scripted(), Lookahead(), Deep(depth=2), Playout()
 
     def events(fn):
         fn()
@@ -96,17 +99,24 @@ def main():
         say(f"kernel: {hw}x{hw}x{S}, the same {rows} rows: Deep(depth=2), snk_pit_deep_values in chunks of {deep._subs[0].n_slots // 81} "
             f"rows, {d[0]:.1f} us (min {d[1]:.1f}, max {d[2]:.1f}), {d[0] / la[0]:.1f}x snk_pit_look_values; sub-engines of "
             f"{[sub.n_slots for sub in deep._subs]} slots, {sum(sub.n_slots * sub.slot_bytes for sub in deep._subs) / 2 ** 20:.0f} MiB")
+        play.q_rows(eng, pairs)                      # the sub-engine and the scratch are made outside the timing
+        pl = events(lambda: play.q_rows(eng, pairs))
+        per = max(arena_mod.PLAYOUT_SLOT_BUDGET // (3 * play.playouts), 1)
+        say(f"kernel: {hw}x{hw}x{S}, the same {rows} rows: Playout() ({play.playouts} playouts of {play.horizon} ticks), "
+            f"snk_pit_playout_values in {(rows + per - 1) // per} calls of at most {per} rows, {pl[0]:.1f} us (min {pl[1]:.1f}, max {pl[2]:.1f}), "
+            f"{pl[0] / la[0]:.1f}x snk_pit_look_values, {pl[0] / k[0]:.1f}x snk_pit_script_values; sub-engine of {play._sub.n_slots} slots, "
+            f"{play._sub.n_slots * play._sub.slot_bytes / 2 ** 20:.0f} MiB")
 
     nets = [AlphaNNet(input_shape=(21, 21, 3), _weights=glorot_uniform_weights((21, 21, 3), a.blocks, seed=s)) for s in (1, 2)]
     Arena(11, 11, 4, 1, 64, 99).match(nets[0], nets[1], 1)             # first launches, plans and range-guard scales settle outside the timing
     Arena(11, 11, 4, 1, 64, 99).match(script, Scripted(), 1)
-    looks, deeps = (Lookahead(), Lookahead()), (Deep(depth=2), Deep(depth=2))
+    looks, deeps, plays = (Lookahead(), Lookahead()), (Deep(depth=2), Deep(depth=2)), (Playout(), Playout(seed=1))
     for n in a.games:
         Arena(11, 11, 4, 1, n, 99).match(looks[0], looks[1], 1)        # their sub-engines grow to this size outside the timing
-        per = {"script v script": [], "look v look": [], "deep v deep": [], "net v net": []}
+        per = {"script v script": [], "look v look": [], "deep v deep": [], "play v play": [], "net v net": []}
         for k in range(a.pairs):
             for name, sides in (("script v script", (script, Scripted())), ("look v look", looks), ("deep v deep", deeps),
-                                ("net v net", nets)):
+                                ("play v play", plays), ("net v net", nets)):
                 arena = Arena(11, 11, 4, 1, n, seed=7)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -118,7 +128,8 @@ def main():
                     f"wins {res.wins_a}-{res.wins_b}, draws {res.draws}")
         s, g, lk = (statistics.median(per[k]) for k in ("script v script", "net v net", "look v look"))
         say(f"match: games {n:5d} median ms per turn: script v script {s:.3f}, look v look {lk:.3f}, net v net {g:.3f}; net / script "
-            f"{g / s:.2f}x, look / script {lk / s:.2f}x; deep v deep (depth 2) {statistics.median(per['deep v deep']):.3f}")
+            f"{g / s:.2f}x, look / script {lk / s:.2f}x; deep v deep (depth 2) {statistics.median(per['deep v deep']):.3f}; "
+            f"play v play (the defaults) {statistics.median(per['play v play']):.3f}")
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 (snake_engine.arena.Searcher) and a greedy side of the SAME net, 11x11.
 
     python tools/search_pit.py [--games 300] [--breadth 16] [--depth 8] [--blocks 4] [--weights CKPT] [--seed 1]
-                               [--time] [--pairs 2] [--log profiles/arena_search.log] [--baseline [script|look|deep2|deep3|deep4]] [--replay K DIR] [--tally]
+                               [--time] [--pairs 2] [--log profiles/arena_search.log] [--baseline [script|look|deep2|deep3|deep4|play|playPxT]] [--replay K DIR] [--tally]
 
 Strength (default): 1 v 3 with the searcher alone, 1 v 3 with the searcher's three against the greedy one, and the duel; win and
 draw rates of the searching side with their binomial 95 % intervals (Wilson), ms per turn and net evaluations per turn.
@@ -12,7 +12,8 @@ turn, and the host time DeviceMCTS._ensure took (its buffers are made again when
 --baseline: the net against the scripted opponent (snake_engine.arena.Scripted with the whole policy, the fixed yardstick) instead
 of against itself: the greedy net in the duel and in 1 v 3 both ways, then the net moving by search in the duel; the net side's
 win and draw rates with the same intervals.  --baseline look: the same against the lookahead yardstick
-(snake_engine.arena.Lookahead: the script one tick deep); --baseline deep2 (deep3, deep4): against snake_engine.arena.Deep of that depth.
+(snake_engine.arena.Lookahead: the script one tick deep); --baseline deep2 (deep3, deep4): against snake_engine.arena.Deep of that depth;
+--baseline play (playPxT, e.g. play8x16): against snake_engine.arena.Playout with its defaults (P playouts of T ticks).
 --replay K DIR: the first match the run reports (strength or --baseline) records its first K games (Arena.record) and writes them
 as DIR/game_<g>.rep, the text of the reference's replay.rep: two boards per tick.
 --tally: the first match the run reports also counts every seat's fate on the device (Arena.tally) and prints the table: per side
@@ -25,6 +26,8 @@ import os
 import statistics
 import sys
 import time
+
+import playout_names
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (REPO, os.path.join(REPO, "alphasnake-zero_amd")):
@@ -52,12 +55,14 @@ def main():
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--pairs", type=int, default=2)
     ap.add_argument("--log", default=None)
-    ap.add_argument("--baseline", nargs="?", const="script", choices=("script", "look", "deep2", "deep3", "deep4"), default=None)
+    ap.add_argument("--baseline", nargs="?", const="script", default=None,
+                    type=lambda v: v if v in ("script", "look", "deep2", "deep3", "deep4") or playout_names.parse(v) is not None
+                    else ap.error(f"--baseline {v}: script, look, deep2, deep3, deep4, play or playPxT"))
     ap.add_argument("--replay", nargs=2, default=None, metavar=("K", "DIR"))
     ap.add_argument("--tally", action="store_true")
     a = ap.parse_args()
     import torch
-    from snake_engine.arena import Arena, Deep, Lookahead, Scripted, Searcher
+    from snake_engine.arena import Arena, Deep, Lookahead, Playout, Scripted, Searcher
     from snake_engine.mcts import DeviceMCTS
     from snake_engine.net import glorot_uniform_weights
     from utils.alpha_nnet import AlphaNNet
@@ -143,6 +148,8 @@ def main():
         script, who_b = (Lookahead(), "lookahead") if a.baseline == "look" else (Scripted(), "script")
         if a.baseline.startswith("deep"):
             script, who_b = Deep(depth=int(a.baseline[4])), a.baseline
+        if playout_names.parse(a.baseline) is not None:
+            script, who_b = Playout(**playout_names.parse(a.baseline)), a.baseline
         lineups = [("duel, the net first", 2, 1, 0), ("1v3, the net alone", 4, 1, 0), (f"1v3, three of the net against the {who_b}", 4, 3, 0)]
         movers = [("greedy net", None, lineups)] + [(f"search breadth {b:3d}", b, lineups[:1]) for b in a.breadth]
         for mover, breadth, ups in movers:
