@@ -1450,6 +1450,19 @@ struct ScriptMasks {
     uint64_t not_cl[6];     // bit c = c < NC and c % W != W - 1: a cell that has a right neighbour
 };
 
+static ScriptMasks script_masks(const Layout &L)
+{
+    ScriptMasks K;
+    memset(&K, 0, sizeof(K));
+    for (int c = 0; c < L.NC; ++c) {
+        const uint64_t bit = 1ull << (c & 63);
+        K.valid[c >> 6] |= bit;
+        if (c % L.W != 0) K.not_c0[c >> 6] |= bit;
+        if (c % L.W != L.W - 1) K.not_cl[c >> 6] |= bit;
+    }
+    return K;
+}
+
 __device__ static inline int script_ring_cell(const uint8_t *rec, const Layout &L, int s, int idx)
 {
     const uint8_t *r = rec + (size_t)s * L.ring_bytes;
@@ -1577,6 +1590,188 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_pit_script(const uint8_t *__r
             int room = space < len_s ? space : len_s;
             room = room < 255 ? room : 255;
             const int fill = space < 511 ? space : 511;
+            score = ((room * 2 + safe) * 64 + food) * 512 + fill;
+        }
+    }
+    if (in && k < 3) q[3 * (size_t)row + k] = (float)score;
+}
+
+// ------------------------------------------------------------------------------------------
+// the territory opponent of the pit (snake_engine.arena.Territory, snk_pit_territory_values): the scripted policy with Voronoi
+// territory -- the free cells the snake reaches before anybody else does -- in place of the flood fill's space.  The policy is the
+// project's own; include/snake_engine.h states it and tests/territory_ref.py restates it in plain Python.
+// k_pit_script's form: a quad of lanes per row, planes as FW words in registers, every loop unrolled or bounded whatever the record
+// holds.  While lane k walks the rings of snakes k and k + 4 for the occupancy plane it also sets, for each of them that is not the
+// row's own snake, the on-board targets of its three moves in one of two start planes: `strong` for a snake at least as long as
+// the row's, `weak` for a shorter one.  The three planes are ORed across the quad by the same DPP moves, so the start planes are
+// built once per row; no lane has left when they run (flags is the same in every lane).  Lanes 0..2 then each score one move.
+// The fronts expand freely over the free cells, a round per step of distance, by the four shifts of script_grow.  A cell that
+// my front reaches first in round r is mine when no strong front has reached it by round r and no weak front before round r
+// (the head-on rule).  "Before round r" is "by round r" of a front that starts one round late, and growing distributes over OR,
+// so the strong and the late weak fronts are ONE plane `their`: the strong starts, grown once, joined by the weak starts -- that
+// is round 1 -- and grown once a round from there on.  Two fronts are carried, and the weak start plane is dead before the loop.
+// The rounds end when my front stops growing, and after NC of them at the latest.
+// ------------------------------------------------------------------------------------------
+template <int FW>
+__device__ __forceinline__ void script_grow(const uint64_t (&r)[FW], const uint64_t (&fr)[FW], const ScriptMasks &K, int WW,
+                                            uint64_t (&nx)[FW])
+{
+#pragma unroll
+    for (int w = 0; w < FW; ++w) {
+        const uint64_t below = w > 0 ? r[w > 0 ? w - 1 : 0] : 0ull, above = w < FW - 1 ? r[w < FW - 1 ? w + 1 : 0] : 0ull;
+        const uint64_t from_up = (r[w] << WW) | (below >> (64 - WW));         // cell c takes cell c - W
+        const uint64_t from_dn = (r[w] >> WW) | (above << (64 - WW));         // cell c takes cell c + W
+        const uint64_t from_lf = ((r[w] << 1) | (below >> 63)) & K.not_c0[w]; // cell c takes cell c - 1, not across a row end
+        const uint64_t from_rt = ((r[w] >> 1) | (above << 63)) & K.not_cl[w]; // cell c takes cell c + 1
+        nx[w] = (r[w] | from_up | from_dn | from_lf | from_rt) & fr[w];
+    }
+}
+
+template <int FW>
+__global__ __launch_bounds__(BLOCK_THREADS) void k_pit_territory(const uint8_t *__restrict__ state, Layout L, int n_slots,
+                                                                const int32_t *__restrict__ pairs, int m, uint32_t flags,
+                                                                int hungry, ScriptMasks K, float *__restrict__ q)
+{
+    const int t = blockIdx.x * BLOCK_THREADS + threadIdx.x;
+    const int row = t >> 2, k = t & 3;
+    const bool in = row < m;
+    int g = -1, s = -1;
+    if (in) { g = pairs[2 * (size_t)row]; s = pairs[2 * (size_t)row + 1]; }
+    const bool pair_ok = in && g >= 0 && g < n_slots && s >= 0 && s < L.S;
+    const uint8_t *rec = state + (size_t)(pair_ok ? g : 0) * L.stride;
+    const SnakeMeta *meta = (const SnakeMeta *)(rec + L.meta_off);
+    SnakeMeta me = {0, 0, 0, 0, 0};
+    if (pair_ok) me = meta[s];
+    const bool ok = pair_ok && me.alive;
+    const bool fronts = (flags & SNK_SCRIPT_SPACE) != 0u;     // the same in every lane
+    const int HH = L.H, WW = L.W;
+    const int len_s = me.len;
+
+    // ---- occupied as in k_pit_script; strong and weak: where the other alive snakes can stand after this tick (free or not)
+    uint64_t occ[FW], strong[FW], weak[FW];
+#pragma unroll
+    for (int w = 0; w < FW; ++w) occ[w] = strong[w] = weak[w] = 0ull;
+    if (ok) {
+        for (int o = k; o < L.S; o += 4) {
+            const SnakeMeta mo = meta[o];
+            if (!mo.alive) continue;
+            const int len = (int)mo.len < L.cap ? (int)mo.len : L.cap;
+            for (int i = 0; i < len; ++i) {
+                const int c = script_ring_cell(rec, L, o, mo.tail + i);
+                if (c < L.NC) {
+#pragma unroll
+                    for (int w = 0; w < FW; ++w) occ[w] |= (c >> 6) == w ? 1ull << (c & 63) : 0ull;
+                }
+            }
+            if (!fronts || o == s) continue;
+            const int ho = script_ring_cell(rec, L, o, mo.tail + mo.len - 1);
+            const int oy = ho / WW, ox = ho - oy * WW;
+            const bool is_strong = (int)mo.len >= len_s;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const int d = (a + mo.dir + 3) & 3;
+                const int y = oy + (d == 2) - (d == 0), x = ox + (d == 1) - (d == 3);
+                if ((y < 0) | (y >= HH) | (x < 0) | (x >= WW)) continue;
+                const int c = y * WW + x;                     // on the board: below NC
+#pragma unroll
+                for (int w = 0; w < FW; ++w) {
+                    const uint64_t bit = (c >> 6) == w ? 1ull << (c & 63) : 0ull;
+                    strong[w] |= is_strong ? bit : 0ull;
+                    weak[w] |= is_strong ? 0ull : bit;
+                }
+            }
+        }
+    }
+#define QUAD_OR(plane)                                                                                  \
+    _Pragma("unroll") for (int w = 0; w < FW; ++w) {                                                    \
+        int lo = (int)(uint32_t)plane[w], hi = (int)(uint32_t)(plane[w] >> 32);                         \
+        lo |= __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xF, 0xF, true);      /* quad_perm [1,0,3,2] */  \
+        hi |= __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xF, 0xF, true);                                 \
+        lo |= __builtin_amdgcn_update_dpp(0, lo, 0x4E, 0xF, 0xF, true);      /* quad_perm [2,3,0,1] */  \
+        hi |= __builtin_amdgcn_update_dpp(0, hi, 0x4E, 0xF, 0xF, true);                                 \
+        plane[w] = ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;                                       \
+    }
+    QUAD_OR(occ)                                      // all 64 lanes are here: the quad's four partial planes become one
+    if (fronts) {
+        QUAD_OR(strong)
+        QUAD_OR(weak)
+    }
+#undef QUAD_OR
+
+    // ---- lane k < 3 scores relative move k
+    int score = -1;
+    if (ok && k < 3) {
+        const int hc = script_ring_cell(rec, L, s, me.tail + len_s - 1);
+        const int d = (k + me.dir + 3) & 3;                   // k_step's heading: 0 = y-1, 1 = x+1, 2 = y+1, 3 = x-1
+        int y = hc / WW, x = hc - y * WW;
+        y += (d == 2) - (d == 0);
+        x += (d == 1) - (d == 3);
+        const bool oob = (y < 0) | (y >= HH) | (x < 0) | (x >= WW);
+        const int tc = oob ? 0 : y * WW + x;
+        bool blocked = oob;
+#pragma unroll
+        for (int w = 0; w < FW; ++w) blocked |= (tc >> 6) == w && ((occ[w] >> (tc & 63)) & 1ull);
+        if (!blocked) {
+            int territory = 0;
+            if (fronts) {
+                uint64_t fr[FW], mine[FW], their[FW], nx[FW];
+#pragma unroll
+                for (int w = 0; w < FW; ++w) {
+                    fr[w] = ~occ[w] & K.valid[w];
+                    mine[w] = (tc >> 6) == w ? 1ull << (tc & 63) : 0ull;          // the target is free
+                    strong[w] &= fr[w];
+                    territory += __popcll(mine[w] & ~strong[w]);                  // round 0: no weak front yet
+                }
+                script_grow<FW>(strong, fr, K, WW, their);                        // round 1: the strong fronts at distance <= 1
+#pragma unroll
+                for (int w = 0; w < FW; ++w) their[w] |= weak[w] & fr[w];         //          and the weak ones at distance 0
+                for (int round = 1; round < L.NC; ++round) {  // a round that changes my front adds a cell: at most NC - 1 of them
+                    script_grow<FW>(mine, fr, K, WW, nx);
+                    bool changed = false;
+#pragma unroll
+                    for (int w = 0; w < FW; ++w) {
+                        const uint64_t fresh = nx[w] & ~mine[w];
+                        changed |= fresh != 0ull;
+                        territory += __popcll(fresh & ~their[w]);
+                        mine[w] = nx[w];
+                    }
+                    if (!changed) break;
+                    script_grow<FW>(their, fr, K, WW, nx);
+#pragma unroll
+                    for (int w = 0; w < FW; ++w) their[w] = nx[w];
+                }
+            }
+            int safe = 1;
+            if (flags & SNK_SCRIPT_HEADS) {
+                for (int o = 0; o < L.S; ++o) {
+                    if (o == s) continue;
+                    const SnakeMeta mo = meta[o];
+                    if (!mo.alive || (int)mo.len < len_s) continue;
+                    const int ho = script_ring_cell(rec, L, o, mo.tail + mo.len - 1);
+                    const int oy = ho / WW, ox = ho - oy * WW;
+                    if (abs(oy - y) + abs(ox - x) == 1) safe = 0;
+                }
+            }
+            int food = 0;
+            if ((flags & SNK_SCRIPT_FOOD) && (int)me.health <= hungry) {
+                const uint64_t *fw = (const uint64_t *)(rec + L.food_off);
+                int best = 1 << 20;
+#pragma unroll
+                for (int w = 0; w < FW; ++w) {
+                    uint64_t f = fw[w < L.FW ? w : 0] & K.valid[w];          // valid[] is 0 from the layout's word count up
+                    while (f) {                                              // one set bit less per pass: at most 64
+                        const int c = w * 64 + __builtin_ctzll(f);
+                        f &= f - 1ull;
+                        const int fy = c / WW, fx = c - fy * WW;
+                        const int dist = abs(fy - y) + abs(fx - x);
+                        best = dist < best ? dist : best;
+                    }
+                }
+                if (best != (1 << 20)) food = HH + WW - best;
+            }
+            int room = territory < len_s ? territory : len_s;
+            room = room < 255 ? room : 255;
+            const int fill = territory < 511 ? territory : 511;
             score = ((room * 2 + safe) * 64 + food) * 512 + fill;
         }
     }
@@ -2647,20 +2842,35 @@ extern "C" int snk_pit_script_values(const snk_engine *e, const int32_t *d_pairs
     if (m == 0) return 0;
     SNK_REQUIRE(d_pairs && d_q, "snk_pit_script_values: NULL argument");
     const Layout L = e->L;
-    ScriptMasks K;
-    memset(&K, 0, sizeof(K));
-    for (int c = 0; c < L.NC; ++c) {
-        const uint64_t bit = 1ull << (c & 63);
-        K.valid[c >> 6] |= bit;
-        if (c % L.W != 0) K.not_c0[c >> 6] |= bit;
-        if (c % L.W != L.W - 1) K.not_cl[c >> 6] |= bit;
-    }
+    const ScriptMasks K = script_masks(L);
     const int grid = (m + BLOCK_THREADS / 4 - 1) / (BLOCK_THREADS / 4);      // a quad per row
 #define SCRIPT_ARGS e->d_state, L, e->n_slots, d_pairs, m, flags, K, d_q
     if (L.FW == 1) k_pit_script<1><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
     else if (L.FW == 2) k_pit_script<2><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
     else k_pit_script<6><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
 #undef SCRIPT_ARGS
+    SNK_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int snk_pit_territory_values(const snk_engine *e, const int32_t *d_pairs, int m, uint32_t flags, int hungry, float *d_q,
+                                        void *stream)
+{
+    SNK_REQUIRE(e != nullptr, "snk_pit_territory_values: engine is NULL");
+    SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
+                "snk_pit_territory_values: unknown flag bits in 0x%x", flags);
+    SNK_REQUIRE(hungry >= 0 && hungry <= 100, "snk_pit_territory_values: hungry=%d outside 0..100", hungry);
+    SNK_REQUIRE(m >= 0, "snk_pit_territory_values: m=%d", m);
+    if (m == 0) return 0;
+    SNK_REQUIRE(d_pairs && d_q, "snk_pit_territory_values: NULL argument");
+    const Layout L = e->L;
+    const ScriptMasks K = script_masks(L);
+    const int grid = (m + BLOCK_THREADS / 4 - 1) / (BLOCK_THREADS / 4);      // a quad per row
+#define TERRITORY_ARGS e->d_state, L, e->n_slots, d_pairs, m, flags, hungry, K, d_q
+    if (L.FW == 1) k_pit_territory<1><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(TERRITORY_ARGS);
+    else if (L.FW == 2) k_pit_territory<2><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(TERRITORY_ARGS);
+    else k_pit_territory<6><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(TERRITORY_ARGS);
+#undef TERRITORY_ARGS
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }

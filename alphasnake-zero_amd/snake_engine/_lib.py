@@ -125,6 +125,7 @@ PROTOTYPES = {
     "snk_pit_roots_owned": (i32, [vp, vp, i32, vp, i32, C.c_uint32, vp, vp, vp, vp, vp, vp]),
     "snk_pit_search_moves_owned": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "snk_pit_script_values": (i32, [vp, vp, i32, C.c_uint32, vp, vp]),
+    "snk_pit_territory_values": (i32, [vp, vp, i32, C.c_uint32, i32, vp, vp]),
     "snk_pit_look_fanout": (i32, [i32]),
     "snk_pit_look_scratch_elems": (C.c_long, [i32, i32]),
     "snk_pit_look_values": (i32, [vp, vp, vp, i32, C.c_uint32, vp, vp, vp]),

@@ -48,6 +48,8 @@ children of a game shared by all its rows at every level, and folds the levels f
 ``Playout`` is flat Monte-Carlo over the same script, the fourth fixed point and the one without a limit on the snakes alive:
 snk_pit_playout_values plays every unblocked move out a few times for several ticks on copies of the game and scores how long the
 snake survives -- launches only again.
+``Territory`` is the fixed point whose judgement differs in kind: snk_pit_territory_values scores a move by the cells the snake
+reaches before anybody else does (Voronoi territory) instead of the cells it reaches if nobody else moves -- one launch, no copies.
 
 ``record(games)`` returns a ``replay.Replay`` that the next match fills with the boards Game.tic(show=True) draws for those games
 (game.py:140-141, 194-195): snk_pit_record_moves before the step and snk_pit_record_boards after it draw them into a log on the
@@ -158,7 +160,30 @@ class Scripted:
         return q
 
 
-LOOK_SLOT_BUDGET = 4096 * 4 * 81     # rows times fanout of one snk_pit_look_values call: a 4 096-game 11x11x4 match, every seat
+class Territory(Scripted):
+    """The scripted policy with Voronoi territory in place of space (include/snake_engine.h states it): a move scores the free
+    cells the snake reaches before any other snake does, every other snake starting from the cells it can stand on after this
+    tick; a tie goes to the longer snake and an equal-length tie to neither.  The food term counts only for a snake whose health
+    is at most `hungry` (0..100): at 100, the default, it always counts and the player is the script with territory for space;
+    below 100 a snake that is not hungry maximises territory.  The same flags and refusals as Scripted, and it sits wherever a
+    Scripted can; a Searcher around it is a TypeError.  One launch of snk_pit_territory_values: no sub-engine, no scratch."""
+
+    def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD, hungry=100):
+        super().__init__(flags)
+        hungry = int(hungry)
+        if not 0 <= hungry <= 100:
+            raise ValueError(f"Territory hungry {hungry}: 0 .. 100")
+        self.hungry = hungry
+
+    def q_rows(self, engine, pairs):
+        """pairs int32[rows][2] (slot, snake id) on the device -> the three move scores float32[rows][3] on the device"""
+        m = int(pairs.shape[0])
+        q = engine.new((m, 3), torch.float32)
+        check(engine.L.snk_pit_territory_values(engine.h, _ptr(pairs), m, self.flags, self.hungry, _ptr(q), _stream()))
+        return q
+
+
+LOOK_SLOT_BUDGET = 4096 * 4 * 81    # rows times fanout of one snk_pit_look_values call: a 4 096-game 11x11x4 match, every seat
 
 
 class Lookahead(Scripted):

@@ -63,8 +63,8 @@ const char *snk_last_error(void);
                              * snk_pit_record_boards) and the tally's (snk_pit_tally) and the lookahead opponent's
                              * (snk_pit_look_fanout, snk_pit_look_scratch_elems, snk_pit_look_values) and the deep opponent's
                              * (snk_pit_deep_fanout, snk_pit_deep_scratch_elems, snk_pit_deep_values) and the playout opponent's
-                             * (snk_pit_playout_clones, snk_pit_playout_scratch_elems, snk_pit_playout_values): no argument list of
-                             * an older one changed */
+                             * (snk_pit_playout_clones, snk_pit_playout_scratch_elems, snk_pit_playout_values) and the territory
+                             * opponent's (snk_pit_territory_values): no argument list of an older one changed */
 int snk_version(void);
 
 /* ---- engine lifetime -------------------------------------------------------------------
@@ -604,6 +604,32 @@ int snk_pit_search_moves_owned(const uint8_t *d_found, const int32_t *d_rank, in
 #define SNK_SCRIPT_HEADS 2u
 #define SNK_SCRIPT_FOOD 4u
 int snk_pit_script_values(const snk_engine *e, const int32_t *d_pairs, int m, uint32_t flags, float *d_q, void *stream);
+
+/* ---- the territory opponent: the scripted policy with Voronoi territory in place of space (the project's own, as above) ---------
+ * snake_engine.arena.Territory sits wherever a Scripted can; tests/territory_ref.py is the statement in plain Python.  The script
+ * asks how many cells the snake reaches if nobody else moves; this asks which cells it reaches before anybody else does.  Integers
+ * only.  For row (slot g, snake s), s alive, and relative move a = 0, 1, 2:
+ *   target, occupied, blocked   exactly as for snk_pit_script_values; a blocked move scores -1
+ *   free       the on-board cells that are not occupied
+ *   start set  of another alive snake t: the targets of t's three relative moves that are free -- the cells t can stand on
+ *              after this tick; it may be empty
+ *   d_s(c)     the fewest 4-neighbour steps from the target to c over free cells; d_s(target) = 0, infinity when c is unreachable
+ *   d_t(c)     the same from the nearest cell of t's start set: 0 on the start set, infinity for an empty set.  Distances are over
+ *              the static free cells only: fronts do not block each other
+ *   strong     alive t != s with len_t >= len_s;  weak: alive t != s with len_t < len_s
+ *   territory  the number of free cells c with d_s(c) finite, d_s(c) < d_t(c) for every strong t and d_s(c) <= d_t(c) for every
+ *              weak t -- the head-on rule: a tie goes to the longer snake, an equal-length tie to neither
+ *   room       min(territory, len_s, 255);  fill: min(territory, 511);  safe: as in the script
+ *   food       the script's food term when health_s <= hungry, else 0
+ *   score      ((room * 2 + safe) * 64 + food) * 512 + fill, below 2^24 and therefore exact as float32
+ * flags are the script's three bits and a bit outside them is an error: without SNK_SCRIPT_SPACE room = fill = 0 (no front is
+ * run), without SNK_SCRIPT_HEADS safe = 1, without SNK_SCRIPT_FOOD food = 0.  hungry: 0..100, anything else is an error; at 100
+ * the food term always counts (the script with territory in place of space), below 100 a snake that is not hungry maximises
+ * territory.  territory <= the script's space for every row and move, and with s the only alive snake the scores at hungry = 100
+ * are snk_pit_script_values' scores.  d_pairs, d_q, m == 0 and the pairs that get -1, -1, -1: as for snk_pit_script_values.
+ * One launch (a quad of lanes per row, as the script's kernel), no sub-engine and no scratch.                                   */
+int snk_pit_territory_values(const snk_engine *e, const int32_t *d_pairs, int m, uint32_t flags, int hungry, float *d_q,
+                             void *stream);
 
 /* ---- the lookahead opponent: the scripted policy one tick deep, a second fixed yardstick (the project's own, as above) -----------
  * snake_engine.arena.Lookahead sits wherever a Scripted can; tests/look_ref.py is the statement in plain Python.  Integers only.

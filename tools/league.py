@@ -21,7 +21,9 @@ scripted owner moves by its script under --search too.  --nets 0 --baseline 0 1 
 --nets 0 --baseline 0 1 3 7 look the same with the lookahead in it.  deep2, deep3, deep4 (a flags digit may follow, as in look5)
 are the deep yardstick (snake_engine.arena.Deep: the script that many ticks deep); the board's snake count limits the depth.
 play and playPxT (play8x16: 8 playouts of 16 ticks) are the playout yardstick (snake_engine.arena.Playout: flat Monte-Carlo over
-the script, with its defaults or P playouts and horizon T).
+the script, with its defaults or P playouts and horizon T).  terr and terrhN (terrh40: the food term counts only at health 40 or
+less; a flags digit may follow terr, as in look5: terr5, terr5h40) are the territory yardstick (snake_engine.arena.Territory: the
+script with Voronoi territory in place of space).
 --replay K DIR (not with --time): the round robin records its first K games (League.record) and writes them as DIR/game_<g>.rep,
 the text of the reference's replay.rep: two boards per tick.
 --tally (not with --time): the round robin also counts every seat's fate on the device (League.tally) and the table is printed
@@ -70,7 +72,7 @@ def main():
     import numpy as np
     import torch
     import playout_names
-    from snake_engine.arena import Arena, Deep, Lookahead, Playout, Scripted, Searcher
+    from snake_engine.arena import Arena, Deep, Lookahead, Playout, Scripted, Searcher, Territory
     from snake_engine.league import SEATS, League, ratings, schedule, searchers, table
     from snake_engine.net import glorot_uniform_weights
     from utils.alpha_nnet import AlphaNNet
@@ -112,6 +114,11 @@ def main():
             if playout_names.parse(flags) is not None:            # play, play8x16: the playout yardstick
                 names.append(flags)
                 nets.append(Playout(**playout_names.parse(flags)))
+            elif flags.startswith("terr"):            # terr, terr5, terrh40, terr5h40: the territory yardstick
+                digits, _, hungry = flags[4:].partition("h")
+                side = Territory(int(digits or 7), int(hungry or 100))
+                names.append(f"terr{side.flags}" + (f"h{side.hungry}" if side.hungry != 100 else ""))
+                nets.append(side)
             elif flags.startswith("deep"):            # deep2, deep3, deep4; deep25: the deep yardstick, depth 2, flags 5
                 names.append(f"deep{int(flags[4])}_{int(flags[5:] or 7)}")
                 nets.append(Deep(int(flags[5:] or 7), int(flags[4])))
