@@ -2875,6 +2875,22 @@ extern "C" int snk_pit_territory_values(const snk_engine *e, const int32_t *d_pa
     return 0;
 }
 
+// the leaf evaluation of the three searching opponents (snk_pit_*_values_leaf): the one-launch scorer of a pair list, the script's
+// flood fill or the Voronoi territory.  Both kernels take the same pair lists -- (-1, -1) entries, records a clone and a step have
+// just written -- and write the same float32[m][3].
+#define LEAF_REFUSAL "%s: leaf=%d, hungry=%d: leaf is SNK_LEAF_SCRIPT with hungry 100 or SNK_LEAF_TERRITORY with hungry 0..100"
+static bool leaf_ok(int leaf, int hungry)
+{
+    return leaf == SNK_LEAF_SCRIPT ? hungry == 100 : leaf == SNK_LEAF_TERRITORY && hungry >= 0 && hungry <= 100;
+}
+
+static int leaf_values(const snk_engine *e, const int32_t *d_pairs, int m, uint32_t flags, int leaf, int hungry, float *d_q,
+                       void *stream)
+{
+    return leaf == SNK_LEAF_TERRITORY ? snk_pit_territory_values(e, d_pairs, m, flags, hungry, d_q, stream)
+                                      : snk_pit_script_values(e, d_pairs, m, flags, d_q, stream);
+}
+
 extern "C" int snk_pit_look_fanout(int S)
 {
     if (S < 2 || S > SNK_MAX_SNAKES) return -1;
@@ -2888,26 +2904,27 @@ extern "C" long snk_pit_look_scratch_elems(int m, int S)
     return look_scratch(m, S, F).total;
 }
 
-extern "C" int snk_pit_look_values(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags,
-                                   int32_t *d_scratch, float *d_q, void *stream)
+extern "C" int snk_pit_look_values_leaf(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int leaf,
+                                        int hungry, int32_t *d_scratch, float *d_q, void *stream)
 {
-    SNK_REQUIRE(e != nullptr && sub != nullptr, "snk_pit_look_values: engine is NULL");
+    SNK_REQUIRE(leaf_ok(leaf, hungry), LEAF_REFUSAL, "snk_pit_look_values_leaf", leaf, hungry);
+    SNK_REQUIRE(e != nullptr && sub != nullptr, "snk_pit_look_values_leaf: engine is NULL");
     SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
-                "snk_pit_look_values: unknown flag bits in 0x%x", flags);
-    SNK_REQUIRE(m >= 0, "snk_pit_look_values: m=%d", m);
-    SNK_REQUIRE(sub != e, "snk_pit_look_values: the sub-engine is the engine itself");
-    SNK_REQUIRE(e->L.H == sub->L.H && e->L.W == sub->L.W && e->L.S == sub->L.S, "snk_pit_look_values: geometry mismatch");
-    SNK_REQUIRE(e->device == sub->device, "snk_pit_look_values: the engines are on devices %d and %d", e->device, sub->device);
+                "snk_pit_look_values_leaf: unknown flag bits in 0x%x", flags);
+    SNK_REQUIRE(m >= 0, "snk_pit_look_values_leaf: m=%d", m);
+    SNK_REQUIRE(sub != e, "snk_pit_look_values_leaf: the sub-engine is the engine itself");
+    SNK_REQUIRE(e->L.H == sub->L.H && e->L.W == sub->L.W && e->L.S == sub->L.S, "snk_pit_look_values_leaf: geometry mismatch");
+    SNK_REQUIRE(e->device == sub->device, "snk_pit_look_values_leaf: the engines are on devices %d and %d", e->device, sub->device);
     SNK_REQUIRE(sub->food_chance == 0.0 && sub->health_dec == e->health_dec,
-                "snk_pit_look_values: the sub-engine must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)",
+                "snk_pit_look_values_leaf: the sub-engine must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)",
                 sub->food_chance, e->health_dec, sub->health_dec);
     if (m == 0) return 0;
-    SNK_REQUIRE(d_pairs && d_scratch && d_q, "snk_pit_look_values: NULL argument");
+    SNK_REQUIRE(d_pairs && d_scratch && d_q, "snk_pit_look_values_leaf: NULL argument");
     const Layout L = e->L;
     const int F = snk_pit_look_fanout(L.S);
-    SNK_REQUIRE((long long)m * F <= LK_MAX_LEAVES, "snk_pit_look_values: m=%d rows of fanout %d exceed %d leaves", m, F, LK_MAX_LEAVES);
+    SNK_REQUIRE((long long)m * F <= LK_MAX_LEAVES, "snk_pit_look_values_leaf: m=%d rows of fanout %d exceed %d leaves", m, F, LK_MAX_LEAVES);
     const int need = m < e->n_slots ? m : e->n_slots;
-    SNK_REQUIRE((long long)need * F <= sub->n_slots, "snk_pit_look_values: %d groups of fanout %d exceed the sub-engine's %d slots", need,
+    SNK_REQUIRE((long long)need * F <= sub->n_slots, "snk_pit_look_values_leaf: %d groups of fanout %d exceed the sub-engine's %d slots", need,
                 F, sub->n_slots);
     const int n_groups = m < sub->n_slots / F ? m : sub->n_slots / F;
     const LookScratch P = look_scratch(m, L.S, F);
@@ -2928,13 +2945,19 @@ extern "C" int snk_pit_look_values(const snk_engine *e, snk_engine *sub, const i
     // the children: Game.subgame of every group's slot F times, one tick of the active ones, s's plain scores on each
     int rc = snk_engine_clone(e, grp_src, n_groups, sub, nullptr, F, stream);
     if (rc == 0) rc = snk_engine_step_active(sub, active, n_groups * F, moves, nullptr, nullptr, stream);
-    if (rc == 0) rc = snk_pit_script_values(sub, leaf_pairs, m * F, flags, leaf_q, stream);
-    if (rc == 0) rc = snk_pit_script_values(e, d_pairs, m, flags, fb_q, stream);
+    if (rc == 0) rc = leaf_values(sub, leaf_pairs, m * F, flags, leaf, hungry, leaf_q, stream);
+    if (rc == 0) rc = leaf_values(e, d_pairs, m, flags, leaf, hungry, fb_q, stream);
     if (rc != 0) return rc;
     k_look_reduce<<<(4 * m + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(sub->d_state, L, m, F, n_groups, d_pairs, row_group,
                                                                               grp_bits, leaf_q, fb_q, d_q);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int snk_pit_look_values(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags,
+                                   int32_t *d_scratch, float *d_q, void *stream)
+{
+    return snk_pit_look_values_leaf(e, sub, d_pairs, m, flags, SNK_LEAF_SCRIPT, 100, d_scratch, d_q, stream);
 }
 
 extern "C" int snk_pit_deep_fanout(int S, int depth)
@@ -2953,44 +2976,45 @@ extern "C" long snk_pit_deep_scratch_elems(int m, int S, int depth)
     return deep_scratch(m, S, snk_pit_look_fanout(S), depth).total;
 }
 
-extern "C" int snk_pit_deep_values(const snk_engine *e, snk_engine *const *subs, int depth, const int32_t *d_pairs, int m,
-                                   uint32_t flags, int32_t *d_scratch, float *d_q, void *stream)
+extern "C" int snk_pit_deep_values_leaf(const snk_engine *e, snk_engine *const *subs, int depth, const int32_t *d_pairs, int m,
+                                        uint32_t flags, int leaf, int hungry, int32_t *d_scratch, float *d_q, void *stream)
 {
-    SNK_REQUIRE(e != nullptr && subs != nullptr, "snk_pit_deep_values: engine is NULL");
+    SNK_REQUIRE(leaf_ok(leaf, hungry), LEAF_REFUSAL, "snk_pit_deep_values_leaf", leaf, hungry);
+    SNK_REQUIRE(e != nullptr && subs != nullptr, "snk_pit_deep_values_leaf: engine is NULL");
     SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
-                "snk_pit_deep_values: unknown flag bits in 0x%x", flags);
-    SNK_REQUIRE(m >= 0, "snk_pit_deep_values: m=%d", m);
+                "snk_pit_deep_values_leaf: unknown flag bits in 0x%x", flags);
+    SNK_REQUIRE(m >= 0, "snk_pit_deep_values_leaf: m=%d", m);
     const Layout L = e->L;
     const int F = snk_pit_look_fanout(L.S), FD = snk_pit_deep_fanout(L.S, depth);
-    SNK_REQUIRE(FD > 0, "snk_pit_deep_values: depth %d with %d snakes (fanout %d) is outside 1 .. the depth at which it reaches %d", depth,
+    SNK_REQUIRE(FD > 0, "snk_pit_deep_values_leaf: depth %d with %d snakes (fanout %d) is outside 1 .. the depth at which it reaches %d", depth,
                 L.S, F, DP_MAX_FANOUT);
     for (int k = 0; k < depth; ++k) {
         const snk_engine *sub = subs[k];
-        SNK_REQUIRE(sub != nullptr, "snk_pit_deep_values: sub-engine %d is NULL", k);
-        SNK_REQUIRE(sub != e, "snk_pit_deep_values: sub-engine %d is the engine itself", k);
-        for (int o = 0; o < k; ++o) SNK_REQUIRE(sub != subs[o], "snk_pit_deep_values: sub-engines %d and %d are the same", o, k);
-        SNK_REQUIRE(L.H == sub->L.H && L.W == sub->L.W && L.S == sub->L.S, "snk_pit_deep_values: geometry mismatch of sub-engine %d", k);
-        SNK_REQUIRE(e->device == sub->device, "snk_pit_deep_values: the engine and sub-engine %d are on devices %d and %d", k, e->device,
+        SNK_REQUIRE(sub != nullptr, "snk_pit_deep_values_leaf: sub-engine %d is NULL", k);
+        SNK_REQUIRE(sub != e, "snk_pit_deep_values_leaf: sub-engine %d is the engine itself", k);
+        for (int o = 0; o < k; ++o) SNK_REQUIRE(sub != subs[o], "snk_pit_deep_values_leaf: sub-engines %d and %d are the same", o, k);
+        SNK_REQUIRE(L.H == sub->L.H && L.W == sub->L.W && L.S == sub->L.S, "snk_pit_deep_values_leaf: geometry mismatch of sub-engine %d", k);
+        SNK_REQUIRE(e->device == sub->device, "snk_pit_deep_values_leaf: the engine and sub-engine %d are on devices %d and %d", k, e->device,
                     sub->device);
         SNK_REQUIRE(sub->food_chance == 0.0 && sub->health_dec == e->health_dec,
-                    "snk_pit_deep_values: sub-engine %d must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)", k,
+                    "snk_pit_deep_values_leaf: sub-engine %d must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)", k,
                     sub->food_chance, e->health_dec, sub->health_dec);
     }
     if (m == 0) return 0;
-    SNK_REQUIRE(d_pairs && d_scratch && d_q, "snk_pit_deep_values: NULL argument");
-    SNK_REQUIRE((long long)m * FD <= LK_MAX_LEAVES, "snk_pit_deep_values: m=%d rows of fanout %d exceed %d leaves", m, FD, LK_MAX_LEAVES);
+    SNK_REQUIRE(d_pairs && d_scratch && d_q, "snk_pit_deep_values_leaf: NULL argument");
+    SNK_REQUIRE((long long)m * FD <= LK_MAX_LEAVES, "snk_pit_deep_values_leaf: m=%d rows of fanout %d exceed %d leaves", m, FD, LK_MAX_LEAVES);
     const int need = m < e->n_slots ? m : e->n_slots;
     int n_groups = m;                                     // the groups every level can hold
     {
         long long pw = 1;
         for (int k = 0; k < depth; ++k) {
             pw *= F;
-            SNK_REQUIRE(need * pw <= subs[k]->n_slots, "snk_pit_deep_values: %d groups of fanout %lld exceed sub-engine %d's %d slots", need,
+            SNK_REQUIRE(need * pw <= subs[k]->n_slots, "snk_pit_deep_values_leaf: %d groups of fanout %lld exceed sub-engine %d's %d slots", need,
                         pw, k, subs[k]->n_slots);
             if (subs[k]->n_slots / pw < n_groups) n_groups = (int)(subs[k]->n_slots / pw);
         }
     }
-    if (depth == 1) return snk_pit_look_values(e, subs[0], d_pairs, m, flags, d_scratch, d_q, stream);
+    if (depth == 1) return snk_pit_look_values_leaf(e, subs[0], d_pairs, m, flags, leaf, hungry, d_scratch, d_q, stream);
     const DeepScratch P = deep_scratch(m, L.S, F, depth);
     int32_t *tile_sums = d_scratch + P.tile_sums, *row_group = d_scratch + P.row_group;
     int32_t *grp_src = d_scratch + P.grp_src, *grp_bits = d_scratch + P.grp_bits, *leaf_pairs = d_scratch + P.leaf_pairs;
@@ -3003,7 +3027,7 @@ extern "C" int snk_pit_deep_values(const snk_engine *e, snk_engine *const *subs,
     k_look_groups<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, L, e->n_slots, d_pairs, m, tile_sums, count, n_groups, row_group, grp_src,
                                                 grp_bits);
     SNK_CHECK_HIP(hipGetLastError());
-    int rc = snk_pit_script_values(e, d_pairs, m, flags, fb_q, stream);
+    int rc = leaf_values(e, d_pairs, m, flags, leaf, hungry, fb_q, stream);
     // level by level: the nodes' flags and moves from the stepped level above, Game.subgame of every node above F times, one tick
     int nodes = n_groups;                                 // of the level above
     for (int k = 0; k < depth && rc == 0; ++k) {
@@ -3023,7 +3047,7 @@ extern "C" int snk_pit_deep_values(const snk_engine *e, snk_engine *const *subs,
         m, FD, L.S, n_groups, subs[depth - 1]->n_slots, d_pairs, row_group, grp_bits, (const uint8_t *)(d_scratch + P.active[depth - 1]),
         leaf_pairs);
     SNK_CHECK_HIP(hipGetLastError());
-    rc = snk_pit_script_values(subs[depth - 1], leaf_pairs, m * FD, flags, leaf_q, stream);
+    rc = leaf_values(subs[depth - 1], leaf_pairs, m * FD, flags, leaf, hungry, leaf_q, stream);
     if (rc != 0) return rc;
     // the fold, from the last level up: level k + 1 (subs[k]) into level k
     int per = FD / F;                                     // parents per row: F^k
@@ -3039,6 +3063,12 @@ extern "C" int snk_pit_deep_values(const snk_engine *e, snk_engine *const *subs,
     return 0;
 }
 
+extern "C" int snk_pit_deep_values(const snk_engine *e, snk_engine *const *subs, int depth, const int32_t *d_pairs, int m,
+                                   uint32_t flags, int32_t *d_scratch, float *d_q, void *stream)
+{
+    return snk_pit_deep_values_leaf(e, subs, depth, d_pairs, m, flags, SNK_LEAF_SCRIPT, 100, d_scratch, d_q, stream);
+}
+
 extern "C" int snk_pit_playout_clones(int P) { return P < 1 || P > PL_MAX_PLAYOUTS ? -1 : 3 * P; }
 
 extern "C" long snk_pit_playout_scratch_elems(int m, int S, int P)
@@ -3047,29 +3077,31 @@ extern "C" long snk_pit_playout_scratch_elems(int m, int S, int P)
     return play_scratch(m, S, P).total;
 }
 
-extern "C" int snk_pit_playout_values(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int P, int T,
-                                      int eps, uint64_t seed, int32_t *d_scratch, float *d_q, void *stream)
+extern "C" int snk_pit_playout_values_leaf(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int leaf,
+                                           int hungry, int P, int T, int eps, uint64_t seed, int32_t *d_scratch, float *d_q,
+                                           void *stream)
 {
-    SNK_REQUIRE(e != nullptr && sub != nullptr, "snk_pit_playout_values: engine is NULL");
+    SNK_REQUIRE(leaf_ok(leaf, hungry), LEAF_REFUSAL, "snk_pit_playout_values_leaf", leaf, hungry);
+    SNK_REQUIRE(e != nullptr && sub != nullptr, "snk_pit_playout_values_leaf: engine is NULL");
     SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
-                "snk_pit_playout_values: unknown flag bits in 0x%x", flags);
-    SNK_REQUIRE(m >= 0, "snk_pit_playout_values: m=%d", m);
-    SNK_REQUIRE(P >= 1 && P <= PL_MAX_PLAYOUTS, "snk_pit_playout_values: playouts P=%d outside 1..%d", P, PL_MAX_PLAYOUTS);
-    SNK_REQUIRE(T >= 1 && T <= PL_MAX_HORIZON, "snk_pit_playout_values: horizon T=%d outside 1..%d", T, PL_MAX_HORIZON);
-    SNK_REQUIRE(eps >= 0 && eps <= PL_MAX_EXPLORE, "snk_pit_playout_values: explore eps=%d outside 0..%d", eps, PL_MAX_EXPLORE);
-    SNK_REQUIRE(sub != e, "snk_pit_playout_values: the sub-engine is the engine itself");
-    SNK_REQUIRE(e->L.H == sub->L.H && e->L.W == sub->L.W && e->L.S == sub->L.S, "snk_pit_playout_values: geometry mismatch");
-    SNK_REQUIRE(e->device == sub->device, "snk_pit_playout_values: the engines are on devices %d and %d", e->device, sub->device);
+                "snk_pit_playout_values_leaf: unknown flag bits in 0x%x", flags);
+    SNK_REQUIRE(m >= 0, "snk_pit_playout_values_leaf: m=%d", m);
+    SNK_REQUIRE(P >= 1 && P <= PL_MAX_PLAYOUTS, "snk_pit_playout_values_leaf: playouts P=%d outside 1..%d", P, PL_MAX_PLAYOUTS);
+    SNK_REQUIRE(T >= 1 && T <= PL_MAX_HORIZON, "snk_pit_playout_values_leaf: horizon T=%d outside 1..%d", T, PL_MAX_HORIZON);
+    SNK_REQUIRE(eps >= 0 && eps <= PL_MAX_EXPLORE, "snk_pit_playout_values_leaf: explore eps=%d outside 0..%d", eps, PL_MAX_EXPLORE);
+    SNK_REQUIRE(sub != e, "snk_pit_playout_values_leaf: the sub-engine is the engine itself");
+    SNK_REQUIRE(e->L.H == sub->L.H && e->L.W == sub->L.W && e->L.S == sub->L.S, "snk_pit_playout_values_leaf: geometry mismatch");
+    SNK_REQUIRE(e->device == sub->device, "snk_pit_playout_values_leaf: the engines are on devices %d and %d", e->device, sub->device);
     SNK_REQUIRE(sub->food_chance == 0.0 && sub->health_dec == e->health_dec,
-                "snk_pit_playout_values: the sub-engine must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)",
+                "snk_pit_playout_values_leaf: the sub-engine must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)",
                 sub->food_chance, e->health_dec, sub->health_dec);
     const Layout L = e->L;
-    SNK_REQUIRE((long long)m * 3 * P * L.S <= LK_MAX_LEAVES, "snk_pit_playout_values: m=%d rows of %d clones and %d snakes exceed %d", m,
+    SNK_REQUIRE((long long)m * 3 * P * L.S <= LK_MAX_LEAVES, "snk_pit_playout_values_leaf: m=%d rows of %d clones and %d snakes exceed %d", m,
                 3 * P, L.S, LK_MAX_LEAVES);
-    SNK_REQUIRE((long long)m * 3 * P <= sub->n_slots, "snk_pit_playout_values: %d rows of %d clones exceed the sub-engine's %d slots", m,
+    SNK_REQUIRE((long long)m * 3 * P <= sub->n_slots, "snk_pit_playout_values_leaf: %d rows of %d clones exceed the sub-engine's %d slots", m,
                 3 * P, sub->n_slots);
     if (m == 0) return 0;
-    SNK_REQUIRE(d_pairs && d_scratch && d_q, "snk_pit_playout_values: NULL argument");
+    SNK_REQUIRE(d_pairs && d_scratch && d_q, "snk_pit_playout_values_leaf: NULL argument");
     const int n = m * 3 * P;                              // the clones
     const PlayScratch Z = play_scratch(m, L.S, P);
     float *fb_q = (float *)(d_scratch + Z.fb_q), *cq = (float *)(d_scratch + Z.q);
@@ -3078,7 +3110,7 @@ extern "C" int snk_pit_playout_values(const snk_engine *e, snk_engine *sub, cons
     hipStream_t st = (hipStream_t)stream;
     const int grid = (n + CMP_THREADS - 1) / CMP_THREADS;
     // the rows' own plain scores (the fallback, the blocked moves, the tie-break), the plan, Game.subgame of every played clone
-    int rc = snk_pit_script_values(e, d_pairs, m, flags, fb_q, stream);
+    int rc = leaf_values(e, d_pairs, m, flags, leaf, hungry, fb_q, stream);
     if (rc != 0) return rc;
     k_play_plan<<<grid, CMP_THREADS, 0, st>>>(e->d_state, L, e->n_slots, sub->n_slots, d_pairs, n, P, fb_q, src, fate, active, moves,
                                              cl_pairs);
@@ -3086,7 +3118,7 @@ extern "C" int snk_pit_playout_values(const snk_engine *e, snk_engine *sub, cons
     rc = snk_engine_clone(e, src, n, sub, nullptr, 1, stream);
     // T ticks: every alive snake's plain scores on every clone, the moves, the step of the clones still running
     for (int i = 0; i < T && rc == 0; ++i) {
-        rc = snk_pit_script_values(sub, cl_pairs, n * L.S, flags, cq, stream);
+        rc = leaf_values(sub, cl_pairs, n * L.S, flags, leaf, hungry, cq, stream);
         if (rc != 0) break;
         k_play_pick<<<grid, CMP_THREADS, 0, st>>>(sub->d_state, L, n, P, T, i, eps, (uint32_t)seed, (uint32_t)(seed >> 32), d_pairs, cq,
                                                  fate, active, moves);
@@ -3097,6 +3129,12 @@ extern "C" int snk_pit_playout_values(const snk_engine *e, snk_engine *sub, cons
     k_play_fold<<<(4 * m + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(sub->d_state, L, m, P, T, d_pairs, fb_q, fate, d_q);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int snk_pit_playout_values(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int P, int T,
+                                      int eps, uint64_t seed, int32_t *d_scratch, float *d_q, void *stream)
+{
+    return snk_pit_playout_values_leaf(e, sub, d_pairs, m, flags, SNK_LEAF_SCRIPT, 100, P, T, eps, seed, d_scratch, d_q, stream);
 }
 
 extern "C" int snk_pit_record_stride(int H, int W)

@@ -129,12 +129,15 @@ PROTOTYPES = {
     "snk_pit_look_fanout": (i32, [i32]),
     "snk_pit_look_scratch_elems": (C.c_long, [i32, i32]),
     "snk_pit_look_values": (i32, [vp, vp, vp, i32, C.c_uint32, vp, vp, vp]),
+    "snk_pit_look_values_leaf": (i32, [vp, vp, vp, i32, C.c_uint32, i32, i32, vp, vp, vp]),
     "snk_pit_deep_fanout": (i32, [i32, i32]),
     "snk_pit_deep_scratch_elems": (C.c_long, [i32, i32, i32]),
     "snk_pit_deep_values": (i32, [vp, vp, i32, vp, i32, C.c_uint32, vp, vp, vp]),
+    "snk_pit_deep_values_leaf": (i32, [vp, vp, i32, vp, i32, C.c_uint32, i32, i32, vp, vp, vp]),
     "snk_pit_playout_clones": (i32, [i32]),
     "snk_pit_playout_scratch_elems": (C.c_long, [i32, i32, i32]),
     "snk_pit_playout_values": (i32, [vp, vp, vp, i32, C.c_uint32, i32, i32, i32, u64, vp, vp, vp]),
+    "snk_pit_playout_values_leaf": (i32, [vp, vp, vp, i32, C.c_uint32, i32, i32, i32, i32, i32, u64, vp, vp, vp]),
     "snk_pit_record_stride": (i32, [i32, i32]),
     "snk_pit_record_slots": (i32, [vp, vp, i32, vp, vp]),
     "snk_pit_record_moves": (i32, [vp, vp, vp, i32, vp, vp, vp]),

@@ -50,6 +50,10 @@ snk_pit_playout_values plays every unblocked move out a few times for several ti
 snake survives -- launches only again.
 ``Territory`` is the fixed point whose judgement differs in kind: snk_pit_territory_values scores a move by the cells the snake
 reaches before anybody else does (Voronoi territory) instead of the cells it reaches if nobody else moves -- one launch, no copies.
+``Lookahead``, ``Deep`` and ``Playout`` take ``leaf=Territory(flags, hungry)``: the searches as they are with the territory
+evaluation wherever they asked the plain script -- the fallback rows, the leaves, the playout's plain scores and its playout moves
+(snk_pit_look_values_leaf, snk_pit_deep_values_leaf, snk_pit_playout_values_leaf).  The same buffers, the same chunks, launches only;
+without a leaf they are the players they were and call the entry points they called.
 
 ``record(games)`` returns a ``replay.Replay`` that the next match fills with the boards Game.tic(show=True) draws for those games
 (game.py:140-141, 194-195): snk_pit_record_moves before the step and snk_pit_record_boards after it draw them into a log on the
@@ -183,6 +187,20 @@ class Territory(Scripted):
         return q
 
 
+LEAF_SCRIPT, LEAF_TERRITORY = 0, 1                         # SNK_LEAF_* of include/snake_engine.h
+
+
+def checked_leaf(leaf, flags):
+    """the leaf evaluation of a Lookahead, a Deep or a Playout with these flags: None (the plain script; a plain Scripted means
+    the same) or a Territory.  A leaf is a one-launch evaluation, so every other object -- a searching opponent too -- is a
+    TypeError, and one flag set governs the root, the fallback and the leaves: other flags are a ValueError"""
+    if leaf is not None and type(leaf) not in (Scripted, Territory):
+        raise TypeError(f"leaf is a {type(leaf).__name__}: None, a plain Scripted or a Territory expected")
+    if leaf is not None and leaf.flags != flags:
+        raise ValueError(f"the leaf's flags {leaf.flags:#x} differ from the player's {flags:#x}")
+    return leaf if type(leaf) is Territory else None
+
+
 LOOK_SLOT_BUDGET = 4096 * 4 * 81    # rows times fanout of one snk_pit_look_values call: a 4 096-game 11x11x4 match, every seat
 
 
@@ -193,10 +211,12 @@ class Lookahead(Scripted):
     Scripted can (mixed_values asks isinstance(side, Scripted)); a Searcher around it is a TypeError.  It owns a sub-engine
     without food spawning for the copies and the scratch of snk_pit_look_values, made at first use, remade when the geometry or
     the device changes, and grown when more rows arrive; the sub-engine holds min(rows, games) * fanout slots and a call takes
-    at most LOOK_SLOT_BUDGET // fanout rows, so it never exceeds LOOK_SLOT_BUDGET slots."""
+    at most LOOK_SLOT_BUDGET // fanout rows, so it never exceeds LOOK_SLOT_BUDGET slots.  leaf=Territory(flags, hungry) -- the
+    player's own flags -- scores the copies and the fallback rows by territory instead (snk_pit_look_values_leaf); .leaf keeps it."""
 
-    def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD):
+    def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD, leaf=None):
         super().__init__(flags)
+        self.leaf = checked_leaf(leaf, self.flags)
         self._sub = self._scratch = None
 
     def _buffers(self, engine, rows, F):
@@ -227,8 +247,12 @@ class Lookahead(Scripted):
         for lo in range(0, m, per):
             cnt = min(per, m - lo)
             sub, scratch = self._buffers(engine, cnt, F)
-            check(engine.L.snk_pit_look_values(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, _ptr(scratch),
-                                               _ptr(q[lo:lo + cnt]), _stream()))
+            if self.leaf is None:
+                check(engine.L.snk_pit_look_values(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, _ptr(scratch),
+                                                   _ptr(q[lo:lo + cnt]), _stream()))
+            else:
+                check(engine.L.snk_pit_look_values_leaf(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, LEAF_TERRITORY,
+                                                        self.leaf.hungry, _ptr(scratch), _ptr(q[lo:lo + cnt]), _stream()))
         return q
 
 
@@ -243,10 +267,11 @@ class Deep(Scripted):
     food spawning (level k holds min(rows, games) * fanout^k slots) and the scratch of snk_pit_deep_values, made at first use,
     remade when the geometry or the device changes, and grown when more rows arrive.  A call takes as many rows as keep the
     sub-engines' records within DEEP_BYTE_BUDGET bytes, at least one; a depth the board's snake count cannot have
-    (snk_pit_deep_fanout) is refused at first use."""
+    (snk_pit_deep_fanout) is refused at first use.  leaf=Territory(flags, hungry) as for Lookahead (snk_pit_deep_values_leaf)."""
 
-    def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD, depth=2):
+    def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD, depth=2, leaf=None):
         super().__init__(flags)
+        self.leaf = checked_leaf(leaf, self.flags)
         depth = int(depth)
         if depth < 1:
             raise ValueError(f"Deep depth {depth}: at least 1")
@@ -288,8 +313,13 @@ class Deep(Scripted):
         for lo in range(0, m, per):
             cnt = min(per, m - lo)
             subs, handles, scratch = self._buffers(engine, cnt, F)
-            check(engine.L.snk_pit_deep_values(engine.h, _ptr(handles), self.depth, _ptr(pairs[lo:lo + cnt]), cnt, self.flags,
-                                               _ptr(scratch), _ptr(q[lo:lo + cnt]), _stream()))
+            if self.leaf is None:
+                check(engine.L.snk_pit_deep_values(engine.h, _ptr(handles), self.depth, _ptr(pairs[lo:lo + cnt]), cnt, self.flags,
+                                                   _ptr(scratch), _ptr(q[lo:lo + cnt]), _stream()))
+            else:
+                check(engine.L.snk_pit_deep_values_leaf(engine.h, _ptr(handles), self.depth, _ptr(pairs[lo:lo + cnt]), cnt, self.flags,
+                                                        LEAF_TERRITORY, self.leaf.hungry, _ptr(scratch), _ptr(q[lo:lo + cnt]),
+                                                        _stream()))
         return q
 
 
@@ -306,10 +336,13 @@ class Playout(Scripted):
     (8 playouts, 8 ticks, explore 64) are a starting point, not tuned values.  The same flags and refusals as Scripted, and it
     sits wherever a Scripted can; a Searcher around it is a TypeError.  It owns a sub-engine without food spawning for the
     clones and the scratch of snk_pit_playout_values, made at first use, remade when the geometry or the device changes, and
-    grown when more rows arrive; a call takes at most PLAYOUT_SLOT_BUDGET // (3 * playouts) rows, at least one."""
+    grown when more rows arrive; a call takes at most PLAYOUT_SLOT_BUDGET // (3 * playouts) rows, at least one.
+    leaf=Territory(flags, hungry) as for Lookahead: the plain scores and every playout move are territory's
+    (snk_pit_playout_values_leaf)."""
 
-    def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD, playouts=8, horizon=8, explore=64, seed=0):
+    def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD, playouts=8, horizon=8, explore=64, seed=0, leaf=None):
         super().__init__(flags)
+        self.leaf = checked_leaf(leaf, self.flags)
         playouts, horizon, explore, seed = int(playouts), int(horizon), int(explore), int(seed)
         if not 1 <= playouts <= 64:
             raise ValueError(f"Playout playouts {playouts}: 1 .. 64")
@@ -349,8 +382,14 @@ class Playout(Scripted):
         for lo in range(0, m, per):
             cnt = min(per, m - lo)
             sub, scratch = self._buffers(engine, cnt)
-            check(engine.L.snk_pit_playout_values(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, self.playouts, self.horizon,
-                                                  self.explore, self.seed, _ptr(scratch), _ptr(q[lo:lo + cnt]), _stream()))
+            if self.leaf is None:
+                check(engine.L.snk_pit_playout_values(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, self.playouts,
+                                                      self.horizon, self.explore, self.seed, _ptr(scratch), _ptr(q[lo:lo + cnt]),
+                                                      _stream()))
+            else:
+                check(engine.L.snk_pit_playout_values_leaf(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, LEAF_TERRITORY,
+                                                           self.leaf.hungry, self.playouts, self.horizon, self.explore, self.seed,
+                                                           _ptr(scratch), _ptr(q[lo:lo + cnt]), _stream()))
         return q
 
 

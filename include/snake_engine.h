@@ -64,7 +64,8 @@ const char *snk_last_error(void);
                              * (snk_pit_look_fanout, snk_pit_look_scratch_elems, snk_pit_look_values) and the deep opponent's
                              * (snk_pit_deep_fanout, snk_pit_deep_scratch_elems, snk_pit_deep_values) and the playout opponent's
                              * (snk_pit_playout_clones, snk_pit_playout_scratch_elems, snk_pit_playout_values) and the territory
-                             * opponent's (snk_pit_territory_values): no argument list of an older one changed */
+                             * opponent's (snk_pit_territory_values) and territory at the leaf (snk_pit_look_values_leaf,
+                             * snk_pit_deep_values_leaf, snk_pit_playout_values_leaf): no argument list of an older one changed */
 int snk_version(void);
 
 /* ---- engine lifetime -------------------------------------------------------------------
@@ -763,6 +764,39 @@ int snk_pit_playout_clones(int P);
 long snk_pit_playout_scratch_elems(int m, int S, int P);
 int snk_pit_playout_values(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int P, int T, int eps,
                            uint64_t seed, int32_t *d_scratch, float *d_q, void *stream);
+
+/* ---- territory at the leaf: the three searching opponents with their one-launch evaluation as a parameter (the project's own) ----
+ * snake_engine.arena.Lookahead / Deep / Playout take leaf=Territory(flags, hungry); tests/leaf_ref.py is the statement in plain
+ * Python.  leaf names the evaluation that scores a pair list in one launch, hungry is its threshold:
+ *   SNK_LEAF_SCRIPT     snk_pit_script_values; hungry must be 100, anything else is an error
+ *   SNK_LEAF_TERRITORY  snk_pit_territory_values with `hungry`, 0..100
+ * The statement of snk_pit_X_values_leaf is the statement of snk_pit_X_values above with every "what snk_pit_script_values gives
+ * with the same flags" read as "what the leaf evaluation gives with the same flags and hungry".  With SNK_LEAF_TERRITORY that is:
+ *   the fallback rows   of all three (A < 2; in the lookahead and the deep search A > 4 too): exactly snk_pit_territory_values'
+ *                       three scores of the row
+ *   leaf                of the lookahead and of V_1 of the deep search: the largest of s's three territory scores on c
+ *   plain(a)            of the playout: the row's three territory scores on the game itself, in the blocked moves, in the tie-break
+ *                       term of the score and in the fallback
+ *   move                of the playout: q = t's three territory scores on the clone as it stands, for every snake at every tick;
+ *                       health falls by health_dec a tick on the clones, so a snake may turn hungry inside a playout
+ * Nothing else changes: DEAD, WIN = 2^24, the punishments -2 - dead - 32 (k-1), the grouping and the slot layout of the
+ * sub-engines, the Philox key, the value and the score of a playout, the tie order of snk_pit_moves.  A territory score lies in the
+ * script's range (-1 .. 2^24 - 1), so every bound stated above holds.  Identities:
+ *   with SNK_LEAF_SCRIPT and hungry = 100 each call writes what its namesake without _leaf writes, bit for bit (the namesakes are
+ *     these calls with those two arguments);
+ *   snk_pit_deep_values_leaf at depth 1 calls snk_pit_look_values_leaf and is that call bit for bit.
+ * Scratch: snk_pit_look_scratch_elems / snk_pit_deep_scratch_elems / snk_pit_playout_scratch_elems, unchanged.  The sub-engine
+ * requirements, the rows that get -1, -1, -1, m == 0 and every refusal are the namesake's; a leaf outside the two constants and a
+ * hungry outside what the leaf allows are two more errors before any launch.  Launches: the namesake's, with k_pit_territory
+ * where k_pit_script stood -- one launch per evaluation, no further scratch.                                                      */
+#define SNK_LEAF_SCRIPT 0
+#define SNK_LEAF_TERRITORY 1
+int snk_pit_look_values_leaf(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int leaf, int hungry,
+                             int32_t *d_scratch, float *d_q, void *stream);
+int snk_pit_deep_values_leaf(const snk_engine *e, snk_engine *const *subs, int depth, const int32_t *d_pairs, int m, uint32_t flags,
+                             int leaf, int hungry, int32_t *d_scratch, float *d_q, void *stream);
+int snk_pit_playout_values_leaf(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int leaf,
+                                int hungry, int P, int T, int eps, uint64_t seed, int32_t *d_scratch, float *d_q, void *stream);
 
 /* ---- replays of chosen games of a pit match (Game.draw game.py:281-300, called by Game.tic game.py:140-141 and 194-195) ----------
  * snake_engine.replay.Replay: the two boards Game.tic(show=True) appends per tick, drawn by kernels into a log in device memory for

@@ -23,7 +23,8 @@ are the deep yardstick (snake_engine.arena.Deep: the script that many ticks deep
 play and playPxT (play8x16: 8 playouts of 16 ticks) are the playout yardstick (snake_engine.arena.Playout: flat Monte-Carlo over
 the script, with its defaults or P playouts and horizon T).  terr and terrhN (terrh40: the food term counts only at health 40 or
 less; a flags digit may follow terr, as in look5: terr5, terr5h40) are the territory yardstick (snake_engine.arena.Territory: the
-script with Voronoi territory in place of space).
+script with Voronoi territory in place of space).  A t behind look, deepN, play or playPxT puts territory at the leaf of that search
+(lookt, deep2t, deep3t, playt: leaf=Territory()), thN the territory with that threshold (lookth40, deep2th40, playth40).
 --replay K DIR (not with --time): the round robin records its first K games (League.record) and writes them as DIR/game_<g>.rep,
 the text of the reference's replay.rep: two boards per tick.
 --tally (not with --time): the round robin also counts every seat's fate on the device (League.tally) and the table is printed
@@ -71,7 +72,9 @@ def main():
     a = ap.parse_args()
     import numpy as np
     import torch
+    import leaf_names
     import playout_names
+    from snake_engine import arena
     from snake_engine.arena import Arena, Deep, Lookahead, Playout, Scripted, Searcher, Territory
     from snake_engine.league import SEATS, League, ratings, schedule, searchers, table
     from snake_engine.net import glorot_uniform_weights
@@ -111,7 +114,10 @@ def main():
         nets = [Counted(net) for net in nets]
     if a.baseline is not None:
         for flags in a.baseline or ["7"]:
-            if playout_names.parse(flags) is not None:            # play, play8x16: the playout yardstick
+            if leaf_names.parse(flags) is not None:               # lookt, deep2th40, playt: a search with territory at the leaf
+                names.append(flags)
+                nets.append(leaf_names.player(flags, arena))
+            elif playout_names.parse(flags) is not None:          # play, play8x16: the playout yardstick
                 names.append(flags)
                 nets.append(Playout(**playout_names.parse(flags)))
             elif flags.startswith("terr"):            # terr, terr5, terrh40, terr5h40: the territory yardstick

@@ -1,7 +1,7 @@
 """The scripted opponent's cost (snake_engine.arena.Scripted, snk_pit_script_values) beside what it replaces for its seats.
 
     python tools/script_time.py [--reps 20] [--pairs 3] [--games 300 4096] [--blocks 4] [--log profiles/script_time.log]
-                                [--forms script look deep play terr net]
+                                [--forms script look deep play terr net lookt deep2t playt lookth40 ...]
 
 kernel: HIP-event time of one snk_pit_script_values launch over the first 16 384 alive rows of 11x11x4 boards and the first 4 096
 of 19x19x8 boards, both taken from games the script itself has played for 20 turns (mid-game bodies, some snakes dead), beside the
@@ -14,12 +14,17 @@ match: ms per turn of Arena.match(Scripted, Scripted) beside Lookahead against L
 Playout, Territory against Territory and greedy net against greedy net (1 v 3,
 11x11), alternating inside this one process, --pairs times; a host clock around a match that ends in a device synchronise.
 --forms: the players that are timed, all six by default; script is always among them (the others are given beside it).  The
-lookahead line needs look, the deep and playout lines need look too (they are given as multiples of it)."""
+lookahead line needs look, the deep and playout lines need look too (they are given as multiples of it).  deep2 is deep.  A name
+of tools/leaf_names.py (lookt, deep2t, playt, lookth40, ...: that search with territory at the leaf) adds one line per board: one
+call of the _leaf entry point (snk_pit_look_values_leaf, ...) by events beside the plain call over the same rows, timed next to
+it, and the player against itself among the matches."""
 import argparse
 import os
 import statistics
 import sys
 import time
+
+import leaf_names
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (REPO, os.path.join(REPO, "alphasnake-zero_amd")):
@@ -37,9 +42,12 @@ def main():
     ap.add_argument("--games", type=int, nargs="*", default=[300, 4096])
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--log", default=None)
-    ap.add_argument("--forms", nargs="+", default=list(FORMS), choices=FORMS)
+    ap.add_argument("--forms", nargs="+", default=list(FORMS),
+                    type=lambda v: v if v in FORMS + ("deep2",) or leaf_names.parse(v) is not None
+                    else ap.error(f"--forms {v}: one of {' '.join(FORMS)}, deep2, or a search with t or thN behind it (lookt, deep2th40)"))
     a = ap.parse_args()
-    forms = set(a.forms) | {"script"}
+    leaf_forms = [v for v in dict.fromkeys(a.forms) if leaf_names.parse(v) is not None]
+    forms = {"deep" if v == "deep2" else v for v in a.forms if v not in leaf_forms} | {"script"}
     if forms & {"deep", "play"} and "look" not in forms:
         ap.error("--forms deep and play are given as multiples of look: name look as well")
     import torch
@@ -62,6 +70,12 @@ def main():
     say(f"script_time: {torch.cuda.get_device_name(0)} ({prop.gcnArchName}, {prop.multi_processor_count} CUs), ROCm / HIP "
         f"{torch.version.hip}, torch {torch.__version__}")
     script, look, deep, play, terr = Scripted(), Lookahead(), Deep(depth=2), Playout(), Territory()
+
+    def plain_of(name):
+        """the player of a leaf name without its leaf"""
+        kind, kw, _ = leaf_names.parse(name)
+        return {"look": Lookahead, "deep": Deep, "play": Playout}[kind](**kw)
+    leaf_sides = {name: (plain_of(name), leaf_names.player(name, arena_mod)) for name in leaf_forms}
 
     def events(fn):
         fn()
@@ -130,6 +144,14 @@ def main():
             say(f"kernel: {hw}x{hw}x{S}, the same {rows} rows: snk_pit_territory_values {te[0]:.1f} us (min {te[1]:.1f}, max {te[2]:.1f}), "
                 f"{te[0] / k2[0]:.1f}x snk_pit_script_values ({k2[0]:.1f} us, min {k2[1]:.1f}, max {k2[2]:.1f}, timed beside it); one launch, "
                 f"no sub-engine")
+        for name, (plain, leafed) in leaf_sides.items():
+            plain.q_rows(eng, pairs)                 # the sub-engines and the scratch are made outside the timing
+            leafed.q_rows(eng, pairs)
+            pe = events(lambda: plain.q_rows(eng, pairs))
+            le = events(lambda: leafed.q_rows(eng, pairs))
+            say(f"kernel: {hw}x{hw}x{S}, the same {rows} rows: {name} ({type(leafed).__name__} with leaf Territory(hungry={leafed.leaf.hungry}), "
+                f"the _leaf entry point) {le[0]:.1f} us (min {le[1]:.1f}, max {le[2]:.1f}), {le[0] / pe[0]:.3f}x the plain call "
+                f"({pe[0]:.1f} us, min {pe[1]:.1f}, max {pe[2]:.1f}, timed beside it)")
 
     sides_of = {"script v script": (script, Scripted())}
     Arena(11, 11, 4, 1, 64, 99).match(script, Scripted(), 1)           # first launches settle outside the timing
@@ -142,6 +164,8 @@ def main():
     if "terr" in forms:
         sides_of["terr v terr"] = (terr, Territory())
         Arena(11, 11, 4, 1, 64, 99).match(terr, Territory(), 1)
+    for name in leaf_forms:
+        sides_of[f"{name} v {name}"] = (leaf_names.player(name, arena_mod), leaf_names.player(name, arena_mod))
     if "net" in forms:
         nets = [AlphaNNet(input_shape=(21, 21, 3), _weights=glorot_uniform_weights((21, 21, 3), a.blocks, seed=s)) for s in (1, 2)]
         Arena(11, 11, 4, 1, 64, 99).match(nets[0], nets[1], 1)         # plans and range-guard scales settle outside the timing

@@ -2,7 +2,7 @@
 (snake_engine.arena.Searcher) and a greedy side of the SAME net, 11x11.
 
     python tools/search_pit.py [--games 300] [--breadth 16] [--depth 8] [--blocks 4] [--weights CKPT] [--seed 1]
-                               [--time] [--pairs 2] [--log profiles/arena_search.log] [--baseline [script|look|deep2|deep3|deep4|play|playPxT|terr]] [--replay K DIR] [--tally]
+                               [--time] [--pairs 2] [--log profiles/arena_search.log] [--baseline [script|look|deep2|deep3|deep4|play|playPxT|terr|lookt|deep2t|playt|lookth40|...]] [--replay K DIR] [--tally]
 
 Strength (default): 1 v 3 with the searcher alone, 1 v 3 with the searcher's three against the greedy one, and the duel; win and
 draw rates of the searching side with their binomial 95 % intervals (Wilson), ms per turn and net evaluations per turn.
@@ -14,7 +14,9 @@ of against itself: the greedy net in the duel and in 1 v 3 both ways, then the n
 win and draw rates with the same intervals.  --baseline look: the same against the lookahead yardstick
 (snake_engine.arena.Lookahead: the script one tick deep); --baseline deep2 (deep3, deep4): against snake_engine.arena.Deep of that depth;
 --baseline play (playPxT, e.g. play8x16): against snake_engine.arena.Playout with its defaults (P playouts of T ticks);
---baseline terr: against snake_engine.arena.Territory with its defaults (the script with Voronoi territory in place of space).
+--baseline terr: against snake_engine.arena.Territory with its defaults (the script with Voronoi territory in place of space);
+--baseline lookt, deep2t, deep3t, playt (lookth40, deep2th40, playth40): against that search with leaf=Territory()
+(Territory(hungry=40)), the names of tools/leaf_names.py.
 --replay K DIR: the first match the run reports (strength or --baseline) records its first K games (Arena.record) and writes them
 as DIR/game_<g>.rep, the text of the reference's replay.rep: two boards per tick.
 --tally: the first match the run reports also counts every seat's fate on the device (Arena.tally) and prints the table: per side
@@ -28,6 +30,7 @@ import statistics
 import sys
 import time
 
+import leaf_names
 import playout_names
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,11 +61,13 @@ def main():
     ap.add_argument("--log", default=None)
     ap.add_argument("--baseline", nargs="?", const="script", default=None,
                     type=lambda v: v if v in ("script", "look", "deep2", "deep3", "deep4", "terr") or playout_names.parse(v) is not None
-                    else ap.error(f"--baseline {v}: script, look, deep2, deep3, deep4, terr, play or playPxT"))
+                    or leaf_names.parse(v) is not None
+                    else ap.error(f"--baseline {v}: script, look, deep2, deep3, deep4, terr, play or playPxT, or one of those searches with t or thN behind it"))
     ap.add_argument("--replay", nargs=2, default=None, metavar=("K", "DIR"))
     ap.add_argument("--tally", action="store_true")
     a = ap.parse_args()
     import torch
+    from snake_engine import arena as arena_module
     from snake_engine.arena import Arena, Deep, Lookahead, Playout, Scripted, Searcher, Territory
     from snake_engine.mcts import DeviceMCTS
     from snake_engine.net import glorot_uniform_weights
@@ -147,7 +152,9 @@ def main():
     play(4, 1, (False, False), 8, 99)
     if a.baseline:
         script, who_b = (Lookahead(), "lookahead") if a.baseline == "look" else (Scripted(), "script")
-        if a.baseline.startswith("deep"):
+        if leaf_names.parse(a.baseline) is not None:
+            script, who_b = leaf_names.player(a.baseline, arena_module), a.baseline
+        elif a.baseline.startswith("deep"):
             script, who_b = Deep(depth=int(a.baseline[4])), a.baseline
         if a.baseline == "terr":
             script, who_b = Territory(), "territory"
