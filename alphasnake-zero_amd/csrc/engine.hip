@@ -1783,15 +1783,15 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_pit_territory(const uint8_t *
 // policy is the project's own; include/snake_engine.h states it and tests/look_ref.py restates it in plain Python.  A row (slot g,
 // snake s) of a game with A = 2..4 snakes alive is scored over the 3^A children of its game: copies made by k_clone, stepped once
 // by the step kernels on a sub-engine without food spawning, and scored by k_pit_script -- launched by the entry point through
-// snk_engine_clone, snk_engine_step_active and snk_pit_script_values.  What is new:
+// snk_engine_clone, snk_engine_step_active and snk_pit_script_values.  It is the deep opponent below at depth 1: the entry point,
+// the scratch (DeepScratch) and the fold (k_deep_reduce, level 0 as the parent) are that one's.  What is the lookahead's own:
 //   k_look_count / k_cmp_scan / k_look_groups   the plan's scan over the rows (the three launches of k_pit_roots_*: tile sums, one
 //                                               block scanning them, the scatter): rows of one slot that stand next to each other
 //                                               form a group and share one set of children; per group its source slot and the
 //                                               alive bits of that slot
 //   k_look_fan                                  the plan's fan-out, a thread per child and per leaf: the children's active flags and
-//                                               dense moves, and the leaf pair list (sub slot, s) the script kernel scores
-//   k_look_reduce                               a quad per row, lane a scores own move a: the worst reply over the children in
-//                                               which s's digit is a, or minus the ways to die
+//                                               dense moves, and the leaf pair list (sub slot, s) the script kernel scores --
+//                                               k_deep_fan and k_deep_leaves of a one-level tree in one launch
 // Every cell of every array has one writer, nothing is read back, and there are no atomics.  All per-thread state is scalar: no
 // array is indexed by a run-time value.
 // ------------------------------------------------------------------------------------------
@@ -1799,38 +1799,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_pit_territory(const uint8_t *
 #define LK_WIN 16777216.0f                       // 2^24: above every plain score
 
 __host__ __device__ static inline int look_pow3(int k) { int p = 1; for (int i = 0; i < k; ++i) p *= 3; return p; }
-
-// scratch, in int32 elements from its start; every part starts at a multiple of four elements (16 bytes)
-struct LookScratch {
-    long tile_sums;     // int32[tiles] + the group count
-    long row_group;     // int32[m]       the group of every row
-    long grp_src;       // int32[m]       a group's source slot (a valid slot for every group < n_groups)
-    long grp_bits;      // int32[m]       bit s = snake s of the source slot is alive; 0: the group is not looked ahead
-    long active;        // uint8[m * F]   a child's flag for the step
-    long moves;         // uint8[m * F][S]
-    long leaf_pairs;    // int32[m * F][2]
-    long leaf_q;        // float[m * F][3]
-    long fb_q;          // float[m][3]    the plain scores of the rows themselves
-    long total;
-};
-
-static LookScratch look_scratch(long m, int S, int F)
-{
-    auto up4 = [](long v) { return (v + 3) / 4 * 4; };
-    LookScratch P;
-    long at = 0;
-    P.tile_sums = at;  at += up4((m + PIT_TILE - 1) / PIT_TILE + 1);
-    P.row_group = at;  at += up4(m);
-    P.grp_src = at;    at += up4(m);
-    P.grp_bits = at;   at += up4(m);
-    P.active = at;     at += up4((m * F + 3) / 4);
-    P.moves = at;      at += up4((m * F * S + 3) / 4);
-    P.leaf_pairs = at; at += up4(2 * m * F);
-    P.leaf_q = at;     at += up4(3 * m * F);
-    P.fb_q = at;       at += up4(3 * m);
-    P.total = at;
-    return P;
-}
 
 // row i starts a group when it is row 0 or names another slot than row i - 1
 __device__ static inline bool look_starts(const int32_t *__restrict__ pairs, int i)
@@ -1924,55 +1892,10 @@ __global__ __launch_bounds__(CMP_THREADS) void k_look_fan(int m, int F, int S, i
     }
 }
 
-// a quad of lanes per row, lane a < 3 scores own move a.  A row whose group lies beyond the sub-engine: -1.  A row that is not
-// looked ahead (a dead or out-of-range pair, A < 2, A > 4): its plain score.  Otherwise over the 3^(A-1) children whose digit of
-// s is a: the smallest leaf value when s lives in all of them, else -2 - (the children in which s is dead); a leaf is 2^24 when s
-// alone is left, else the largest of s's three plain scores on the child
-__global__ __launch_bounds__(CMP_THREADS) void k_look_reduce(const uint8_t *__restrict__ sub_state, Layout L, int m, int F, int n_groups,
-                                                            const int32_t *__restrict__ pairs, const int32_t *__restrict__ row_group,
-                                                            const int32_t *__restrict__ grp_bits, const float *__restrict__ leaf_q,
-                                                            const float *__restrict__ fb_q, float *__restrict__ q)
-{
-    const int t = blockIdx.x * CMP_THREADS + threadIdx.x;
-    const int row = t >> 2, a = t & 3;
-    if (row >= m || a >= 3) return;
-    const int s = pairs[2 * (size_t)row + 1], grp = row_group[row];
-    float out = -1.0f;
-    if (grp < n_groups) {
-        const uint32_t bits = (uint32_t)grp_bits[grp];
-        const int A = __popc(bits);
-        const bool look = s >= 0 && s < L.S && ((bits >> s) & 1u) && A >= 2 && A <= 4;
-        if (!look) {
-            out = fb_q[3 * (size_t)row + a];
-        } else {
-            const int p = look_pow3(__popc(bits & ((1u << s) - 1u)));        // the weight of s's digit
-            const int replies = look_pow3(A - 1);
-            const uint32_t others = bits & ~(1u << s);
-            int dead = 0;
-            float worst = LK_WIN;
-            for (int i = 0; i < replies; ++i) {
-                const int hi = i / p, j = hi * 3 * p + a * p + (i - hi * p);
-                const SnakeMeta *meta = (const SnakeMeta *)(sub_state + ((size_t)grp * F + j) * L.stride + L.meta_off);
-                if (!meta[s].alive) { ++dead; continue; }
-                bool alone = true;
-                for (uint32_t b = others; b; b &= b - 1u) alone &= !meta[__ffs((int)b) - 1].alive;
-                float leaf = LK_WIN;
-                if (!alone) {
-                    const float *z = leaf_q + 3 * ((size_t)row * F + j);
-                    leaf = fmaxf(z[0], fmaxf(z[1], z[2]));
-                }
-                worst = fminf(worst, leaf);
-            }
-            out = dead ? (float)(-2 - dead) : worst;
-        }
-    }
-    q[3 * (size_t)row + a] = out;
-}
-
 // ------------------------------------------------------------------------------------------
 // the deep opponent of the pit (snake_engine.arena.Deep, snk_pit_deep_values): the scripted policy `depth` ticks deep, a paranoid
 // fixed-depth search over the lookahead's children.  include/snake_engine.h states the policy, tests/deep_ref.py restates it in
-// plain Python.  Depth 1 IS snk_pit_look_values (the entry point calls it).  From depth 2 on the rows are grouped by the
+// plain Python.  Depth 1 IS snk_pit_look_values (that entry point runs this body with one level).  The rows are grouped by the
 // lookahead's scan (k_look_count / k_cmp_scan / k_look_groups), and the tree of a group stands in one sub-engine per level:
 // node c of level k (slot c of subs[k-1]) is child c % F of node c / F of level k - 1; level 0 is the group's game.  What is new:
 //   k_deep_fan      a thread per node of a level, after the level above has been stepped: the node is active when its parent is
@@ -1989,9 +1912,13 @@ __global__ __launch_bounds__(CMP_THREADS) void k_look_reduce(const uint8_t *__re
 #define DP_MAX_DEPTH 4
 #define DP_MAX_FANOUT 6561                       // F^depth: 3^8
 
+// scratch, in int32 elements from its start; every part starts at a multiple of four elements (16 bytes)
 struct DeepScratch {
-    long tile_sums, row_group, grp_src, grp_bits;     // as LookScratch
-    long fb_q;                      // float[m][3]          the plain scores of the rows themselves
+    long tile_sums;                 // int32[tiles] + the group count
+    long row_group;                 // int32[m]             the group of every row
+    long grp_src;                   // int32[m]             a group's source slot (a valid slot for every group < n_groups)
+    long grp_bits;                  // int32[m]             bit s = snake s of the source slot is alive; 0: the group is not searched
+    long fb_q;                     // float[m][3]          the plain scores of the rows themselves
     long active[DP_MAX_DEPTH];      // uint8[m * F^k]       level k's flags for the step
     long moves[DP_MAX_DEPTH];       // uint8[m * F^k][S]
     long best[DP_MAX_DEPTH];        // float[m * F^k]       per (row, node of level k < depth): the best of s's three scores there
@@ -2020,7 +1947,6 @@ static DeepScratch deep_scratch(long m, int S, int F, int depth)
     P.leaf_pairs = at; at += up4(2 * n);
     P.leaf_q = at;     at += up4(3 * n);
     P.total = at;
-    if (depth == 1) { const long look = look_scratch(m, S, F).total; if (look > P.total) P.total = look; }
     return P;
 }
 
@@ -2557,6 +2483,14 @@ static bool supported_board(int H, int W) { return H == W && H >= 5 && H * W <= 
         else { constexpr int BH = -1, BW = -1; CALL; }                          \
     } while (0)
 
+// the same for the kernels templated on the 64-bit words of a board plane (Layout::FW): k_pit_script, k_pit_territory
+#define DISPATCH_FW(L, CALL)                                                    \
+    do {                                                                        \
+        if ((L).FW == 1) { constexpr int FW = 1; CALL; }                        \
+        else if ((L).FW == 2) { constexpr int FW = 2; CALL; }                   \
+        else { constexpr int FW = 6; CALL; }                                    \
+    } while (0)
+
 extern "C" int snk_engine_create(snk_engine **out, int n_slots, int H, int W, int S, int health_dec,
                                  double food_spawn_chance, uint64_t seed, int device)
 {
@@ -2833,22 +2767,47 @@ extern "C" int snk_pit_roots_owned(const snk_engine *e, const uint8_t *d_live, i
     return 0;
 }
 
+// the refusals every scripted entry point `fn` shares, in their order: the engine (`engines`: every engine pointer of the call is
+// there), the flags, hungry (0..100; 100 where the entry point has none) and m
+static int pit_args_ok(const char *fn, bool engines, uint32_t flags, int hungry, int m)
+{
+    SNK_REQUIRE(engines, "%s: engine is NULL", fn);
+    SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u, "%s: unknown flag bits in 0x%x", fn,
+                flags);
+    SNK_REQUIRE(hungry >= 0 && hungry <= 100, "%s: hungry=%d outside 0..100", fn, hungry);
+    SNK_REQUIRE(m >= 0, "%s: m=%d", fn, m);
+    return 0;
+}
+
+// the refusals of one sub-engine of e: there, not e, e's geometry, device and health_dec, no food.  k >= 0: level k of a tree,
+// "sub-engine k" in the messages; k < 0: the only one, "the sub-engine"
+static int pit_sub_ok(const char *fn, const snk_engine *e, const snk_engine *sub, int k)
+{
+    char who[32] = "the sub-engine", of[32] = "", both[48] = "the engines";
+    if (k >= 0) {
+        snprintf(who, sizeof(who), "sub-engine %d", k);
+        snprintf(of, sizeof(of), " of %s", who);
+        snprintf(both, sizeof(both), "the engine and %s", who);
+    }
+    SNK_REQUIRE(sub != nullptr, "%s: %s is NULL", fn, who);
+    SNK_REQUIRE(sub != e, "%s: %s is the engine itself", fn, who);
+    SNK_REQUIRE(e->L.H == sub->L.H && e->L.W == sub->L.W && e->L.S == sub->L.S, "%s: geometry mismatch%s", fn, of);
+    SNK_REQUIRE(e->device == sub->device, "%s: %s are on devices %d and %d", fn, both, e->device, sub->device);
+    SNK_REQUIRE(sub->food_chance == 0.0 && sub->health_dec == e->health_dec,
+                "%s: %s must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)", fn, who, sub->food_chance,
+                e->health_dec, sub->health_dec);
+    return 0;
+}
+
 extern "C" int snk_pit_script_values(const snk_engine *e, const int32_t *d_pairs, int m, uint32_t flags, float *d_q, void *stream)
 {
-    SNK_REQUIRE(e != nullptr, "snk_pit_script_values: engine is NULL");
-    SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
-                "snk_pit_script_values: unknown flag bits in 0x%x", flags);
-    SNK_REQUIRE(m >= 0, "snk_pit_script_values: m=%d", m);
+    if (pit_args_ok("snk_pit_script_values", e != nullptr, flags, 100, m)) return -1;
     if (m == 0) return 0;
     SNK_REQUIRE(d_pairs && d_q, "snk_pit_script_values: NULL argument");
     const Layout L = e->L;
     const ScriptMasks K = script_masks(L);
     const int grid = (m + BLOCK_THREADS / 4 - 1) / (BLOCK_THREADS / 4);      // a quad per row
-#define SCRIPT_ARGS e->d_state, L, e->n_slots, d_pairs, m, flags, K, d_q
-    if (L.FW == 1) k_pit_script<1><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
-    else if (L.FW == 2) k_pit_script<2><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
-    else k_pit_script<6><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(SCRIPT_ARGS);
-#undef SCRIPT_ARGS
+    DISPATCH_FW(L, (k_pit_script<FW><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(e->d_state, L, e->n_slots, d_pairs, m, flags, K, d_q)));
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -2856,21 +2815,14 @@ extern "C" int snk_pit_script_values(const snk_engine *e, const int32_t *d_pairs
 extern "C" int snk_pit_territory_values(const snk_engine *e, const int32_t *d_pairs, int m, uint32_t flags, int hungry, float *d_q,
                                         void *stream)
 {
-    SNK_REQUIRE(e != nullptr, "snk_pit_territory_values: engine is NULL");
-    SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
-                "snk_pit_territory_values: unknown flag bits in 0x%x", flags);
-    SNK_REQUIRE(hungry >= 0 && hungry <= 100, "snk_pit_territory_values: hungry=%d outside 0..100", hungry);
-    SNK_REQUIRE(m >= 0, "snk_pit_territory_values: m=%d", m);
+    if (pit_args_ok("snk_pit_territory_values", e != nullptr, flags, hungry, m)) return -1;
     if (m == 0) return 0;
     SNK_REQUIRE(d_pairs && d_q, "snk_pit_territory_values: NULL argument");
     const Layout L = e->L;
     const ScriptMasks K = script_masks(L);
     const int grid = (m + BLOCK_THREADS / 4 - 1) / (BLOCK_THREADS / 4);      // a quad per row
-#define TERRITORY_ARGS e->d_state, L, e->n_slots, d_pairs, m, flags, hungry, K, d_q
-    if (L.FW == 1) k_pit_territory<1><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(TERRITORY_ARGS);
-    else if (L.FW == 2) k_pit_territory<2><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(TERRITORY_ARGS);
-    else k_pit_territory<6><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(TERRITORY_ARGS);
-#undef TERRITORY_ARGS
+    DISPATCH_FW(L, (k_pit_territory<FW><<<grid, BLOCK_THREADS, 0, (hipStream_t)stream>>>(e->d_state, L, e->n_slots, d_pairs, m, flags,
+                                                                                         hungry, K, d_q)));
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -2897,69 +2849,6 @@ extern "C" int snk_pit_look_fanout(int S)
     return look_pow3(S < 4 ? S : 4);
 }
 
-extern "C" long snk_pit_look_scratch_elems(int m, int S)
-{
-    const int F = snk_pit_look_fanout(S);
-    if (m < 0 || F < 0 || (long long)m * F > LK_MAX_LEAVES) return -1;
-    return look_scratch(m, S, F).total;
-}
-
-extern "C" int snk_pit_look_values_leaf(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int leaf,
-                                        int hungry, int32_t *d_scratch, float *d_q, void *stream)
-{
-    SNK_REQUIRE(leaf_ok(leaf, hungry), LEAF_REFUSAL, "snk_pit_look_values_leaf", leaf, hungry);
-    SNK_REQUIRE(e != nullptr && sub != nullptr, "snk_pit_look_values_leaf: engine is NULL");
-    SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
-                "snk_pit_look_values_leaf: unknown flag bits in 0x%x", flags);
-    SNK_REQUIRE(m >= 0, "snk_pit_look_values_leaf: m=%d", m);
-    SNK_REQUIRE(sub != e, "snk_pit_look_values_leaf: the sub-engine is the engine itself");
-    SNK_REQUIRE(e->L.H == sub->L.H && e->L.W == sub->L.W && e->L.S == sub->L.S, "snk_pit_look_values_leaf: geometry mismatch");
-    SNK_REQUIRE(e->device == sub->device, "snk_pit_look_values_leaf: the engines are on devices %d and %d", e->device, sub->device);
-    SNK_REQUIRE(sub->food_chance == 0.0 && sub->health_dec == e->health_dec,
-                "snk_pit_look_values_leaf: the sub-engine must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)",
-                sub->food_chance, e->health_dec, sub->health_dec);
-    if (m == 0) return 0;
-    SNK_REQUIRE(d_pairs && d_scratch && d_q, "snk_pit_look_values_leaf: NULL argument");
-    const Layout L = e->L;
-    const int F = snk_pit_look_fanout(L.S);
-    SNK_REQUIRE((long long)m * F <= LK_MAX_LEAVES, "snk_pit_look_values_leaf: m=%d rows of fanout %d exceed %d leaves", m, F, LK_MAX_LEAVES);
-    const int need = m < e->n_slots ? m : e->n_slots;
-    SNK_REQUIRE((long long)need * F <= sub->n_slots, "snk_pit_look_values_leaf: %d groups of fanout %d exceed the sub-engine's %d slots", need,
-                F, sub->n_slots);
-    const int n_groups = m < sub->n_slots / F ? m : sub->n_slots / F;
-    const LookScratch P = look_scratch(m, L.S, F);
-    int32_t *tile_sums = d_scratch + P.tile_sums, *row_group = d_scratch + P.row_group;
-    int32_t *grp_src = d_scratch + P.grp_src, *grp_bits = d_scratch + P.grp_bits, *leaf_pairs = d_scratch + P.leaf_pairs;
-    uint8_t *active = (uint8_t *)(d_scratch + P.active), *moves = (uint8_t *)(d_scratch + P.moves);
-    float *leaf_q = (float *)(d_scratch + P.leaf_q), *fb_q = (float *)(d_scratch + P.fb_q);
-    hipStream_t st = (hipStream_t)stream;
-    const int tiles = (m + PIT_TILE - 1) / PIT_TILE;
-    int32_t *count = tile_sums + tiles;
-    k_look_count<<<tiles, CMP_THREADS, 0, st>>>(d_pairs, m, tile_sums);
-    k_cmp_scan<<<1, CMP_THREADS, 0, st>>>(tile_sums, tiles, count);
-    k_look_groups<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, L, e->n_slots, d_pairs, m, tile_sums, count, n_groups, row_group, grp_src,
-                                                grp_bits);
-    k_look_fan<<<(m * F + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(m, F, L.S, n_groups, d_pairs, row_group, grp_bits, active,
-                                                                           moves, leaf_pairs);
-    SNK_CHECK_HIP(hipGetLastError());
-    // the children: Game.subgame of every group's slot F times, one tick of the active ones, s's plain scores on each
-    int rc = snk_engine_clone(e, grp_src, n_groups, sub, nullptr, F, stream);
-    if (rc == 0) rc = snk_engine_step_active(sub, active, n_groups * F, moves, nullptr, nullptr, stream);
-    if (rc == 0) rc = leaf_values(sub, leaf_pairs, m * F, flags, leaf, hungry, leaf_q, stream);
-    if (rc == 0) rc = leaf_values(e, d_pairs, m, flags, leaf, hungry, fb_q, stream);
-    if (rc != 0) return rc;
-    k_look_reduce<<<(4 * m + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(sub->d_state, L, m, F, n_groups, d_pairs, row_group,
-                                                                              grp_bits, leaf_q, fb_q, d_q);
-    SNK_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-extern "C" int snk_pit_look_values(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags,
-                                   int32_t *d_scratch, float *d_q, void *stream)
-{
-    return snk_pit_look_values_leaf(e, sub, d_pairs, m, flags, SNK_LEAF_SCRIPT, 100, d_scratch, d_q, stream);
-}
-
 extern "C" int snk_pit_deep_fanout(int S, int depth)
 {
     const int F = snk_pit_look_fanout(S);
@@ -2976,45 +2865,43 @@ extern "C" long snk_pit_deep_scratch_elems(int m, int S, int depth)
     return deep_scratch(m, S, snk_pit_look_fanout(S), depth).total;
 }
 
-extern "C" int snk_pit_deep_values_leaf(const snk_engine *e, snk_engine *const *subs, int depth, const int32_t *d_pairs, int m,
-                                        uint32_t flags, int leaf, int hungry, int32_t *d_scratch, float *d_q, void *stream)
+extern "C" long snk_pit_look_scratch_elems(int m, int S) { return snk_pit_deep_scratch_elems(m, S, 1); }
+
+// the body of the lookahead (depth 1, one sub-engine) and the deep search, under the name `fn` of the entry point called.  The
+// launches of a call, in their order (clone and step through snk_engine_clone and snk_engine_step_active, `leaf` the script or the
+// territory kernel through leaf_values):
+//   depth 1        k_look_count, k_cmp_scan, k_look_groups, k_look_fan, clone, step, leaf over the m * F leaves, leaf over the m
+//                  rows themselves (the fallback), k_deep_reduce
+//   depth D >= 2   k_look_count, k_cmp_scan, k_look_groups, leaf over the m rows themselves, D x (k_deep_fan, clone, step),
+//                  k_deep_leaves, leaf over the m * F^D leaves, D x k_deep_reduce
+// At depth 1 k_look_fan stands for k_deep_fan and k_deep_leaves: the leaf list of a one-level tree needs no stepped level above.
+static int search_values(const char *fn, const snk_engine *e, snk_engine *const *subs, int depth, const int32_t *d_pairs, int m,
+                         uint32_t flags, int leaf, int hungry, int32_t *d_scratch, float *d_q, void *stream)
 {
-    SNK_REQUIRE(leaf_ok(leaf, hungry), LEAF_REFUSAL, "snk_pit_deep_values_leaf", leaf, hungry);
-    SNK_REQUIRE(e != nullptr && subs != nullptr, "snk_pit_deep_values_leaf: engine is NULL");
-    SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
-                "snk_pit_deep_values_leaf: unknown flag bits in 0x%x", flags);
-    SNK_REQUIRE(m >= 0, "snk_pit_deep_values_leaf: m=%d", m);
+    SNK_REQUIRE(leaf_ok(leaf, hungry), LEAF_REFUSAL, fn, leaf, hungry);
+    if (pit_args_ok(fn, e != nullptr && subs != nullptr, flags, hungry, m)) return -1;
     const Layout L = e->L;
     const int F = snk_pit_look_fanout(L.S), FD = snk_pit_deep_fanout(L.S, depth);
-    SNK_REQUIRE(FD > 0, "snk_pit_deep_values_leaf: depth %d with %d snakes (fanout %d) is outside 1 .. the depth at which it reaches %d", depth,
-                L.S, F, DP_MAX_FANOUT);
+    SNK_REQUIRE(FD > 0, "%s: depth %d with %d snakes (fanout %d) is outside 1 .. the depth at which it reaches %d", fn, depth, L.S, F,
+                DP_MAX_FANOUT);
     for (int k = 0; k < depth; ++k) {
-        const snk_engine *sub = subs[k];
-        SNK_REQUIRE(sub != nullptr, "snk_pit_deep_values_leaf: sub-engine %d is NULL", k);
-        SNK_REQUIRE(sub != e, "snk_pit_deep_values_leaf: sub-engine %d is the engine itself", k);
-        for (int o = 0; o < k; ++o) SNK_REQUIRE(sub != subs[o], "snk_pit_deep_values_leaf: sub-engines %d and %d are the same", o, k);
-        SNK_REQUIRE(L.H == sub->L.H && L.W == sub->L.W && L.S == sub->L.S, "snk_pit_deep_values_leaf: geometry mismatch of sub-engine %d", k);
-        SNK_REQUIRE(e->device == sub->device, "snk_pit_deep_values_leaf: the engine and sub-engine %d are on devices %d and %d", k, e->device,
-                    sub->device);
-        SNK_REQUIRE(sub->food_chance == 0.0 && sub->health_dec == e->health_dec,
-                    "snk_pit_deep_values_leaf: sub-engine %d must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)", k,
-                    sub->food_chance, e->health_dec, sub->health_dec);
+        if (pit_sub_ok(fn, e, subs[k], k)) return -1;
+        for (int o = 0; o < k; ++o) SNK_REQUIRE(subs[k] != subs[o], "%s: sub-engines %d and %d are the same", fn, o, k);
     }
     if (m == 0) return 0;
-    SNK_REQUIRE(d_pairs && d_scratch && d_q, "snk_pit_deep_values_leaf: NULL argument");
-    SNK_REQUIRE((long long)m * FD <= LK_MAX_LEAVES, "snk_pit_deep_values_leaf: m=%d rows of fanout %d exceed %d leaves", m, FD, LK_MAX_LEAVES);
+    SNK_REQUIRE(d_pairs && d_scratch && d_q, "%s: NULL argument", fn);
+    SNK_REQUIRE((long long)m * FD <= LK_MAX_LEAVES, "%s: m=%d rows of fanout %d exceed %d leaves", fn, m, FD, LK_MAX_LEAVES);
     const int need = m < e->n_slots ? m : e->n_slots;
     int n_groups = m;                                     // the groups every level can hold
     {
         long long pw = 1;
         for (int k = 0; k < depth; ++k) {
             pw *= F;
-            SNK_REQUIRE(need * pw <= subs[k]->n_slots, "snk_pit_deep_values_leaf: %d groups of fanout %lld exceed sub-engine %d's %d slots", need,
-                        pw, k, subs[k]->n_slots);
+            SNK_REQUIRE(need * pw <= subs[k]->n_slots, "%s: %d groups of fanout %lld exceed sub-engine %d's %d slots", fn, need, pw, k,
+                        subs[k]->n_slots);
             if (subs[k]->n_slots / pw < n_groups) n_groups = (int)(subs[k]->n_slots / pw);
         }
     }
-    if (depth == 1) return snk_pit_look_values_leaf(e, subs[0], d_pairs, m, flags, leaf, hungry, d_scratch, d_q, stream);
     const DeepScratch P = deep_scratch(m, L.S, F, depth);
     int32_t *tile_sums = d_scratch + P.tile_sums, *row_group = d_scratch + P.row_group;
     int32_t *grp_src = d_scratch + P.grp_src, *grp_bits = d_scratch + P.grp_bits, *leaf_pairs = d_scratch + P.leaf_pairs;
@@ -3027,15 +2914,19 @@ extern "C" int snk_pit_deep_values_leaf(const snk_engine *e, snk_engine *const *
     k_look_groups<<<tiles, CMP_THREADS, 0, st>>>(e->d_state, L, e->n_slots, d_pairs, m, tile_sums, count, n_groups, row_group, grp_src,
                                                 grp_bits);
     SNK_CHECK_HIP(hipGetLastError());
-    int rc = leaf_values(e, d_pairs, m, flags, leaf, hungry, fb_q, stream);
+    int rc = depth > 1 ? leaf_values(e, d_pairs, m, flags, leaf, hungry, fb_q, stream) : 0;
     // level by level: the nodes' flags and moves from the stepped level above, Game.subgame of every node above F times, one tick
     int nodes = n_groups;                                 // of the level above
     for (int k = 0; k < depth && rc == 0; ++k) {
         uint8_t *active = (uint8_t *)(d_scratch + P.active[k]), *moves = (uint8_t *)(d_scratch + P.moves[k]);
         const snk_engine *par = k ? subs[k - 1] : nullptr;
-        k_deep_fan<<<(nodes * F + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(
-            nodes * F, F, grp_bits, par ? par->d_state : nullptr, L, par ? par->n_slots : 0,
-            k ? (const uint8_t *)(d_scratch + P.active[k - 1]) : nullptr, active, moves);
+        if (depth == 1)
+            k_look_fan<<<(m * F + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(m, F, L.S, n_groups, d_pairs, row_group, grp_bits,
+                                                                                   active, moves, leaf_pairs);
+        else
+            k_deep_fan<<<(nodes * F + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(
+                nodes * F, F, grp_bits, par ? par->d_state : nullptr, L, par ? par->n_slots : 0,
+                k ? (const uint8_t *)(d_scratch + P.active[k - 1]) : nullptr, active, moves);
         SNK_CHECK_HIP(hipGetLastError());
         rc = k ? snk_engine_clone(par, nullptr, nodes, subs[k], nullptr, F, stream)
                : snk_engine_clone(e, grp_src, nodes, subs[k], nullptr, F, stream);
@@ -3043,11 +2934,13 @@ extern "C" int snk_pit_deep_values_leaf(const snk_engine *e, snk_engine *const *
         if (rc == 0) rc = snk_engine_step_active(subs[k], active, nodes, moves, nullptr, nullptr, stream);
     }
     if (rc != 0) return rc;
-    k_deep_leaves<<<(m * FD + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(
-        m, FD, L.S, n_groups, subs[depth - 1]->n_slots, d_pairs, row_group, grp_bits, (const uint8_t *)(d_scratch + P.active[depth - 1]),
-        leaf_pairs);
+    if (depth > 1)
+        k_deep_leaves<<<(m * FD + CMP_THREADS - 1) / CMP_THREADS, CMP_THREADS, 0, st>>>(
+            m, FD, L.S, n_groups, subs[depth - 1]->n_slots, d_pairs, row_group, grp_bits,
+            (const uint8_t *)(d_scratch + P.active[depth - 1]), leaf_pairs);
     SNK_CHECK_HIP(hipGetLastError());
     rc = leaf_values(subs[depth - 1], leaf_pairs, m * FD, flags, leaf, hungry, leaf_q, stream);
+    if (rc == 0 && depth == 1) rc = leaf_values(e, d_pairs, m, flags, leaf, hungry, fb_q, stream);
     if (rc != 0) return rc;
     // the fold, from the last level up: level k + 1 (subs[k]) into level k
     int per = FD / F;                                     // parents per row: F^k
@@ -3061,6 +2954,24 @@ extern "C" int snk_pit_deep_values_leaf(const snk_engine *e, snk_engine *const *
     }
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int snk_pit_look_values_leaf(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags, int leaf,
+                                        int hungry, int32_t *d_scratch, float *d_q, void *stream)
+{
+    return search_values("snk_pit_look_values_leaf", e, sub ? &sub : nullptr, 1, d_pairs, m, flags, leaf, hungry, d_scratch, d_q, stream);
+}
+
+extern "C" int snk_pit_look_values(const snk_engine *e, snk_engine *sub, const int32_t *d_pairs, int m, uint32_t flags,
+                                   int32_t *d_scratch, float *d_q, void *stream)
+{
+    return snk_pit_look_values_leaf(e, sub, d_pairs, m, flags, SNK_LEAF_SCRIPT, 100, d_scratch, d_q, stream);
+}
+
+extern "C" int snk_pit_deep_values_leaf(const snk_engine *e, snk_engine *const *subs, int depth, const int32_t *d_pairs, int m,
+                                        uint32_t flags, int leaf, int hungry, int32_t *d_scratch, float *d_q, void *stream)
+{
+    return search_values("snk_pit_deep_values_leaf", e, subs, depth, d_pairs, m, flags, leaf, hungry, d_scratch, d_q, stream);
 }
 
 extern "C" int snk_pit_deep_values(const snk_engine *e, snk_engine *const *subs, int depth, const int32_t *d_pairs, int m,
@@ -3082,19 +2993,11 @@ extern "C" int snk_pit_playout_values_leaf(const snk_engine *e, snk_engine *sub,
                                            void *stream)
 {
     SNK_REQUIRE(leaf_ok(leaf, hungry), LEAF_REFUSAL, "snk_pit_playout_values_leaf", leaf, hungry);
-    SNK_REQUIRE(e != nullptr && sub != nullptr, "snk_pit_playout_values_leaf: engine is NULL");
-    SNK_REQUIRE((flags & ~(uint32_t)(SNK_SCRIPT_SPACE | SNK_SCRIPT_HEADS | SNK_SCRIPT_FOOD)) == 0u,
-                "snk_pit_playout_values_leaf: unknown flag bits in 0x%x", flags);
-    SNK_REQUIRE(m >= 0, "snk_pit_playout_values_leaf: m=%d", m);
+    if (pit_args_ok("snk_pit_playout_values_leaf", e != nullptr && sub != nullptr, flags, hungry, m)) return -1;
     SNK_REQUIRE(P >= 1 && P <= PL_MAX_PLAYOUTS, "snk_pit_playout_values_leaf: playouts P=%d outside 1..%d", P, PL_MAX_PLAYOUTS);
     SNK_REQUIRE(T >= 1 && T <= PL_MAX_HORIZON, "snk_pit_playout_values_leaf: horizon T=%d outside 1..%d", T, PL_MAX_HORIZON);
     SNK_REQUIRE(eps >= 0 && eps <= PL_MAX_EXPLORE, "snk_pit_playout_values_leaf: explore eps=%d outside 0..%d", eps, PL_MAX_EXPLORE);
-    SNK_REQUIRE(sub != e, "snk_pit_playout_values_leaf: the sub-engine is the engine itself");
-    SNK_REQUIRE(e->L.H == sub->L.H && e->L.W == sub->L.W && e->L.S == sub->L.S, "snk_pit_playout_values_leaf: geometry mismatch");
-    SNK_REQUIRE(e->device == sub->device, "snk_pit_playout_values_leaf: the engines are on devices %d and %d", e->device, sub->device);
-    SNK_REQUIRE(sub->food_chance == 0.0 && sub->health_dec == e->health_dec,
-                "snk_pit_playout_values_leaf: the sub-engine must spawn no food (chance %g) and have the engine's health_dec (%d, not %d)",
-                sub->food_chance, e->health_dec, sub->health_dec);
+    if (pit_sub_ok("snk_pit_playout_values_leaf", e, sub, -1)) return -1;
     const Layout L = e->L;
     SNK_REQUIRE((long long)m * 3 * P * L.S <= LK_MAX_LEAVES, "snk_pit_playout_values_leaf: m=%d rows of %d clones and %d snakes exceed %d", m,
                 3 * P, L.S, LK_MAX_LEAVES);

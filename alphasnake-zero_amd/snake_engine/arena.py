@@ -201,132 +201,127 @@ def checked_leaf(leaf, flags):
     return leaf if type(leaf) is Territory else None
 
 
+class _Search(Scripted):
+    """What Lookahead, Deep and Playout share: the leaf, the sub-engines without food spawning and the scratch a player owns, and
+    the chunks of q_rows.  _subs holds one sub-engine per level (one level for Lookahead and Playout: _sub), _handles their
+    snk_engine * as an array on the host, _scratch int32 on the device.  They are made at first use; all levels are remade, and
+    the replaced ones closed, when the geometry, health_dec or the device changes or level 1 is too small; the scratch only grows."""
+
+    def __init__(self, flags, leaf):
+        super().__init__(flags)
+        self.leaf = checked_leaf(leaf, self.flags)
+        self._subs = self._handles = self._scratch = None
+
+    @property
+    def _sub(self):
+        return self._subs[0] if self._subs else None
+
+    def _buffers(self, engine, slots, elems):
+        """sub-engines of at least slots[k] slots at level k + 1, the array of their handles and a scratch of at least elems elements"""
+        top = self._sub
+        key = (engine.H, engine.W, engine.S, engine.health_dec, engine.device)
+        if top is not None and (top.H, top.W, top.S, top.health_dec, top.device) != key:
+            top = self._scratch = None
+        if top is None or top.n_slots < slots[0]:
+            for sub in self._subs or ():
+                sub.close()
+            self._subs = [Engine(n, engine.H, engine.W, engine.S, engine.health_dec, 0, seed=0, device=engine.device.index) for n in slots]
+            self._handles = torch.tensor([sub.h.value for sub in self._subs], dtype=torch.int64)       # snk_engine *[levels], on the host
+        if self._scratch is None or self._scratch.numel() < elems:
+            self._scratch = engine.new((elems,), torch.int32)
+        return self._subs, self._handles, self._scratch
+
+    def _chunks(self, engine, pairs, name, per, need, head, tail=()):
+        """q_rows in calls of at most `per` rows.  need(rows) -> the slots per level and the scratch elements of a call of that many
+        rows; head(subs, handles) -> the arguments between the engine and the pair list; tail: those between the leaf and the
+        scratch.  Without a leaf the call is the entry point `name` with its plain argument list, with one it is name_leaf with
+        LEAF_TERRITORY and the leaf's hungry after the flags"""
+        m = int(pairs.shape[0])
+        q = engine.new((m, 3), torch.float32)
+        leaf = () if self.leaf is None else (LEAF_TERRITORY, self.leaf.hungry)
+        call = getattr(engine.L, name + "_leaf" if leaf else name)
+        for lo in range(0, m, per):
+            cnt = min(per, m - lo)
+            subs, handles, scratch = self._buffers(engine, *need(cnt))
+            check(call(engine.h, *head(subs, handles), _ptr(pairs[lo:lo + cnt]), cnt, self.flags, *leaf, *tail, _ptr(scratch),
+                       _ptr(q[lo:lo + cnt]), _stream()))
+        return q
+
+    @staticmethod
+    def _one(subs, handles):
+        return (subs[0].h,)
+
+
 LOOK_SLOT_BUDGET = 4096 * 4 * 81    # rows times fanout of one snk_pit_look_values call: a 4 096-game 11x11x4 match, every seat
 
 
-class Lookahead(Scripted):
+class Lookahead(_Search):
     """The scripted policy one tick deep (include/snake_engine.h states it): every joint move of the up to four snakes alive is
     played on a copy of the game, the copies are scored by the plain script, and a move scores what the worst reply leaves --
     or, when a reply can kill, minus the number of ways to die.  The same flags and refusals as Scripted, and it sits wherever a
     Scripted can (mixed_values asks isinstance(side, Scripted)); a Searcher around it is a TypeError.  It owns a sub-engine
-    without food spawning for the copies and the scratch of snk_pit_look_values, made at first use, remade when the geometry or
-    the device changes, and grown when more rows arrive; the sub-engine holds min(rows, games) * fanout slots and a call takes
-    at most LOOK_SLOT_BUDGET // fanout rows, so it never exceeds LOOK_SLOT_BUDGET slots.  leaf=Territory(flags, hungry) -- the
-    player's own flags -- scores the copies and the fallback rows by territory instead (snk_pit_look_values_leaf); .leaf keeps it."""
+    without food spawning for the copies and the scratch of snk_pit_look_values (_Search keeps them); the sub-engine holds
+    min(rows, games) * fanout slots and a call takes at most LOOK_SLOT_BUDGET // fanout rows, so it never exceeds
+    LOOK_SLOT_BUDGET slots.  leaf=Territory(flags, hungry) -- the player's own flags -- scores the copies and the fallback rows by
+    territory instead (snk_pit_look_values_leaf); .leaf keeps it."""
 
     def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD, leaf=None):
-        super().__init__(flags)
-        self.leaf = checked_leaf(leaf, self.flags)
-        self._sub = self._scratch = None
-
-    def _buffers(self, engine, rows, F):
-        """the sub-engine and the scratch for a call of `rows` rows"""
-        sub = self._sub
-        key = (engine.H, engine.W, engine.S, engine.health_dec, engine.device)
-        if sub is None or (sub.H, sub.W, sub.S, sub.health_dec, sub.device) != key:
-            sub = self._scratch = None
-        slots = min(rows, engine.n_slots) * F
-        if sub is None or sub.n_slots < slots:
-            if sub is not None:
-                sub.close()
-            sub = Engine(slots, engine.H, engine.W, engine.S, engine.health_dec, 0, seed=0, device=engine.device.index)
-        elems = engine.L.snk_pit_look_scratch_elems(rows, engine.S)
-        if elems < 0:
-            raise EngineError(f"no lookahead scratch for {rows} rows of {engine.S} snakes")
-        if self._scratch is None or self._scratch.numel() < elems:
-            self._scratch = engine.new((elems,), torch.int32)
-        self._sub = sub
-        return sub, self._scratch
+        super().__init__(flags, leaf)
 
     def q_rows(self, engine, pairs):
         """pairs int32[rows][2] (slot, snake id) on the device -> the three move scores float32[rows][3] on the device"""
-        m = int(pairs.shape[0])
-        q = engine.new((m, 3), torch.float32)
         F = engine.L.snk_pit_look_fanout(engine.S)
-        per = max(LOOK_SLOT_BUDGET // F, 1)           # a boundary inside a game is harmless: the game is cloned again
-        for lo in range(0, m, per):
-            cnt = min(per, m - lo)
-            sub, scratch = self._buffers(engine, cnt, F)
-            if self.leaf is None:
-                check(engine.L.snk_pit_look_values(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, _ptr(scratch),
-                                                   _ptr(q[lo:lo + cnt]), _stream()))
-            else:
-                check(engine.L.snk_pit_look_values_leaf(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, LEAF_TERRITORY,
-                                                        self.leaf.hungry, _ptr(scratch), _ptr(q[lo:lo + cnt]), _stream()))
-        return q
+
+        def need(rows):
+            elems = engine.L.snk_pit_look_scratch_elems(rows, engine.S)
+            if elems < 0:
+                raise EngineError(f"no lookahead scratch for {rows} rows of {engine.S} snakes")
+            return [min(rows, engine.n_slots) * F], elems
+        # a boundary inside a game is harmless: the game is cloned again
+        return self._chunks(engine, pairs, "snk_pit_look_values", max(LOOK_SLOT_BUDGET // F, 1), need, self._one)
 
 
 DEEP_BYTE_BUDGET = 1 << 30           # bytes of records in the sub-engines of one snk_pit_deep_values call, all levels together
 
 
-class Deep(Scripted):
+class Deep(_Search):
     """The scripted policy `depth` ticks deep (include/snake_engine.h states it): a fixed-depth paranoid search over the
     lookahead's children.  A move scores what the worst replies of the next `depth` ticks leave; a move that can be punished now
     ranks below every move that can only be punished later.  Deep(depth=1) is Lookahead bit for bit.  The same flags and refusals
     as Scripted, and it sits wherever a Scripted can; a Searcher around it is a TypeError.  It owns `depth` sub-engines without
-    food spawning (level k holds min(rows, games) * fanout^k slots) and the scratch of snk_pit_deep_values, made at first use,
-    remade when the geometry or the device changes, and grown when more rows arrive.  A call takes as many rows as keep the
-    sub-engines' records within DEEP_BYTE_BUDGET bytes, at least one; a depth the board's snake count cannot have
-    (snk_pit_deep_fanout) is refused at first use.  leaf=Territory(flags, hungry) as for Lookahead (snk_pit_deep_values_leaf)."""
+    food spawning (level k holds min(rows, games) * fanout^k slots) and the scratch of snk_pit_deep_values (_Search keeps them).
+    A call takes as many rows as keep the sub-engines' records within DEEP_BYTE_BUDGET bytes, at least one; a depth the board's
+    snake count cannot have (snk_pit_deep_fanout) is refused at first use.  leaf=Territory(flags, hungry) as for Lookahead
+    (snk_pit_deep_values_leaf)."""
 
     def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD, depth=2, leaf=None):
-        super().__init__(flags)
-        self.leaf = checked_leaf(leaf, self.flags)
+        super().__init__(flags, leaf)
         depth = int(depth)
         if depth < 1:
             raise ValueError(f"Deep depth {depth}: at least 1")
         self.depth = depth
-        self._subs = self._scratch = self._handles = None
-
-    def _buffers(self, engine, rows, F):
-        """the sub-engines, the array of their handles and the scratch for a call of `rows` rows"""
-        subs = self._subs
-        key = (engine.H, engine.W, engine.S, engine.health_dec, engine.device)
-        if subs is not None and (subs[0].H, subs[0].W, subs[0].S, subs[0].health_dec, subs[0].device) != key:
-            for sub in subs:
-                sub.close()
-            subs = self._scratch = None
-        groups = min(rows, engine.n_slots)
-        if subs is None or subs[0].n_slots < groups * F:
-            for sub in subs or ():
-                sub.close()
-            subs = [Engine(groups * F ** k, engine.H, engine.W, engine.S, engine.health_dec, 0, seed=0, device=engine.device.index)
-                    for k in range(1, self.depth + 1)]
-            self._handles = torch.tensor([sub.h.value for sub in subs], dtype=torch.int64)       # snk_engine *[depth], on the host
-        elems = engine.L.snk_pit_deep_scratch_elems(rows, engine.S, self.depth)
-        if elems < 0:
-            raise EngineError(f"no deep scratch for {rows} rows of {engine.S} snakes at depth {self.depth}")
-        if self._scratch is None or self._scratch.numel() < elems:
-            self._scratch = engine.new((elems,), torch.int32)
-        self._subs = subs
-        return subs, self._handles, self._scratch
 
     def q_rows(self, engine, pairs):
         """pairs int32[rows][2] (slot, snake id) on the device -> the three move scores float32[rows][3] on the device"""
-        m = int(pairs.shape[0])
         F, FD = engine.L.snk_pit_look_fanout(engine.S), engine.L.snk_pit_deep_fanout(engine.S, self.depth)
         if FD < 0:
             raise EngineError(f"Deep depth {self.depth} is too deep for {engine.S} snakes (fanout {F} a tick, at most 6561 in all)")
-        q = engine.new((m, 3), torch.float32)
-        per_row = engine.slot_bytes * sum(F ** k for k in range(1, self.depth + 1))
-        per = max(DEEP_BYTE_BUDGET // per_row, 1)     # a boundary inside a game is harmless: the game is cloned again
-        for lo in range(0, m, per):
-            cnt = min(per, m - lo)
-            subs, handles, scratch = self._buffers(engine, cnt, F)
-            if self.leaf is None:
-                check(engine.L.snk_pit_deep_values(engine.h, _ptr(handles), self.depth, _ptr(pairs[lo:lo + cnt]), cnt, self.flags,
-                                                   _ptr(scratch), _ptr(q[lo:lo + cnt]), _stream()))
-            else:
-                check(engine.L.snk_pit_deep_values_leaf(engine.h, _ptr(handles), self.depth, _ptr(pairs[lo:lo + cnt]), cnt, self.flags,
-                                                        LEAF_TERRITORY, self.leaf.hungry, _ptr(scratch), _ptr(q[lo:lo + cnt]),
-                                                        _stream()))
-        return q
+        levels = [F ** k for k in range(1, self.depth + 1)]
+
+        def need(rows):
+            elems = engine.L.snk_pit_deep_scratch_elems(rows, engine.S, self.depth)
+            if elems < 0:
+                raise EngineError(f"no deep scratch for {rows} rows of {engine.S} snakes at depth {self.depth}")
+            return [min(rows, engine.n_slots) * n for n in levels], elems
+        # a boundary inside a game is harmless: the game is cloned again
+        return self._chunks(engine, pairs, "snk_pit_deep_values", max(DEEP_BYTE_BUDGET // (engine.slot_bytes * sum(levels)), 1), need,
+                            lambda subs, handles: (_ptr(handles), self.depth))
 
 
 PLAYOUT_SLOT_BUDGET = 1 << 18        # clones (rows times 3 * playouts) of one snk_pit_playout_values call: 296 MiB of 11x11x4 records
 
 
-class Playout(Scripted):
+class Playout(_Search):
     """Flat Monte-Carlo over the scripted policy (include/snake_engine.h states it): every unblocked move is played out
     `playouts` times for `horizon` ticks on copies of the game, every snake following the plain script, or with probability
     `explore` / 256 a uniformly drawn unblocked move, and the move scores how long the snake survives; the plain script breaks the
@@ -335,14 +330,12 @@ class Playout(Scripted):
     seed, slot and snake), so the same position and seed give the same move in every run and in every row order.  The defaults
     (8 playouts, 8 ticks, explore 64) are a starting point, not tuned values.  The same flags and refusals as Scripted, and it
     sits wherever a Scripted can; a Searcher around it is a TypeError.  It owns a sub-engine without food spawning for the
-    clones and the scratch of snk_pit_playout_values, made at first use, remade when the geometry or the device changes, and
-    grown when more rows arrive; a call takes at most PLAYOUT_SLOT_BUDGET // (3 * playouts) rows, at least one.
-    leaf=Territory(flags, hungry) as for Lookahead: the plain scores and every playout move are territory's
-    (snk_pit_playout_values_leaf)."""
+    clones and the scratch of snk_pit_playout_values (_Search keeps them); a call takes at most
+    PLAYOUT_SLOT_BUDGET // (3 * playouts) rows, at least one.  leaf=Territory(flags, hungry) as for Lookahead: the plain scores
+    and every playout move are territory's (snk_pit_playout_values_leaf)."""
 
     def __init__(self, flags=SCRIPT_SPACE | SCRIPT_HEADS | SCRIPT_FOOD, playouts=8, horizon=8, explore=64, seed=0, leaf=None):
-        super().__init__(flags)
-        self.leaf = checked_leaf(leaf, self.flags)
+        super().__init__(flags, leaf)
         playouts, horizon, explore, seed = int(playouts), int(horizon), int(explore), int(seed)
         if not 1 <= playouts <= 64:
             raise ValueError(f"Playout playouts {playouts}: 1 .. 64")
@@ -353,44 +346,17 @@ class Playout(Scripted):
         if not 0 <= seed < 1 << 64:
             raise ValueError(f"Playout seed {seed}: 64 bits")
         self.playouts, self.horizon, self.explore, self.seed = playouts, horizon, explore, seed
-        self._sub = self._scratch = None
-
-    def _buffers(self, engine, rows):
-        """the sub-engine and the scratch for a call of `rows` rows"""
-        sub = self._sub
-        key = (engine.H, engine.W, engine.S, engine.health_dec, engine.device)
-        if sub is None or (sub.H, sub.W, sub.S, sub.health_dec, sub.device) != key:
-            sub = self._scratch = None
-        slots = rows * 3 * self.playouts
-        if sub is None or sub.n_slots < slots:
-            if sub is not None:
-                sub.close()
-            sub = Engine(slots, engine.H, engine.W, engine.S, engine.health_dec, 0, seed=0, device=engine.device.index)
-        elems = engine.L.snk_pit_playout_scratch_elems(rows, engine.S, self.playouts)
-        if elems < 0:
-            raise EngineError(f"no playout scratch for {rows} rows of {engine.S} snakes and {self.playouts} playouts")
-        if self._scratch is None or self._scratch.numel() < elems:
-            self._scratch = engine.new((elems,), torch.int32)
-        self._sub = sub
-        return sub, self._scratch
 
     def q_rows(self, engine, pairs):
         """pairs int32[rows][2] (slot, snake id) on the device -> the three move scores float32[rows][3] on the device"""
-        m = int(pairs.shape[0])
-        q = engine.new((m, 3), torch.float32)
-        per = max(PLAYOUT_SLOT_BUDGET // (3 * self.playouts), 1)      # a cut anywhere changes nothing: the draws are keyed by slot and snake
-        for lo in range(0, m, per):
-            cnt = min(per, m - lo)
-            sub, scratch = self._buffers(engine, cnt)
-            if self.leaf is None:
-                check(engine.L.snk_pit_playout_values(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, self.playouts,
-                                                      self.horizon, self.explore, self.seed, _ptr(scratch), _ptr(q[lo:lo + cnt]),
-                                                      _stream()))
-            else:
-                check(engine.L.snk_pit_playout_values_leaf(engine.h, sub.h, _ptr(pairs[lo:lo + cnt]), cnt, self.flags, LEAF_TERRITORY,
-                                                           self.leaf.hungry, self.playouts, self.horizon, self.explore, self.seed,
-                                                           _ptr(scratch), _ptr(q[lo:lo + cnt]), _stream()))
-        return q
+        def need(rows):
+            elems = engine.L.snk_pit_playout_scratch_elems(rows, engine.S, self.playouts)
+            if elems < 0:
+                raise EngineError(f"no playout scratch for {rows} rows of {engine.S} snakes and {self.playouts} playouts")
+            return [rows * 3 * self.playouts], elems
+        # a cut anywhere changes nothing: the draws are keyed by slot and snake
+        return self._chunks(engine, pairs, "snk_pit_playout_values", max(PLAYOUT_SLOT_BUDGET // (3 * self.playouts), 1), need, self._one,
+                            (self.playouts, self.horizon, self.explore, self.seed))
 
 
 def mixed_values(eng, sides, rows, pairs):

@@ -687,14 +687,15 @@ int snk_pit_look_values(const snk_engine *e, snk_engine *sub, const int32_t *d_p
  * snake, or a slot outside 0..n_slots-1 or a snake id outside 0..S-1, gets -1, -1, -1.
  * snk_pit_deep_fanout(S, depth): F^depth; -1 for S outside 2..8, depth < 1 or F^depth > 6561 (depth <= 4 at S = 2, <= 2 from S = 3).
  * snk_pit_deep_scratch_elems(m, S, depth): the int32 elements of d_scratch; -1 on those refusals, for m < 0 or m * F^depth above
- *   2^28.  At depth 1 it is at least snk_pit_look_scratch_elems(m, S).
+ *   2^28.  At depth 1 it is equal to snk_pit_look_scratch_elems(m, S).
  * snk_pit_deep_values: subs[k-1] holds level k of the trees, k = 1 .. depth; every sub-engine has e's geometry, device and
  *   health_dec, spawns no food, and is neither e nor another of them; their records are overwritten, e's are only read.  Rows are
  *   grouped as in snk_pit_look_values and the rows of a group share their children at EVERY level: node c of level k is slot c
  *   of subs[k-1], child c % F of node c / F of level k-1, and level 0 is group i = the game itself, so level k of group i
  *   occupies slots i*F^k .. of subs[k-1].  THE ROWS OF A GROUP WHOSE INDEX IS min over k of (n_slots of subs[k-1]) / F^k OR MORE
- *   GET -1, -1, -1, as above; the call refuses sub-engines of fewer than min(m, n_slots of e) * F^k slots.  depth == 1 calls
- *   snk_pit_look_values(e, subs[0], ...) and is therefore that call bit for bit.  From depth 2, launches only, all on `stream`:
+ *   GET -1, -1, -1, as above; the call refuses sub-engines of fewer than min(m, n_slots of e) * F^k slots.  snk_pit_look_values
+ *   (e, sub, ...) runs this search with depth 1 and subs = {sub}, so depth == 1 is that call bit for bit, launch for launch (the
+ *   sequence stated there, its fold being this one's with level 0 as the parent).  From depth 2, launches only, all on `stream`:
  *   the lookahead's scan (groups, source slots, alive bits), snk_pit_script_values on e for the fallback rows; per level the
  *   fan (a thread per node: active when its parent is active, has 2..4 snakes alive after its step and the node's index is
  *   below 3^alive -- so a child in which the game is over, or past the last group, has no children --, and its dense moves),
@@ -784,7 +785,7 @@ int snk_pit_playout_values(const snk_engine *e, snk_engine *sub, const int32_t *
  * script's range (-1 .. 2^24 - 1), so every bound stated above holds.  Identities:
  *   with SNK_LEAF_SCRIPT and hungry = 100 each call writes what its namesake without _leaf writes, bit for bit (the namesakes are
  *     these calls with those two arguments);
- *   snk_pit_deep_values_leaf at depth 1 calls snk_pit_look_values_leaf and is that call bit for bit.
+ *   snk_pit_look_values_leaf is snk_pit_deep_values_leaf at depth 1 with its one sub-engine, so the two agree bit for bit.
  * Scratch: snk_pit_look_scratch_elems / snk_pit_deep_scratch_elems / snk_pit_playout_scratch_elems, unchanged.  The sub-engine
  * requirements, the rows that get -1, -1, -1, m == 0 and every refusal are the namesake's; a leaf outside the two constants and a
  * hungry outside what the leaf allows are two more errors before any launch.  Launches: the namesake's, with k_pit_territory

@@ -151,7 +151,9 @@ def test_the_scratch_function():
     L = snake_engine.lib()
     for S in range(2, 9):
         for m in (0, 1, 2, 255, 1000, 16384):
-            assert L.snk_pit_deep_scratch_elems(m, S, 1) >= L.snk_pit_look_scratch_elems(m, S) >= 0
+            assert L.snk_pit_deep_scratch_elems(m, S, 1) == L.snk_pit_look_scratch_elems(m, S) >= 0
+        for m in (0, 1, 2, 100, 1000):                            # depth 1 is the lookahead: one scratch plan
+            assert L.snk_pit_deep_scratch_elems(m, S, 1) == L.snk_pit_look_scratch_elems(m, S)
     assert L.snk_pit_deep_scratch_elems(-1, 4, 2) == -1
     assert [L.snk_pit_deep_scratch_elems(8, S, 2) for S in (1, 9, 0)] == [-1] * 3
     assert [L.snk_pit_deep_scratch_elems(8, S, d) for S, d in ((4, 0), (4, 3), (3, 3), (2, 5), (2, -1))] == [-1] * 5

@@ -97,6 +97,8 @@ def _same(got, want, pairs, what):
 # ---- 1. depth 1 is the lookahead, bit for bit ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cfg", ["7x7x2", "9x9x3", "11x11x4"])
 def test_depth_one_is_snk_pit_look_values_bit_for_bit(cfg):
+    """the two entry points run one body since the lookahead became the deep search at depth 1, so this compares a path with
+    itself (two names, two argument lists); the exact pin of the scores is the integer comparison with look_ref in test_look_gpu"""
     import torch
     from snake_engine._lib import check
     H, W, S, hd, boards = K.sampled(cfg)

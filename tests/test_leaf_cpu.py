@@ -224,3 +224,22 @@ def test_the_three_entry_points_are_declared_exported_and_bound():
         for leaf, hungry in ((2, 100), (-1, 100), (0, 40), (1, 101), (1, -1)):
             assert call(leaf, hungry) == -1 and b"leaf=" in L.snk_last_error() and b"_leaf" in L.snk_last_error()
         assert call(1, 40) == -1 and b"NULL" in L.snk_last_error()
+
+
+def test_a_refusal_names_the_leaf_entry_point_it_came_through():
+    """the six search entry points with a valid leaf and a NULL engine at m = 0: each is refused, and the message starts with the
+    name of its own _leaf entry point -- the plain ones forward to it -- whichever body the refusal is written in.  No device:
+    the call returns before any HIP call"""
+    import snake_engine
+    L = snake_engine.lib()
+    calls = {"snk_pit_look_values": lambda: L.snk_pit_look_values(None, None, None, 0, 7, None, None, None),
+             "snk_pit_look_values_leaf": lambda: L.snk_pit_look_values_leaf(None, None, None, 0, 7, 1, 40, None, None, None),
+             "snk_pit_deep_values": lambda: L.snk_pit_deep_values(None, None, 1, None, 0, 7, None, None, None),
+             "snk_pit_deep_values_leaf": lambda: L.snk_pit_deep_values_leaf(None, None, 1, None, 0, 7, 1, 40, None, None, None),
+             "snk_pit_playout_values": lambda: L.snk_pit_playout_values(None, None, None, 0, 7, 2, 3, 64, 0, None, None, None),
+             "snk_pit_playout_values_leaf": lambda: L.snk_pit_playout_values_leaf(None, None, None, 0, 7, 1, 40, 2, 3, 64, 0, None, None,
+                                                                                  None)}
+    for name, call in calls.items():
+        leaf_name = name if name.endswith("_leaf") else name + "_leaf"
+        assert call() == -1, name
+        assert L.snk_last_error().startswith(leaf_name.encode() + b":"), (name, L.snk_last_error())

@@ -158,6 +158,37 @@ def test_groups_beyond_the_sub_engine_get_minus_one():
     assert np.array_equal(got[:len(pairs)], _want(CFG, pairs)) and (got[len(pairs):] == -1).all()
 
 
+def _four_kinds(cfg):
+    """a pair list with every kind of row the fold tells apart, and the groups it forms: a dead pair, an out-of-range pair and
+    (-1, -1), a group each, then every alive row, a group per board"""
+    H, W, S, hd, boards = K.sampled(cfg)
+    dead = [(g, s) for g, st in enumerate(boards) for s in range(S) if not st["alive"][s]][-1]
+    pairs = np.concatenate([np.array([dead, (1 << 20, 0), (-1, -1)], np.int32), _alive_pairs(boards)])
+    groups = 1 + int(np.count_nonzero(np.diff(pairs[:, 0])))
+    return pairs, groups
+
+
+@pytest.mark.parametrize("cfg", ["7x7x2", CFG])
+def test_every_kind_of_row_in_one_call_through_a_sub_engine_one_group_short(cfg):
+    """searched rows, rows that fall back (dead, out of range, (-1, -1), a lone survivor) and rows whose group the sub-engine
+    does not hold, in one list: the last board's rows are not served and get -1, every other row the statement's integers"""
+    H, W, S, hd, boards = K.sampled(cfg)
+    pairs, groups = _four_kinds(cfg)
+    assert groups == len(boards) + 3
+    eng = _engine_with(cfg)
+    got = _values(eng, _sub(eng, groups - 1), pairs)
+    want = _want(cfg, pairs)
+    last = pairs[:, 0] == len(boards) - 1
+    last[0] = False                                                           # the dead pair may name the last board: it is group 0
+    assert last.any() and (want[last] != -1).any() and (want[:3] == -1).all()
+    alive = np.array([np.count_nonzero(st["alive"]) for st in boards])
+    assert ((alive >= 2) & (alive <= 4))[:-1].any() and (alive < 2).any() == (cfg == "7x7x2"), "searched rows; 7x7x2: lone survivors too"
+    want[last] = -1
+    bad = np.flatnonzero((got != want).any(1))
+    assert len(bad) == 0, f"{cfg}: {len(bad)} of {len(pairs)} rows differ, first {pairs[bad[0]]}: {got[bad[0]]} != {want[bad[0]]}"
+    assert (got[~last] <= -3).any() and (got[~last] >= 0).any()
+
+
 def test_refusals():
     import torch
     from snake_engine import Engine, EngineError
