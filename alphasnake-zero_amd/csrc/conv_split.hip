@@ -1991,16 +1991,17 @@ extern "C" int snk_conv_rect_plan_pack_host(const unsigned *h_bbox, int n_images
     return 0;
 }
 
-static int conv_f16s_rect_launch(const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
+// who: the entry point that was called, for the wording of a refusal
+static int conv_f16s_rect_launch(const char *who, const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
                                  const float *d_residual, float *d_out, const void *d_desc, const int *d_count,
                                  const float *d_bg_in, int grow_in, const float *d_bg_res, int grow_res, const float *d_bg_out,
                                  int n_images, int height, int width, bool act16, void *stream, bool bf = false, bool mx = false)
 {
-    SNK_REQUIRE(grow_in >= 0 && grow_in < 128 && grow_res >= 0 && grow_res < 128, "snk_conv3x3_bn_f16s_rect: grow_in %d, grow_res %d", grow_in, grow_res);
-    SNK_REQUIRE(d_x && d_wS && d_scale && d_shift && d_out && d_desc && d_count, "snk_conv3x3_bn_f16s_rect: NULL argument");
-    SNK_REQUIRE(d_out != d_x, "snk_conv3x3_bn_f16s_rect: in-place convolution is not possible");
+    SNK_REQUIRE(grow_in >= 0 && grow_in < 128 && grow_res >= 0 && grow_res < 128, "%s: grow_in %d, grow_res %d", who, grow_in, grow_res);
+    SNK_REQUIRE(d_x && d_wS && d_scale && d_shift && d_out && d_desc && d_count, "%s: NULL argument", who);
+    SNK_REQUIRE(d_out != d_x, "%s: in-place convolution is not possible", who);
     const long mb = rect_max_blocks(n_images, height, width, act16);
-    SNK_REQUIRE(mb >= 0 && mb < (1l << 31) && (long)height * width * HS_C < (1l << 31), "snk_conv3x3_bn_f16s_rect: bad shape %d x %d x %d",
+    SNK_REQUIRE(mb >= 0 && mb < (1l << 31) && (long)height * width * HS_C < (1l << 31), "%s: bad shape %d x %d x %d", who,
                 n_images, height, width);
     if (n_images == 0) return 0;
     ConvHsArgs a = {d_x, (const f16x8 *)d_wS, (const float *)((const _Float16 *)d_wS + HS_WS_ELEMS), d_scale, d_shift,
@@ -2026,8 +2027,8 @@ extern "C" int snk_conv3x3_bn_f16s_rect(const float *d_x, const void *d_wS, cons
                                         const float *d_bg_in, int grow_in, const float *d_bg_res, int grow_res,
                                         const float *d_bg_out, int n_images, int height, int width, void *stream)
 {
-    return conv_f16s_rect_launch(d_x, d_wS, d_scale, d_shift, d_residual, d_out, d_desc, d_count, d_bg_in, grow_in, d_bg_res, grow_res,
-                                 d_bg_out, n_images, height, width, false, stream);
+    return conv_f16s_rect_launch("snk_conv3x3_bn_f16s_rect", d_x, d_wS, d_scale, d_shift, d_residual, d_out, d_desc, d_count, d_bg_in,
+                                 grow_in, d_bg_res, grow_res, d_bg_out, n_images, height, width, false, stream);
 }
 
 // snk_conv3x3_bn_f16s_rect on the packed plan's descriptors (snk_conv_rect_plan_pack)
@@ -2060,9 +2061,9 @@ extern "C" int snk_conv3x3_bn_f16_act16_rect(const void *d_x16, const void *d_wS
                                              const void *d_bg_in16, int grow_in, const void *d_bg_res16, int grow_res,
                                              const void *d_bg_out16, int n_images, int height, int width, void *stream)
 {
-    return conv_f16s_rect_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, (float *)d_out16, d_desc,
-                                 d_count, (const float *)d_bg_in16, grow_in, (const float *)d_bg_res16, grow_res,
-                                 (const float *)d_bg_out16, n_images, height, width, true, stream);
+    return conv_f16s_rect_launch("snk_conv3x3_bn_f16_act16_rect", (const float *)d_x16, d_wS, d_scale, d_shift,
+                                 (const float *)d_residual16, (float *)d_out16, d_desc, d_count, (const float *)d_bg_in16, grow_in,
+                                 (const float *)d_bg_res16, grow_res, (const float *)d_bg_out16, n_images, height, width, true, stream);
 }
 
 // the same for the bf16 tower (bf16 activations in and out, bf16 background images, weights = snk_conv3x3_prepare_weights_bf16)
@@ -2071,9 +2072,9 @@ extern "C" int snk_conv3x3_bn_bf16_act16_rect(const void *d_x16, const void *d_w
                                               const void *d_bg_in16, int grow_in, const void *d_bg_res16, int grow_res,
                                               const void *d_bg_out16, int n_images, int height, int width, void *stream)
 {
-    return conv_f16s_rect_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, (float *)d_out16, d_desc,
-                                 d_count, (const float *)d_bg_in16, grow_in, (const float *)d_bg_res16, grow_res,
-                                 (const float *)d_bg_out16, n_images, height, width, true, stream, true);
+    return conv_f16s_rect_launch("snk_conv3x3_bn_bf16_act16_rect", (const float *)d_x16, d_wS, d_scale, d_shift,
+                                 (const float *)d_residual16, (float *)d_out16, d_desc, d_count, (const float *)d_bg_in16, grow_in,
+                                 (const float *)d_bg_res16, grow_res, (const float *)d_bg_out16, n_images, height, width, true, stream, true);
 }
 
 extern "C" int snk_conv3x3_bn_f16s(const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
@@ -2283,9 +2284,9 @@ extern "C" int snk_conv3x3_bn_mxfp8_act16_rect(const void *d_x16, const void *d_
                                                const void *d_bg_out16, int n_images, int height, int width, void *stream)
 {
     SNK_REQUIRE(n_images > 0, "snk_conv3x3_bn_mxfp8_act16_rect: %d images", n_images);
-    return conv_f16s_rect_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, (float *)d_out16, d_desc,
-                                 d_count, (const float *)d_bg_in16, grow_in, (const float *)d_bg_res16, grow_res,
-                                 (const float *)d_bg_out16, n_images, height, width, true, stream, true, true);
+    return conv_f16s_rect_launch("snk_conv3x3_bn_mxfp8_act16_rect", (const float *)d_x16, d_wS, d_scale, d_shift,
+                                 (const float *)d_residual16, (float *)d_out16, d_desc, d_count, (const float *)d_bg_in16, grow_in,
+                                 (const float *)d_bg_res16, grow_res, (const float *)d_bg_out16, n_images, height, width, true, stream, true, true);
 }
 
 extern "C" int snk_conv3x3_bn_mxfp8_act16_head(const void *d_x16, const void *d_wS, const float *d_scale, const float *d_shift,
