@@ -1093,7 +1093,8 @@ __global__ __launch_bounds__(1024) void k_f16s_wscale(const float *__restrict__ 
         const float mx = red[0];
         int k = 0;
         if (mx > 0.f && mx < 3.0e38f) k = 8 - ilogbf(mx);
-        k = max(-100, min(100, k));
+        k = max(-119, min(100, k));                           // (-119 is never reached: ilogb <= 127; a clamp at -100 left
+                                                              //  max * 2^k >= 65536 from max = 2^116 on: hi halves of infinity)
         tail[0] = ldexpf(1.0f, -k);
         tail[1] = ldexpf(1.0f, k);
         tail[2] = in_tail ? in_tail[2] : x_scale;             // the producer of the input measured its range (train.hip)
@@ -1112,6 +1113,15 @@ __global__ void k_f16s_tail_from(const float *__restrict__ w_tail, const float *
     }
 }
 
+// f16(v), round to nearest even, a zero result with v's sign: the compiler folds the product in front of the conversion into
+// v_fma_mixlo_f16 (w, 2^k, +0), whose +0 addend turns a weight of -0.0 into hi = +0 and lo = -0 (the same value; the images are
+// specified byte for byte, tests/weight_image_ref.py)
+__device__ __forceinline__ _Float16 hs_f16_keep_sign(float v)
+{
+    const unsigned short b = __builtin_bit_cast(unsigned short, (_Float16)v) | (unsigned short)((__builtin_bit_cast(unsigned, v) >> 16) & 0x8000u);
+    return __builtin_bit_cast(_Float16, b);
+}
+
 // Keras kernel (kh, kw, cin, cout) float32 -> split f16 fragments in the order the conv kernel's waves load them
 // FLIP: the kernel of the INPUT GRADIENT of the same layer -- taps mirrored, channel axes swapped: w'[tap][ci][co] = w[8 - tap][co][ci]
 template <bool FLIP>
@@ -1128,7 +1138,7 @@ __global__ void k_f16s_weights(const float *__restrict__ w, _Float16 *__restrict
     for (int j = 0; j < 8; ++j) {
         const int cin = HS_KC * c + 8 * h + j;
         const float val = (FLIP ? w[(long)((8 - tap) * HS_C + cout) * HS_C + cin] : w[(long)(tap * HS_C + cin) * HS_C + cout]) * mul;
-        const _Float16 hi = (_Float16)val;
+        const _Float16 hi = hs_f16_keep_sign(val);
         wS[(long)v * 8 + j] = hl ? (_Float16)(val - (float)hi) : hi;
     }
 }
@@ -1149,7 +1159,7 @@ __global__ void k_a16_weights(const float *__restrict__ w, _Float16 *__restrict_
     for (int j = 0; j < 8; ++j) {
         const int cin = 32 * c + 16 * ks + 8 * h + j;
         const float val = w[(long)(tap * HS_C + cin) * HS_C + cout] * mul;
-        wS[(long)v * 8 + j] = BF ? __builtin_bit_cast(_Float16, (__bf16)val) : (_Float16)val;
+        wS[(long)v * 8 + j] = BF ? __builtin_bit_cast(_Float16, (__bf16)val) : hs_f16_keep_sign(val);
     }
 }
 
@@ -1317,7 +1327,7 @@ __global__ __launch_bounds__(1024) void k_f16s_wscale_batch(F16sBatch b)
         const float mx = red[0];
         int k = 0;
         if (mx > 0.f && mx < 3.0e38f) k = 8 - ilogbf(mx);          // as k_f16s_wscale
-        k = max(-100, min(100, k));
+        k = max(-119, min(100, k));
         tail[0] = ldexpf(1.0f, -k);
         tail[1] = ldexpf(1.0f, k);
         tail[4] = tail[5] = tail[6] = tail[7] = 0.f;              // range flag, no guard word; tail[2..3] belong to the input's producer
@@ -1341,7 +1351,7 @@ __global__ __launch_bounds__(256) void k_f16s_weights_batch(F16sBatch b)
     for (int j = 0; j < 8; ++j) {
         const int cin = HS_KC * c + 8 * h + j;
         const float val = (flip ? w[(long)((8 - tap) * HS_C + cout) * HS_C + cin] : w[(long)(tap * HS_C + cin) * HS_C + cout]) * mul;
-        const _Float16 hi = (_Float16)val;
+        const _Float16 hi = hs_f16_keep_sign(val);
         wS[(long)v * 8 + j] = hl ? (_Float16)(val - (float)hi) : hi;
     }
 }
