@@ -1112,14 +1112,19 @@ __global__ __launch_bounds__(CMP_THREADS) void k_cmp_one(const uint8_t *__restri
 #define PIT_ITEMS 4
 #define PIT_TILE (CMP_THREADS * PIT_ITEMS)      // games per block
 
-// bit s = snake s of game gi is alive; 0 for a game that is closed (or past the end)
+// bit s = snake s of the record in `slot` is alive
+__device__ static inline uint32_t slot_alive_bits(const uint8_t *__restrict__ state, const Layout &L, int slot)
+{
+    const SnakeMeta *meta = (const SnakeMeta *)(state + (size_t)slot * L.stride + L.meta_off);
+    uint32_t bits = 0u;
+    for (int s = 0; s < L.S; ++s) bits |= (meta[s].alive ? 1u : 0u) << s;
+    return bits;
+}
+
+// the same of game gi; 0 for a game that is closed (or past the end)
 __device__ static inline uint32_t pit_alive_bits(const uint8_t *__restrict__ state, const Layout &L, const uint8_t *live, int gi, int n)
 {
-    if (gi >= n || !live[gi]) return 0u;
-    const SnakeMeta *meta = (const SnakeMeta *)(state + (size_t)gi * L.stride + L.meta_off);
-    uint32_t b = 0u;
-    for (int s = 0; s < L.S; ++s) b |= (meta[s].alive ? 1u : 0u) << s;
-    return b;
+    return gi < n && live[gi] ? slot_alive_bits(state, L, gi) : 0u;
 }
 
 // rows of each team in the block's PIT_TILE games: tile_sums[2 b] team A, [2 b + 1] team B
@@ -1470,130 +1475,197 @@ __device__ static inline int script_ring_cell(const uint8_t *rec, const Layout &
     return L.cell_bytes == 1 ? (int)r[idx] : (int)((const uint16_t *)r)[idx];
 }
 
+// ---- what the two one-launch scorers share (k_pit_script here, k_pit_territory below): each kernel states only its own part
+// a lane's row: lane k of the quad of row `row`, the row's pair (slot, snake s) decoded and guarded.  in: the row is below m; ok:
+// the pair names an alive snake of a slot of the engine -- when it does not, rec is slot 0's record and nothing of it is read
+struct ScriptRow {
+    int row, k, s;
+    bool in, ok;
+    const uint8_t *rec;
+    const SnakeMeta *meta;
+    SnakeMeta me;
+};
+
+__device__ __forceinline__ ScriptRow script_row(const uint8_t *__restrict__ state, const Layout &L, int n_slots,
+                                                const int32_t *__restrict__ pairs, int m)
+{
+    const int t = blockIdx.x * BLOCK_THREADS + threadIdx.x;
+    ScriptRow R;
+    R.row = t >> 2;
+    R.k = t & 3;
+    R.in = R.row < m;
+    int g = -1;
+    R.s = -1;
+    if (R.in) { g = pairs[2 * (size_t)R.row]; R.s = pairs[2 * (size_t)R.row + 1]; }
+    const bool pair_ok = R.in && g >= 0 && g < n_slots && R.s >= 0 && R.s < L.S;
+    R.rec = state + (size_t)(pair_ok ? g : 0) * L.stride;
+    R.meta = (const SnakeMeta *)(R.rec + L.meta_off);
+    R.me = {0, 0, 0, 0, 0};
+    if (pair_ok) R.me = R.meta[R.s];
+    R.ok = pair_ok && R.me.alive;
+    return R;
+}
+
+// the ring cells of snake o (its meta mo) into a plane: tails and all, min(len, cap) steps
+template <int FW>
+__device__ __forceinline__ void script_mark_ring(const ScriptRow &R, const Layout &L, int o, const SnakeMeta &mo, uint64_t (&occ)[FW])
+{
+    const int len = (int)mo.len < L.cap ? (int)mo.len : L.cap;
+    for (int i = 0; i < len; ++i) {
+        const int c = script_ring_cell(R.rec, L, o, mo.tail + i);
+        if (c < L.NC) {
+#pragma unroll
+            for (int w = 0; w < FW; ++w) occ[w] |= (c >> 6) == w ? 1ull << (c & 63) : 0ull;
+        }
+    }
+}
+
+// a plane ORed across the quad, every lane of it getting the whole.  Cross-lane: all 64 lanes of the wavefront must reach the call
+template <int FW>
+__device__ __forceinline__ void quad_or(uint64_t (&plane)[FW])
+{
+#pragma unroll
+    for (int w = 0; w < FW; ++w) {
+        int lo = (int)(uint32_t)plane[w], hi = (int)(uint32_t)(plane[w] >> 32);
+        lo |= __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xF, 0xF, true);      // quad_perm [1,0,3,2]
+        hi |= __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xF, 0xF, true);
+        lo |= __builtin_amdgcn_update_dpp(0, lo, 0x4E, 0xF, 0xF, true);      // quad_perm [2,3,0,1]
+        hi |= __builtin_amdgcn_update_dpp(0, hi, 0x4E, 0xF, 0xF, true);
+        plane[w] = ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
+    }
+}
+
+// where relative move R.k takes the row's head: (y, x), its cell tc (0 off the board), and blocked = off the board or occupied
+struct ScriptTarget {
+    int y, x, tc;
+    bool blocked;
+};
+
+template <int FW>
+__device__ __forceinline__ ScriptTarget script_target(const ScriptRow &R, const Layout &L, const uint64_t (&occ)[FW])
+{
+    const int hc = script_ring_cell(R.rec, L, R.s, R.me.tail + (int)R.me.len - 1);
+    const int d = (R.k + R.me.dir + 3) & 3;                   // k_step's heading: 0 = y-1, 1 = x+1, 2 = y+1, 3 = x-1
+    ScriptTarget T;
+    T.y = hc / L.W;
+    T.x = hc - T.y * L.W;
+    T.y += (d == 2) - (d == 0);
+    T.x += (d == 1) - (d == 3);
+    const bool oob = (T.y < 0) | (T.y >= L.H) | (T.x < 0) | (T.x >= L.W);
+    T.tc = oob ? 0 : T.y * L.W + T.x;
+    T.blocked = oob;
+#pragma unroll
+    for (int w = 0; w < FW; ++w) T.blocked |= (T.tc >> 6) == w && ((occ[w] >> (T.tc & 63)) & 1ull);
+    return T;
+}
+
+// one round of growth: nx = r and its four neighbours inside fr, as whole-plane shifts
+template <int FW>
+__device__ __forceinline__ void script_grow(const uint64_t (&r)[FW], const uint64_t (&fr)[FW], const ScriptMasks &K, int WW,
+                                            uint64_t (&nx)[FW])
+{
+#pragma unroll
+    for (int w = 0; w < FW; ++w) {
+        const uint64_t below = w > 0 ? r[w > 0 ? w - 1 : 0] : 0ull, above = w < FW - 1 ? r[w < FW - 1 ? w + 1 : 0] : 0ull;
+        const uint64_t from_up = (r[w] << WW) | (below >> (64 - WW));         // cell c takes cell c - W
+        const uint64_t from_dn = (r[w] >> WW) | (above << (64 - WW));         // cell c takes cell c + W
+        const uint64_t from_lf = ((r[w] << 1) | (below >> 63)) & K.not_c0[w]; // cell c takes cell c - 1, not across a row end
+        const uint64_t from_rt = ((r[w] >> 1) | (above << 63)) & K.not_cl[w]; // cell c takes cell c + 1
+        nx[w] = (r[w] | from_up | from_dn | from_lf | from_rt) & fr[w];
+    }
+}
+
+// the score of a move that is not blocked, from its space (the script) or territory.  safe: 0 when another alive snake at least as
+// long as the row's has its head next to the target; food: H + W - the smallest Manhattan distance from the target to a food cell,
+// 0 without food and for a row that is not `hungry` (the script's rows always are)
+template <int FW>
+__device__ __forceinline__ int script_score(const ScriptRow &R, const Layout &L, const ScriptMasks &K, uint32_t flags, bool hungry,
+                                            const ScriptTarget &T, int space)
+{
+    const int len_s = R.me.len;
+    int safe = 1;
+    if (flags & SNK_SCRIPT_HEADS) {
+        for (int o = 0; o < L.S; ++o) {
+            if (o == R.s) continue;
+            const SnakeMeta mo = R.meta[o];
+            if (!mo.alive || (int)mo.len < len_s) continue;
+            const int ho = script_ring_cell(R.rec, L, o, mo.tail + mo.len - 1);
+            const int oy = ho / L.W, ox = ho - oy * L.W;
+            if (abs(oy - T.y) + abs(ox - T.x) == 1) safe = 0;
+        }
+    }
+    int food = 0;
+    if ((flags & SNK_SCRIPT_FOOD) && hungry) {
+        const uint64_t *fw = (const uint64_t *)(R.rec + L.food_off);
+        int best = 1 << 20;
+#pragma unroll
+        for (int w = 0; w < FW; ++w) {
+            uint64_t f = fw[w < L.FW ? w : 0] & K.valid[w];          // valid[] is 0 from the layout's word count up
+            while (f) {                                              // one set bit less per pass: at most 64
+                const int c = w * 64 + __builtin_ctzll(f);
+                f &= f - 1ull;
+                const int fy = c / L.W, fx = c - fy * L.W;
+                const int dist = abs(fy - T.y) + abs(fx - T.x);
+                best = dist < best ? dist : best;
+            }
+        }
+        if (best != (1 << 20)) food = L.H + L.W - best;
+    }
+    int room = space < len_s ? space : len_s;
+    room = room < 255 ? room : 255;
+    const int fill = space < 511 ? space : 511;
+    return ((room * 2 + safe) * 64 + food) * 512 + fill;
+}
+
 template <int FW>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_pit_script(const uint8_t *__restrict__ state, Layout L, int n_slots,
                                                              const int32_t *__restrict__ pairs, int m, uint32_t flags,
                                                              ScriptMasks K, float *__restrict__ q)
 {
-    const int t = blockIdx.x * BLOCK_THREADS + threadIdx.x;
-    const int row = t >> 2, k = t & 3;
-    const bool in = row < m;
-    int g = -1, s = -1;
-    if (in) { g = pairs[2 * (size_t)row]; s = pairs[2 * (size_t)row + 1]; }
-    const bool pair_ok = in && g >= 0 && g < n_slots && s >= 0 && s < L.S;
-    const uint8_t *rec = state + (size_t)(pair_ok ? g : 0) * L.stride;
-    const SnakeMeta *meta = (const SnakeMeta *)(rec + L.meta_off);
-    SnakeMeta me = {0, 0, 0, 0, 0};
-    if (pair_ok) me = meta[s];
-    const bool ok = pair_ok && me.alive;
+    const ScriptRow R = script_row(state, L, n_slots, pairs, m);
 
     // ---- occupied: every ring cell of every alive snake, tails and the row's own body included
     uint64_t occ[FW];
 #pragma unroll
     for (int w = 0; w < FW; ++w) occ[w] = 0ull;
-    if (ok) {
-        for (int o = k; o < L.S; o += 4) {
-            const SnakeMeta mo = meta[o];
-            if (!mo.alive) continue;
-            const int len = (int)mo.len < L.cap ? (int)mo.len : L.cap;
-            for (int i = 0; i < len; ++i) {
-                const int c = script_ring_cell(rec, L, o, mo.tail + i);
-                if (c < L.NC) {
-#pragma unroll
-                    for (int w = 0; w < FW; ++w) occ[w] |= (c >> 6) == w ? 1ull << (c & 63) : 0ull;
-                }
-            }
+    if (R.ok) {
+        for (int o = R.k; o < L.S; o += 4) {
+            const SnakeMeta mo = R.meta[o];
+            if (mo.alive) script_mark_ring<FW>(R, L, o, mo, occ);
         }
     }
-#pragma unroll
-    for (int w = 0; w < FW; ++w) {                    // all 64 lanes are here: the quad's four partial planes become one
-        int lo = (int)(uint32_t)occ[w], hi = (int)(uint32_t)(occ[w] >> 32);
-        lo |= __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xF, 0xF, true);      // quad_perm [1,0,3,2]
-        hi |= __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xF, 0xF, true);
-        lo |= __builtin_amdgcn_update_dpp(0, lo, 0x4E, 0xF, 0xF, true);      // quad_perm [2,3,0,1]
-        hi |= __builtin_amdgcn_update_dpp(0, hi, 0x4E, 0xF, 0xF, true);
-        occ[w] = ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
-    }
+    quad_or<FW>(occ);                                 // all 64 lanes are here: the quad's four partial planes become one
 
     // ---- lane k < 3 scores relative move k
     int score = -1;
-    if (ok && k < 3) {
-        const int HH = L.H, WW = L.W;
-        const int len_s = me.len;
-        const int hc = script_ring_cell(rec, L, s, me.tail + len_s - 1);
-        const int d = (k + me.dir + 3) & 3;                   // k_step's heading: 0 = y-1, 1 = x+1, 2 = y+1, 3 = x-1
-        int y = hc / WW, x = hc - y * WW;
-        y += (d == 2) - (d == 0);
-        x += (d == 1) - (d == 3);
-        const bool oob = (y < 0) | (y >= HH) | (x < 0) | (x >= WW);
-        const int tc = oob ? 0 : y * WW + x;
-        bool blocked = oob;
-#pragma unroll
-        for (int w = 0; w < FW; ++w) blocked |= (tc >> 6) == w && ((occ[w] >> (tc & 63)) & 1ull);
-        if (!blocked) {
+    if (R.ok && R.k < 3) {
+        const ScriptTarget T = script_target<FW>(R, L, occ);
+        if (!T.blocked) {
             int space = 0;
-            if (flags & SNK_SCRIPT_SPACE) {
-                uint64_t fr[FW], r[FW];
+            if (flags & SNK_SCRIPT_SPACE) {           // the flood fill: a reach mask grown from the target until it stops
+                uint64_t fr[FW], r[FW], nx[FW];
 #pragma unroll
                 for (int w = 0; w < FW; ++w) {
                     fr[w] = ~occ[w] & K.valid[w];
-                    r[w] = (tc >> 6) == w ? 1ull << (tc & 63) : 0ull;
+                    r[w] = (T.tc >> 6) == w ? 1ull << (T.tc & 63) : 0ull;
                 }
                 for (int round = 0; round < L.NC; ++round) {  // a round that changes the mask adds a cell: at most NC - 1 of them
-                    uint64_t nx[FW];
+                    script_grow<FW>(r, fr, K, L.W, nx);
                     bool changed = false;
 #pragma unroll
                     for (int w = 0; w < FW; ++w) {
-                        const uint64_t below = w > 0 ? r[w > 0 ? w - 1 : 0] : 0ull, above = w < FW - 1 ? r[w < FW - 1 ? w + 1 : 0] : 0ull;
-                        const uint64_t from_up = (r[w] << WW) | (below >> (64 - WW));         // cell c takes cell c - W
-                        const uint64_t from_dn = (r[w] >> WW) | (above << (64 - WW));         // cell c takes cell c + W
-                        const uint64_t from_lf = ((r[w] << 1) | (below >> 63)) & K.not_c0[w]; // cell c takes cell c - 1, not across a row end
-                        const uint64_t from_rt = ((r[w] >> 1) | (above << 63)) & K.not_cl[w]; // cell c takes cell c + 1
-                        nx[w] = (r[w] | from_up | from_dn | from_lf | from_rt) & fr[w];
                         changed |= nx[w] != r[w];
+                        r[w] = nx[w];
                     }
-#pragma unroll
-                    for (int w = 0; w < FW; ++w) r[w] = nx[w];
                     if (!changed) break;
                 }
 #pragma unroll
                 for (int w = 0; w < FW; ++w) space += __popcll(r[w]);
             }
-            int safe = 1;
-            if (flags & SNK_SCRIPT_HEADS) {
-                for (int o = 0; o < L.S; ++o) {
-                    if (o == s) continue;
-                    const SnakeMeta mo = meta[o];
-                    if (!mo.alive || (int)mo.len < len_s) continue;
-                    const int ho = script_ring_cell(rec, L, o, mo.tail + mo.len - 1);
-                    const int oy = ho / WW, ox = ho - oy * WW;
-                    if (abs(oy - y) + abs(ox - x) == 1) safe = 0;
-                }
-            }
-            int food = 0;
-            if (flags & SNK_SCRIPT_FOOD) {
-                const uint64_t *fw = (const uint64_t *)(rec + L.food_off);
-                int best = 1 << 20;
-#pragma unroll
-                for (int w = 0; w < FW; ++w) {
-                    uint64_t f = fw[w < L.FW ? w : 0] & K.valid[w];          // valid[] is 0 from the layout's word count up
-                    while (f) {                                              // one set bit less per pass: at most 64
-                        const int c = w * 64 + __builtin_ctzll(f);
-                        f &= f - 1ull;
-                        const int fy = c / WW, fx = c - fy * WW;
-                        const int dist = abs(fy - y) + abs(fx - x);
-                        best = dist < best ? dist : best;
-                    }
-                }
-                if (best != (1 << 20)) food = HH + WW - best;
-            }
-            int room = space < len_s ? space : len_s;
-            room = room < 255 ? room : 255;
-            const int fill = space < 511 ? space : 511;
-            score = ((room * 2 + safe) * 64 + food) * 512 + fill;
+            score = script_score<FW>(R, L, K, flags, true, T, space);
         }
     }
-    if (in && k < 3) q[3 * (size_t)row + k] = (float)score;
+    if (R.in && R.k < 3) q[3 * (size_t)R.row + R.k] = (float)score;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1613,58 +1685,26 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_pit_script(const uint8_t *__r
 // The rounds end when my front stops growing, and after NC of them at the latest.
 // ------------------------------------------------------------------------------------------
 template <int FW>
-__device__ __forceinline__ void script_grow(const uint64_t (&r)[FW], const uint64_t (&fr)[FW], const ScriptMasks &K, int WW,
-                                            uint64_t (&nx)[FW])
-{
-#pragma unroll
-    for (int w = 0; w < FW; ++w) {
-        const uint64_t below = w > 0 ? r[w > 0 ? w - 1 : 0] : 0ull, above = w < FW - 1 ? r[w < FW - 1 ? w + 1 : 0] : 0ull;
-        const uint64_t from_up = (r[w] << WW) | (below >> (64 - WW));         // cell c takes cell c - W
-        const uint64_t from_dn = (r[w] >> WW) | (above << (64 - WW));         // cell c takes cell c + W
-        const uint64_t from_lf = ((r[w] << 1) | (below >> 63)) & K.not_c0[w]; // cell c takes cell c - 1, not across a row end
-        const uint64_t from_rt = ((r[w] >> 1) | (above << 63)) & K.not_cl[w]; // cell c takes cell c + 1
-        nx[w] = (r[w] | from_up | from_dn | from_lf | from_rt) & fr[w];
-    }
-}
-
-template <int FW>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_pit_territory(const uint8_t *__restrict__ state, Layout L, int n_slots,
                                                                 const int32_t *__restrict__ pairs, int m, uint32_t flags,
                                                                 int hungry, ScriptMasks K, float *__restrict__ q)
 {
-    const int t = blockIdx.x * BLOCK_THREADS + threadIdx.x;
-    const int row = t >> 2, k = t & 3;
-    const bool in = row < m;
-    int g = -1, s = -1;
-    if (in) { g = pairs[2 * (size_t)row]; s = pairs[2 * (size_t)row + 1]; }
-    const bool pair_ok = in && g >= 0 && g < n_slots && s >= 0 && s < L.S;
-    const uint8_t *rec = state + (size_t)(pair_ok ? g : 0) * L.stride;
-    const SnakeMeta *meta = (const SnakeMeta *)(rec + L.meta_off);
-    SnakeMeta me = {0, 0, 0, 0, 0};
-    if (pair_ok) me = meta[s];
-    const bool ok = pair_ok && me.alive;
+    const ScriptRow R = script_row(state, L, n_slots, pairs, m);
     const bool fronts = (flags & SNK_SCRIPT_SPACE) != 0u;     // the same in every lane
     const int HH = L.H, WW = L.W;
-    const int len_s = me.len;
+    const int len_s = R.me.len;
 
     // ---- occupied as in k_pit_script; strong and weak: where the other alive snakes can stand after this tick (free or not)
     uint64_t occ[FW], strong[FW], weak[FW];
 #pragma unroll
     for (int w = 0; w < FW; ++w) occ[w] = strong[w] = weak[w] = 0ull;
-    if (ok) {
-        for (int o = k; o < L.S; o += 4) {
-            const SnakeMeta mo = meta[o];
+    if (R.ok) {
+        for (int o = R.k; o < L.S; o += 4) {
+            const SnakeMeta mo = R.meta[o];
             if (!mo.alive) continue;
-            const int len = (int)mo.len < L.cap ? (int)mo.len : L.cap;
-            for (int i = 0; i < len; ++i) {
-                const int c = script_ring_cell(rec, L, o, mo.tail + i);
-                if (c < L.NC) {
-#pragma unroll
-                    for (int w = 0; w < FW; ++w) occ[w] |= (c >> 6) == w ? 1ull << (c & 63) : 0ull;
-                }
-            }
-            if (!fronts || o == s) continue;
-            const int ho = script_ring_cell(rec, L, o, mo.tail + mo.len - 1);
+            script_mark_ring<FW>(R, L, o, mo, occ);
+            if (!fronts || o == R.s) continue;
+            const int ho = script_ring_cell(R.rec, L, o, mo.tail + mo.len - 1);
             const int oy = ho / WW, ox = ho - oy * WW;
             const bool is_strong = (int)mo.len >= len_s;
 #pragma unroll
@@ -1682,43 +1722,24 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_pit_territory(const uint8_t *
             }
         }
     }
-#define QUAD_OR(plane)                                                                                  \
-    _Pragma("unroll") for (int w = 0; w < FW; ++w) {                                                    \
-        int lo = (int)(uint32_t)plane[w], hi = (int)(uint32_t)(plane[w] >> 32);                         \
-        lo |= __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xF, 0xF, true);      /* quad_perm [1,0,3,2] */  \
-        hi |= __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xF, 0xF, true);                                 \
-        lo |= __builtin_amdgcn_update_dpp(0, lo, 0x4E, 0xF, 0xF, true);      /* quad_perm [2,3,0,1] */  \
-        hi |= __builtin_amdgcn_update_dpp(0, hi, 0x4E, 0xF, 0xF, true);                                 \
-        plane[w] = ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;                                       \
-    }
-    QUAD_OR(occ)                                      // all 64 lanes are here: the quad's four partial planes become one
+    quad_or<FW>(occ);                                 // all 64 lanes are here: the quad's four partial planes become one
     if (fronts) {
-        QUAD_OR(strong)
-        QUAD_OR(weak)
+        quad_or<FW>(strong);
+        quad_or<FW>(weak);
     }
-#undef QUAD_OR
 
     // ---- lane k < 3 scores relative move k
     int score = -1;
-    if (ok && k < 3) {
-        const int hc = script_ring_cell(rec, L, s, me.tail + len_s - 1);
-        const int d = (k + me.dir + 3) & 3;                   // k_step's heading: 0 = y-1, 1 = x+1, 2 = y+1, 3 = x-1
-        int y = hc / WW, x = hc - y * WW;
-        y += (d == 2) - (d == 0);
-        x += (d == 1) - (d == 3);
-        const bool oob = (y < 0) | (y >= HH) | (x < 0) | (x >= WW);
-        const int tc = oob ? 0 : y * WW + x;
-        bool blocked = oob;
-#pragma unroll
-        for (int w = 0; w < FW; ++w) blocked |= (tc >> 6) == w && ((occ[w] >> (tc & 63)) & 1ull);
-        if (!blocked) {
+    if (R.ok && R.k < 3) {
+        const ScriptTarget T = script_target<FW>(R, L, occ);
+        if (!T.blocked) {
             int territory = 0;
             if (fronts) {
                 uint64_t fr[FW], mine[FW], their[FW], nx[FW];
 #pragma unroll
                 for (int w = 0; w < FW; ++w) {
                     fr[w] = ~occ[w] & K.valid[w];
-                    mine[w] = (tc >> 6) == w ? 1ull << (tc & 63) : 0ull;          // the target is free
+                    mine[w] = (T.tc >> 6) == w ? 1ull << (T.tc & 63) : 0ull;      // the target is free
                     strong[w] &= fr[w];
                     territory += __popcll(mine[w] & ~strong[w]);                  // round 0: no weak front yet
                 }
@@ -1741,41 +1762,10 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_pit_territory(const uint8_t *
                     for (int w = 0; w < FW; ++w) their[w] = nx[w];
                 }
             }
-            int safe = 1;
-            if (flags & SNK_SCRIPT_HEADS) {
-                for (int o = 0; o < L.S; ++o) {
-                    if (o == s) continue;
-                    const SnakeMeta mo = meta[o];
-                    if (!mo.alive || (int)mo.len < len_s) continue;
-                    const int ho = script_ring_cell(rec, L, o, mo.tail + mo.len - 1);
-                    const int oy = ho / WW, ox = ho - oy * WW;
-                    if (abs(oy - y) + abs(ox - x) == 1) safe = 0;
-                }
-            }
-            int food = 0;
-            if ((flags & SNK_SCRIPT_FOOD) && (int)me.health <= hungry) {
-                const uint64_t *fw = (const uint64_t *)(rec + L.food_off);
-                int best = 1 << 20;
-#pragma unroll
-                for (int w = 0; w < FW; ++w) {
-                    uint64_t f = fw[w < L.FW ? w : 0] & K.valid[w];          // valid[] is 0 from the layout's word count up
-                    while (f) {                                              // one set bit less per pass: at most 64
-                        const int c = w * 64 + __builtin_ctzll(f);
-                        f &= f - 1ull;
-                        const int fy = c / WW, fx = c - fy * WW;
-                        const int dist = abs(fy - y) + abs(fx - x);
-                        best = dist < best ? dist : best;
-                    }
-                }
-                if (best != (1 << 20)) food = HH + WW - best;
-            }
-            int room = territory < len_s ? territory : len_s;
-            room = room < 255 ? room : 255;
-            const int fill = territory < 511 ? territory : 511;
-            score = ((room * 2 + safe) * 64 + food) * 512 + fill;
+            score = script_score<FW>(R, L, K, flags, (int)R.me.health <= hungry, T, territory);
         }
     }
-    if (in && k < 3) q[3 * (size_t)row + k] = (float)score;
+    if (R.in && R.k < 3) q[3 * (size_t)R.row + R.k] = (float)score;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1950,15 +1940,6 @@ static DeepScratch deep_scratch(long m, int S, int F, int depth)
     return P;
 }
 
-// bit s = snake s of a record is alive
-__device__ static inline uint32_t deep_alive_bits(const uint8_t *__restrict__ state, const Layout &L, int slot)
-{
-    const SnakeMeta *meta = (const SnakeMeta *)(state + (size_t)slot * L.stride + L.meta_off);
-    uint32_t bits = 0u;
-    for (int s = 0; s < L.S; ++s) bits |= (meta[s].alive ? 1u : 0u) << s;
-    return bits;
-}
-
 // thread t < n_nodes is node t of a level: child j = t % F of parent p = t / F.  par_state == nullptr: level 1, the parent is
 // group p and grp_bits[p] its alive bits (0 for a group that is not looked ahead).  Otherwise the parent is slot p of the
 // sub-engine above, after its step: a parent that was not active, or in which the game is over, has no children
@@ -1972,7 +1953,7 @@ __global__ __launch_bounds__(CMP_THREADS) void k_deep_fan(int n_nodes, int F, co
     const int p = t / F, j = t - p * F;
     uint32_t bits = 0u;
     if (par_state == nullptr) bits = (uint32_t)grp_bits[p];
-    else if (p < par_slots && par_active[p]) bits = deep_alive_bits(par_state, L, p);
+    else if (p < par_slots && par_active[p]) bits = slot_alive_bits(par_state, L, p);
     const int A = __popc(bits);
     const bool act = A >= 2 && A <= 4 && j < look_pow3(A);
     active[t] = act ? 1 : 0;
@@ -2038,7 +2019,7 @@ __global__ __launch_bounds__(CMP_THREADS) void k_deep_reduce(const uint8_t *__re
             if (par_state == nullptr) bits = (uint32_t)grp_bits[grp];
             else {
                 par = grp * P + pi;
-                if (par < par_slots && par_active[par]) bits = deep_alive_bits(par_state, L, par);
+                if (par < par_slots && par_active[par]) bits = slot_alive_bits(par_state, L, par);
             }
         }
         const int A = __popc(bits);
@@ -2154,7 +2135,7 @@ __global__ __launch_bounds__(CMP_THREADS) void k_play_plan(const uint8_t *__rest
     const int g = pairs[2 * (size_t)row], s = pairs[2 * (size_t)row + 1];
     bool play = false;
     if (g >= 0 && g < n_slots && s >= 0 && s < L.S && c < sub_slots) {
-        const uint32_t bits = deep_alive_bits(state, L, g);
+        const uint32_t bits = slot_alive_bits(state, L, g);
         play = ((bits >> s) & 1u) && __popc(bits) >= 2 && fb_q[3 * (size_t)row + a] != -1.0f;
     }
     src[c] = play ? g : 0;
@@ -2182,7 +2163,7 @@ __global__ __launch_bounds__(CMP_THREADS) void k_play_pick(const uint8_t *__rest
     if (fate[c] != PL_RUN) { active[c] = 0; return; }
     const int row = c / (3 * P), a = (c - row * 3 * P) / P, p = c - (row * 3 + a) * P;
     const int g = pairs[2 * (size_t)row], s = pairs[2 * (size_t)row + 1];          // in range: the plan played the clone
-    const uint32_t bits = deep_alive_bits(sub_state, L, c);                        // c < the sub-engine's n_slots, as above
+    const uint32_t bits = slot_alive_bits(sub_state, L, c);                        // c < the sub-engine's n_slots, as above
     if (tick > 0) {
         const int v = play_settle(bits, s, tick - 1, T);
         if (v != PL_RUN) { fate[c] = v; active[c] = 0; return; }
@@ -2231,7 +2212,7 @@ __global__ __launch_bounds__(CMP_THREADS) void k_play_fold(const uint8_t *__rest
         for (int p = 0; p < P; ++p) {
             int v = fate[base + p];
             if (v == PL_RUN) {
-                v = play_settle(deep_alive_bits(sub_state, L, base + p), s, T - 1, T);
+                v = play_settle(slot_alive_bits(sub_state, L, base + p), s, T - 1, T);
                 if (v == PL_RUN) v = T;
             }
             sum += v;

@@ -1,5 +1,5 @@
 """Test infrastructure: the CPU statement of the deep opponent (snake_engine.arena.Deep, snk_pit_deep_values) in plain Python, built
-on tests/look_ref.py (the children, the depth-1 scores) and tests/script_ref.py (the plain scores), and a match player.
+on tests/look_ref.py (the children, the depth-1 scores, the fold) and tests/script_ref.py (the plain scores, the match player).
 
 The policy (include/snake_engine.h), for snake s of a board with A snakes alive, V_k = the three scores of a search k ticks deep:
 
@@ -19,7 +19,6 @@ import league_ref as LR
 import look_ref as K
 import script_ref as R
 import search_pit_ref as SR
-from oracle.mcts_oracle import argmaxs
 
 WIN = K.WIN
 STEP_PENALTY = 32                                   # a death one tick earlier costs this much: above the 27 ways to die of a tick
@@ -35,33 +34,24 @@ def fanout(S, depth):
     return F if 2 <= S <= 8 and depth >= 1 and F <= 6561 else -1
 
 
-def board_deep_scores(H, W, S, health_dec, st, depth, flags=R.ALL):
-    """{s: the three scores of a search `depth` ticks deep} of every alive snake of a compact board"""
+def board_deep_scores(H, W, S, health_dec, st, depth, flags=R.ALL, score=R.board_scores, only=None):
+    """{s: the three scores of a search `depth` ticks deep} of the alive snakes of a compact board (only: of those ids), the rows
+    scored by the row-scoring function `score` as in look_ref.board_look_scores"""
     assert depth >= 1
     A = int(np.count_nonzero(st["alive"][:S]))
-    if A < 2 or A > 4:
-        return R.board_scores(H, W, st, flags)
-    if depth == 1:
-        return K.board_look_scores(H, W, S, health_dec, st, flags)
+    if depth == 1 or A < 2 or A > 4:                # the fallback is the lookahead's
+        return K.board_look_scores(H, W, S, health_dec, st, flags, score, only)
     children, alive = K.child_boards(H, W, S, health_dec, st)
     leaf = []
     for c in children:
         left = [s for s in alive if c["alive"][s]]
-        if len(left) >= 2:                          # 2 .. A alive: never the fallback
-            below = board_deep_scores(H, W, S, health_dec, c, depth - 1, flags)
-            leaf.append({s: max(below[s]) for s in left})
+        mine = [s for s in left if only is None or s in only]
+        if len(left) >= 2 and mine:                 # 2 .. A alive: never the fallback
+            below = board_deep_scores(H, W, S, health_dec, c, depth - 1, flags, score, mine)
+            leaf.append({s: max(below[s]) for s in mine})
         else:
-            leaf.append({s: WIN for s in left})
-    out = {}
-    for k, s in enumerate(alive):
-        q = []
-        for a in range(3):
-            mine = [lf for j, lf in enumerate(leaf) if (j // 3 ** k) % 3 == a]
-            assert len(mine) == 3 ** (len(alive) - 1)
-            dead = sum(s not in lf for lf in mine)
-            q.append(-2 - dead - STEP_PENALTY * (depth - 1) if dead else min(lf[s] for lf in mine))
-        out[s] = q
-    return out
+            leaf.append({s: WIN for s in mine})
+    return K.fold(leaf, alive, only, -2 - STEP_PENALTY * (depth - 1))
 
 
 def deep_scores(H, W, S, health_dec, st, s, depth, flags=R.ALL):
@@ -72,69 +62,11 @@ def deep_scores(H, W, S, health_dec, st, s, depth, flags=R.ALL):
 
 
 class RefDeep(R.RefScripted):
-    """the statement's side of a match: what snake_engine.arena.Deep(flags, depth) is on the device"""
+    """the statement's side of a match: what snake_engine.arena.Deep(flags, depth, leaf) is on the device"""
 
-    def __init__(self, depth=2, flags=R.ALL):
+    def __init__(self, depth=2, flags=R.ALL, leaf=None):
         super().__init__(flags)
-        self.depth = depth
-
-
-def side_scores(side, H, W, S, health_dec, st):
-    """{s: three scores} of a board for a scripted side of any of the three kinds"""
-    if isinstance(side, RefDeep):
-        return board_deep_scores(H, W, S, health_dec, st, side.depth, side.flags)
-    if isinstance(side, K.RefLookahead):
-        return K.board_look_scores(H, W, S, health_dec, st, side.flags)
-    return R.board_scores(H, W, st, side.flags)
-
-
-# ---- the match player -------------------------------------------------------------------------------------------------------------
-def deep_run(games, sides, owner, spawn_seed, max_turns=None):
-    """look_ref.look_run with RefDeep among the sides and an optional turn cap: the games still open after max_turns turns stay
-    as they stand, without a winner.  Returns what look_run returns, and open = the games still open"""
-    S, K_ = games[0].g.S, len(sides)
-    H, W, hd = games[0].g.H, games[0].g.W, games[0].g.health_dec
-    owner = np.asarray(owner)
-    assert owner.shape == (len(games), S) and owner.min() >= 0 and owner.max() < K_
-    rng = np.random.RandomState(spawn_seed)
-    winners, lengths = [None] * len(games), [0] * len(games)
-    live = list(range(len(games)))
-    counts, spawn_log, turn = [], [], 0
-    while live and (max_turns is None or turn < max_turns):
-        turn += 1
-        dense = {g: np.ones(S, np.uint8) for g in live}
-        rows_of = []
-        for o in range(K_):
-            ids = [(g, s) for g in live for s in games[g].alive_ids() if owner[g][s] == o]
-            rows_of.append(len(ids))
-            if isinstance(sides[o], R.RefScripted):
-                for g in sorted({g for g, _ in ids}):
-                    q = side_scores(sides[o], H, W, S, hd, games[g].compact())
-                    for s in (s for gg, s in ids if gg == g):
-                        dense[g][s] = R.move(q[s])
-            elif ids:
-                for (g, s), m in zip(ids, argmaxs(sides[o].v([games[g].make_state(s) for g, s in ids]))):
-                    dense[g][s] = m
-        counts.append(rows_of)
-        spawn_log.append(np.full(len(games), -2, np.int16))
-        nxt = []
-        for g in live:
-            done = games[g].tic(dense[g], draws=(rng.random_sample(), rng.random_sample()))
-            spawn_log[-1][g] = games[g].last_spawn
-            lengths[g] += 1
-            if done:                                                        # pit_mp_game_runner.py:43-47
-                for i, r in enumerate(games[g].rewards):
-                    if r == 1.0:
-                        winners[g] = i
-            else:                                                           # :48-60 with a team read as an owner
-                ids = games[g].alive_ids()
-                if len({int(owner[g][s]) for s in ids}) <= 1:
-                    winners[g] = ids[0] if ids else None
-                else:
-                    nxt.append(g)
-        live = nxt
-    return dict(winners=winners, winner_owner=[None if w is None else int(owner[g][w]) for g, w in enumerate(winners)],
-                lengths=lengths, turns=turn, counts=counts, spawn_log=spawn_log, boards=[g.compact() for g in games], open=live)
+        self.depth, self.leaf = depth, leaf
 
 
 # ---- what the tests share -------------------------------------------------------------------------------------------------------------
@@ -173,14 +105,13 @@ def reference(name):
     """the statement's run of one of the matches, computed once and shared (callers must not change it)"""
     if name == "duel-7x7x2":                      # Deep(depth=2) against Lookahead(), one snake each, sixteen recorded start boards
         games, geo = SR.start_games("7x7x2", N_DUEL)
-        out = deep_run(games, [RefDeep(2), K.RefLookahead()], LR.two_team_table(N_DUEL, 2, 1), SPAWN_SEED)
+        out = R.run(games, [RefDeep(2), K.RefLookahead()], LR.two_team_table(N_DUEL, 2, 1), SPAWN_SEED, R.NO_CAP)
     elif name == "1v3-11x11x4":                   # one Deep(depth=2) against three snakes of Scripted(), cut at CAP_FOUR turns
         games, geo = SR.start_games("11x11x4", N_FOUR)
-        out = deep_run(games, [RefDeep(2), R.RefScripted()], LR.two_team_table(N_FOUR, 4, 1), SPAWN_SEED, CAP_FOUR)
+        out = R.run(games, [RefDeep(2), R.RefScripted()], LR.two_team_table(N_FOUR, 4, 1), SPAWN_SEED, CAP_FOUR)
     else:                                         # a deep owner, a scripted owner and stub net 0, cut at CAP_LEAGUE turns
         assert name == "league-11x11x4"
         games, geo = SR.start_games("11x11x4", N_LEAGUE)
-        out = deep_run(games, [RefDeep(2), R.RefScripted(R.SPACE), LR.RefStub(0)], R.three_owner_table(N_LEAGUE), SPAWN_SEED,
-                       CAP_LEAGUE)
+        out = R.run(games, [RefDeep(2), R.RefScripted(R.SPACE), LR.RefStub(0)], R.three_owner_table(N_LEAGUE), SPAWN_SEED, CAP_LEAGUE)
     out["geometry"] = geo
     return out

@@ -1,6 +1,6 @@
 """Test infrastructure: the CPU statement of the playout opponent (snake_engine.arena.Playout, snk_pit_playout_values) in plain
 Python, built on tests/script_ref.py (the plain scores, snk_pit_moves' tie order), the stepper of tests/look_ref.py (Game.subgame
-and Game.tic of the C game of oracle/, no food spawning) and the Philox of tests/mcts_ref.py, and a match player.
+and Game.tic of the C game of oracle/, no food spawning) and the Philox of tests/mcts_ref.py; script_ref.run plays it in matches.
 
 The policy (include/snake_engine.h), for snake s of the board in slot g with A snakes alive, P playouts, horizon T, exploration eps
 and a 64-bit seed:
@@ -20,14 +20,12 @@ import functools
 
 import numpy as np
 
-import deep_ref as D
 import league_ref as LR
 import look_ref as K
 import script_ref as R
 import search_pit_ref as SR
 from mcts_ref import philox4x32_10
 from oracle import snake_oracle
-from oracle.mcts_oracle import argmaxs
 
 TAG = 0x504C4159                                    # counter word 3 of every playout draw
 MAX_P, MAX_T, MAX_EPS = 64, 64, 256
@@ -46,16 +44,16 @@ def playout_move(q, r, eps):
     return R.move(q)
 
 
-def playout_value(root, g, s, a, p, T, eps, seed, flags):
-    """the value of playout (a, p) of snake s of the oracle game `root` in slot g; root is not changed"""
+def playout_value(root, g, s, a, p, T, eps, seed, flags, score=R.board_scores):
+    """the value of playout (a, p) of snake s of the oracle game `root` in slot g, every snake's playout move taken from the
+    row-scoring function `score`; root is not changed"""
     c = root.subgame()
     S, H, W = c.g.S, c.g.H, c.g.W
     key = (seed & 0xFFFFFFFF, seed >> 32)
     for i in range(T):
         alive = c.alive_ids()
         assert s in alive and len(alive) >= 2
-        st = c.compact()
-        q = R.board_scores(H, W, st, flags)
+        q = score(H, W, c.compact(), flags)
         r = philox4x32_10((g, [s | a << 4 | t << 8 for t in alive], p | i << 8, TAG), key)
         moves = np.ones(S, np.uint8)
         for k, t in enumerate(alive):
@@ -70,18 +68,19 @@ def playout_value(root, g, s, a, p, T, eps, seed, flags):
     return T
 
 
-def board_playout_scores(H, W, S, health_dec, st, g, P, T, eps=64, seed=0, flags=R.ALL, only=None):
-    """{s: the three playout scores} of the alive snakes of the compact board st standing in slot g (only: of those ids)"""
+def board_playout_scores(H, W, S, health_dec, st, g, P, T, eps=64, seed=0, flags=R.ALL, score=R.board_scores, only=None):
+    """{s: the three playout scores} of the alive snakes of the compact board st standing in slot g (only: of those ids), the
+    plain scores those of the row-scoring function `score` (script_ref.board_scores, or leaf_ref.scorer of a leaf)"""
     assert 1 <= P <= MAX_P and 1 <= T <= MAX_T and 0 <= eps <= MAX_EPS and 0 <= seed < 1 << 64
-    plain = R.board_scores(H, W, st, flags)
+    plain = score(H, W, st, flags)
     if len(plain) < 2:
-        return plain
+        return plain if only is None else {s: z for s, z in plain.items() if s in only}
     root = snake_oracle.Game.from_compact(H, W, S, health_dec, 0.15, st)
     out = {}
     for s in plain if only is None else [s for s in only if s in plain]:
         z = plain[s]
         out[s] = [-1 if z[a] == -1 else
-                  4 * sum(playout_value(root, g, s, a, p, T, eps, seed, flags) for p in range(P)) + sum(z[b] < z[a] for b in range(3) if b != a)
+                  4 * sum(playout_value(root, g, s, a, p, T, eps, seed, flags, score) for p in range(P)) + sum(z[b] < z[a] for b in range(3) if b != a)
                   for a in range(3)]
     return out
 
@@ -94,67 +93,11 @@ def playout_scores(H, W, S, health_dec, st, g, s, P, T, eps=64, seed=0, flags=R.
 
 
 class RefPlayout(R.RefScripted):
-    """the statement's side of a match: what snake_engine.arena.Playout(flags, P, T, eps, seed) is on the device"""
+    """the statement's side of a match: what snake_engine.arena.Playout(flags, P, T, eps, seed, leaf) is on the device"""
 
-    def __init__(self, P=8, T=8, eps=64, seed=0, flags=R.ALL):
+    def __init__(self, P=8, T=8, eps=64, seed=0, flags=R.ALL, leaf=None):
         super().__init__(flags)
-        self.P, self.T, self.eps, self.seed = P, T, eps, seed
-
-
-def side_scores(side, H, W, S, health_dec, st, g, only=None):
-    """{s: three scores} of the board in slot g for a scripted side of any of the four kinds"""
-    if isinstance(side, RefPlayout):
-        return board_playout_scores(H, W, S, health_dec, st, g, side.P, side.T, side.eps, side.seed, side.flags, only)
-    return D.side_scores(side, H, W, S, health_dec, st)
-
-
-# ---- the match player -------------------------------------------------------------------------------------------------------------
-def playout_run(games, sides, owner, spawn_seed, max_turns=None):
-    """deep_ref.deep_run with RefPlayout among the sides (a game's slot is its index).  Returns what deep_run returns"""
-    S, K_ = games[0].g.S, len(sides)
-    H, W, hd = games[0].g.H, games[0].g.W, games[0].g.health_dec
-    owner = np.asarray(owner)
-    assert owner.shape == (len(games), S) and owner.min() >= 0 and owner.max() < K_
-    rng = np.random.RandomState(spawn_seed)
-    winners, lengths = [None] * len(games), [0] * len(games)
-    live = list(range(len(games)))
-    counts, spawn_log, turn = [], [], 0
-    while live and (max_turns is None or turn < max_turns):
-        turn += 1
-        dense = {g: np.ones(S, np.uint8) for g in live}
-        rows_of = []
-        for o in range(K_):
-            ids = [(g, s) for g in live for s in games[g].alive_ids() if owner[g][s] == o]
-            rows_of.append(len(ids))
-            if isinstance(sides[o], R.RefScripted):
-                for g in sorted({g for g, _ in ids}):
-                    mine = [s for gg, s in ids if gg == g]
-                    q = side_scores(sides[o], H, W, S, hd, games[g].compact(), g, mine)
-                    for s in mine:
-                        dense[g][s] = R.move(q[s])
-            elif ids:
-                for (g, s), m in zip(ids, argmaxs(sides[o].v([games[g].make_state(s) for g, s in ids]))):
-                    dense[g][s] = m
-        counts.append(rows_of)
-        spawn_log.append(np.full(len(games), -2, np.int16))
-        nxt = []
-        for g in live:
-            done = games[g].tic(dense[g], draws=(rng.random_sample(), rng.random_sample()))
-            spawn_log[-1][g] = games[g].last_spawn
-            lengths[g] += 1
-            if done:                                                        # pit_mp_game_runner.py:43-47
-                for i, r in enumerate(games[g].rewards):
-                    if r == 1.0:
-                        winners[g] = i
-            else:                                                           # :48-60 with a team read as an owner
-                ids = games[g].alive_ids()
-                if len({int(owner[g][s]) for s in ids}) <= 1:
-                    winners[g] = ids[0] if ids else None
-                else:
-                    nxt.append(g)
-        live = nxt
-    return dict(winners=winners, winner_owner=[None if w is None else int(owner[g][w]) for g, w in enumerate(winners)],
-                lengths=lengths, turns=turn, counts=counts, spawn_log=spawn_log, boards=[g.compact() for g in games], open=live)
+        self.P, self.T, self.eps, self.seed, self.leaf = P, T, eps, seed, leaf
 
 
 # ---- what the tests share -------------------------------------------------------------------------------------------------------------
@@ -226,17 +169,17 @@ def reference(name):
     """the statement's run of one of the matches, computed once and shared (callers must not change it)"""
     if name == "duel-7x7x2":                      # Playout(P=2, T=3) against Scripted(), one snake each, sixteen recorded start boards
         games, geo = SR.start_games("7x7x2", N_DUEL)
-        out = playout_run(games, [RefPlayout(MATCH_P, MATCH_T), R.RefScripted()], LR.two_team_table(N_DUEL, 2, 1), SPAWN_SEED)
+        out = R.run(games, [RefPlayout(MATCH_P, MATCH_T), R.RefScripted()], LR.two_team_table(N_DUEL, 2, 1), SPAWN_SEED, R.NO_CAP)
     elif name == "strength-7x7x2":                # the reading of DESIGN section 7: RefPlayout(P=4, T=6) against RefScripted()
         games, geo = SR.start_games("7x7x2", N_DUEL)
-        out = playout_run(games, [RefPlayout(4, 6), R.RefScripted()], LR.two_team_table(N_DUEL, 2, 1), SPAWN_SEED)
+        out = R.run(games, [RefPlayout(4, 6), R.RefScripted()], LR.two_team_table(N_DUEL, 2, 1), SPAWN_SEED, R.NO_CAP)
     elif name == "1v3-11x11x4":                   # one Playout against three snakes of Scripted(), cut at CAP_FOUR turns
         games, geo = SR.start_games("11x11x4", N_FOUR)
-        out = playout_run(games, [RefPlayout(MATCH_P, MATCH_T), R.RefScripted()], LR.two_team_table(N_FOUR, 4, 1), SPAWN_SEED, CAP_FOUR)
+        out = R.run(games, [RefPlayout(MATCH_P, MATCH_T), R.RefScripted()], LR.two_team_table(N_FOUR, 4, 1), SPAWN_SEED, CAP_FOUR)
     else:                                         # a playout owner, a lookahead owner and a scripted owner, cut at CAP_LEAGUE turns
         assert name == "league-11x11x4"
         games, geo = SR.start_games("11x11x4", N_LEAGUE)
-        out = playout_run(games, [RefPlayout(MATCH_P, MATCH_T, seed=9), K.RefLookahead(), R.RefScripted(R.SPACE)],
-                          R.three_owner_table(N_LEAGUE), SPAWN_SEED, CAP_LEAGUE)
+        out = R.run(games, [RefPlayout(MATCH_P, MATCH_T, seed=9), K.RefLookahead(), R.RefScripted(R.SPACE)],
+                    R.three_owner_table(N_LEAGUE), SPAWN_SEED, CAP_LEAGUE)
     out["geometry"] = geo
     return out

@@ -83,12 +83,13 @@ def region_sizes(H, W, occupied):
     return sizes
 
 
-def board_scores(H, W, st, flags=ALL):
-    """{s: scores(H, W, st, s, flags)} of every alive snake of a board, its regions flooded once"""
+def board_scores(H, W, st, flags=ALL, only=None):
+    """{s: scores(H, W, st, s, flags)} of every alive snake of a board (only: of those ids), its regions flooded once.  This is
+    the form of a row-scoring function: what the searches of look_ref, deep_ref and playout_ref take as `score`"""
     alive = [t for t in range(len(st["alive"])) if st["alive"][t]]
     occupied = {int(c) for t in alive for c in st["nodes"][t][:int(st["length"][t])]}
     sizes = region_sizes(H, W, occupied) if flags & SPACE else None
-    return {s: scores(H, W, st, s, flags, sizes) for s in alive}
+    return {s: scores(H, W, st, s, flags, sizes) for s in alive if only is None or s in only}
 
 
 def scores(H, W, st, s, flags=ALL, sizes=None):
@@ -138,24 +139,31 @@ class RefScripted:
 
 
 # ---- the match player -------------------------------------------------------------------------------------------------------------
-def script_run(games, sides, owner, spawn_seed, searching=None, tapes=None, depth=4, breadth=8, base=100):
-    """league_ref.league_run / league_search_ref.league_search_run with scripted owners: sides[o] is a RefScripted or a net
-    with .v; searching[o]: owner o (a net) moves by search with the uniform tape tapes[o].  A scripted owner counts as a greedy
+NO_CAP = float("inf")                               # a turn cap that never cuts: the result still says which games are open
+
+
+def run(games, sides, owner, spawn_seed, max_turns=None, log_moves=False, searching=None, tapes=None, depth=4, breadth=8, base=100):
+    """the match player of every scripted statement: league_ref.league_run / league_search_ref.league_search_run with scripted
+    owners.  sides[o] is a RefScripted of any kind (its moves are `move` of leaf_ref.side_scores; a game's slot is its index) or a
+    net with .v; searching[o]: owner o (a net) moves by search with the uniform tape tapes[o].  A scripted owner counts as a greedy
     one.  Food from RandomState(spawn_seed), two uniforms per open game and turn in game order.  Returns a dict: winners (None for
     a draw), winner_owner, lengths, turns, counts [turn - 1] (without a searcher the K row counts; with one the greedy owners' row
-    counts in owner order, then the K counts of games per owner), spawn_log, boards, tape_pos"""
+    counts in owner order, then the K counts of games per owner), spawn_log, boards; and
+        max_turns   (a turn cap; NO_CAP for none) open: the games still open after it, which stay as they stand, without a winner
+        log_moves   moves [turn - 1] = {game: the dense moves of the turn}
+        searching   tape_pos [o] = how far owner o's tape was read, None for an owner that does not search"""
+    from leaf_ref import side_scores                # the module that sees every player class; it imports this one
     S, K = games[0].g.S, len(sides)
-    H, W = games[0].g.H, games[0].g.W
+    H, W, hd = games[0].g.H, games[0].g.W, games[0].g.health_dec
     owner = np.asarray(owner)
     assert owner.shape == (len(games), S) and owner.min() >= 0 and owner.max() < K
-    searching = [False] * K if searching is None else list(searching)
     rng = np.random.RandomState(spawn_seed)
     oracles = [SelfPlayOracle(side, base, False, depth, breadth, draws=SR.CheckedDraws(tapes[o])) if s else None
-               for o, (side, s) in enumerate(zip(sides, searching))]
+               for o, (side, s) in enumerate(zip(sides, searching or [False] * K))]
     winners, lengths = [None] * len(games), [0] * len(games)
     live = list(range(len(games)))
-    counts, spawn_log, turn = [], [], 0
-    while live:
+    counts, spawn_log, moves_log, turn = [], [], [], 0
+    while live and (max_turns is None or turn < max_turns):
         turn += 1
         dense = {g: np.ones(S, np.uint8) for g in live}
         rows_of, games_of = [], [0] * K
@@ -172,13 +180,16 @@ def script_run(games, sides, owner, spawn_seed, searching=None, tapes=None, dept
             ids = [(g, s) for g in live for s in games[g].alive_ids() if owner[g][s] == o]
             rows_of.append(len(ids))
             if isinstance(sides[o], RefScripted):
-                boards = {g: games[g].compact() for g in {g for g, _ in ids}}
-                for g, s in ids:
-                    dense[g][s] = move(scores(H, W, boards[g], s, sides[o].flags))
+                for g in sorted({g for g, _ in ids}):
+                    mine = [s for gg, s in ids if gg == g]
+                    q = side_scores(sides[o], H, W, S, hd, games[g].compact(), g, mine)
+                    for s in mine:
+                        dense[g][s] = move(q[s])
             elif ids:
                 for (g, s), m in zip(ids, argmaxs(sides[o].v([games[g].make_state(s) for g, s in ids]))):
                     dense[g][s] = m
-        counts.append(rows_of + games_of if any(searching) else rows_of)
+        counts.append(rows_of + games_of if searching and any(searching) else rows_of)
+        moves_log.append(dense)
         spawn_log.append(np.full(len(games), -2, np.int16))
         nxt = []
         for g in live:
@@ -196,9 +207,20 @@ def script_run(games, sides, owner, spawn_seed, searching=None, tapes=None, dept
                 else:
                     nxt.append(g)
         live = nxt
-    return dict(winners=winners, winner_owner=[None if w is None else int(owner[g][w]) for g, w in enumerate(winners)],
-                lengths=lengths, turns=turn, counts=counts, spawn_log=spawn_log, boards=[g.compact() for g in games],
-                tape_pos=[None if o is None else o.draw.pos for o in oracles])
+    out = dict(winners=winners, winner_owner=[None if w is None else int(owner[g][w]) for g, w in enumerate(winners)],
+               lengths=lengths, turns=turn, counts=counts, spawn_log=spawn_log, boards=[g.compact() for g in games])
+    if max_turns is not None:
+        out["open"] = live
+    if log_moves:
+        out["moves"] = moves_log
+    if searching is not None:
+        out["tape_pos"] = [None if o is None else o.draw.pos for o in oracles]
+    return out
+
+
+def script_run(games, sides, owner, spawn_seed, searching=None, **search):
+    """run with searching owners, or with none of them: it returns tape_pos either way"""
+    return run(games, sides, owner, spawn_seed, searching=searching or [False] * len(sides), **search)
 
 
 # ---- the matches of the GPU test ---------------------------------------------------------------------------------------------------

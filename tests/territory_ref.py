@@ -1,5 +1,5 @@
 """Test infrastructure: the CPU statement of the territory opponent (snake_engine.arena.Territory, snk_pit_territory_values) in
-plain Python over the compact boards of tests/script_ref.py, and a match player built on it.
+plain Python over the compact boards of tests/script_ref.py, whose match player (script_ref.run) plays it.
 
 The policy (include/snake_engine.h), for snake s of a board and relative move a:
 
@@ -26,7 +26,6 @@ import league_ref as LR
 import script_ref as R
 import search_pit_ref as SR
 from conftest import golden_state, load_golden
-from oracle.mcts_oracle import argmaxs
 
 FAR = 1 << 30                                       # the distance of a cell a front never reaches
 
@@ -120,10 +119,12 @@ def scores(H, W, st, s, flags=R.ALL, hungry=100, their=None, terrs=None):
     return out
 
 
-def board_scores(H, W, st, flags=R.ALL, hungry=100):
-    """{s: scores(H, W, st, s, flags, hungry)} of every alive snake of a board, the other snakes' distances taken once"""
+def board_scores(H, W, st, flags=R.ALL, hungry=100, only=None):
+    """{s: scores(H, W, st, s, flags, hungry)} of every alive snake of a board (only: of those ids), the other snakes' distances
+    taken once"""
     their = fronts(H, W, st) if flags & R.SPACE else None
-    return {s: scores(H, W, st, s, flags, hungry, their) for s in range(len(st["alive"])) if st["alive"][s]}
+    return {s: scores(H, W, st, s, flags, hungry, their)
+            for s in range(len(st["alive"])) if st["alive"][s] and (only is None or s in only)}
 
 
 def parts(score):
@@ -137,58 +138,6 @@ class RefTerritory(R.RefScripted):
     def __init__(self, flags=R.ALL, hungry=100):
         super().__init__(flags)
         self.hungry = hungry
-
-
-# ---- the match player -------------------------------------------------------------------------------------------------------------
-def territory_run(games, sides, owner, spawn_seed):
-    """look_ref.look_run with RefTerritory among the sides: sides[o] is a RefTerritory, a RefScripted or a net with .v.  Returns
-    what look_run returns; counts [turn - 1] = the turn's K row counts"""
-    S, K = games[0].g.S, len(sides)
-    H, W = games[0].g.H, games[0].g.W
-    owner = np.asarray(owner)
-    assert owner.shape == (len(games), S) and owner.min() >= 0 and owner.max() < K
-    rng = np.random.RandomState(spawn_seed)
-    winners, lengths = [None] * len(games), [0] * len(games)
-    live = list(range(len(games)))
-    counts, spawn_log, turn = [], [], 0
-    while live:
-        turn += 1
-        dense = {g: np.ones(S, np.uint8) for g in live}
-        rows_of = []
-        for o in range(K):
-            ids = [(g, s) for g in live for s in games[g].alive_ids() if owner[g][s] == o]
-            rows_of.append(len(ids))
-            side = sides[o]
-            if isinstance(side, R.RefScripted):
-                for g in sorted({g for g, _ in ids}):
-                    st = games[g].compact()
-                    q = (board_scores(H, W, st, side.flags, side.hungry) if isinstance(side, RefTerritory)
-                         else R.board_scores(H, W, st, side.flags))
-                    for s in (s for gg, s in ids if gg == g):
-                        dense[g][s] = R.move(q[s])
-            elif ids:
-                for (g, s), m in zip(ids, argmaxs(side.v([games[g].make_state(s) for g, s in ids]))):
-                    dense[g][s] = m
-        counts.append(rows_of)
-        spawn_log.append(np.full(len(games), -2, np.int16))
-        nxt = []
-        for g in live:
-            done = games[g].tic(dense[g], draws=(rng.random_sample(), rng.random_sample()))
-            spawn_log[-1][g] = games[g].last_spawn
-            lengths[g] += 1
-            if done:                                                        # pit_mp_game_runner.py:43-47
-                for i, r in enumerate(games[g].rewards):
-                    if r == 1.0:
-                        winners[g] = i
-            else:                                                           # :48-60 with a team read as an owner
-                ids = games[g].alive_ids()
-                if len({int(owner[g][s]) for s in ids}) <= 1:
-                    winners[g] = ids[0] if ids else None
-                else:
-                    nxt.append(g)
-        live = nxt
-    return dict(winners=winners, winner_owner=[None if w is None else int(owner[g][w]) for g, w in enumerate(winners)],
-                lengths=lengths, turns=turn, counts=counts, spawn_log=spawn_log, boards=[g.compact() for g in games])
 
 
 # ---- what the tests share: the golden boards, the statement over them and the matches of the GPU test ------------------------------
@@ -238,14 +187,14 @@ def reference(name):
     """the statement's run of one of the matches, computed once and shared (callers must not change it)"""
     if name == "duel-7x7x2":                      # Territory() against Scripted(), one snake each, sixteen recorded start boards
         games, geo = SR.start_games("7x7x2", N_DUEL)
-        out = territory_run(games, [RefTerritory(), R.RefScripted()], LR.two_team_table(N_DUEL, 2, 1), SPAWN_SEED)
+        out = R.run(games, [RefTerritory(), R.RefScripted()], LR.two_team_table(N_DUEL, 2, 1), SPAWN_SEED)
     elif name == "1v3-11x11x4":                   # one Territory(hungry=40) against three snakes of Scripted(HEADS)
         games, geo = SR.start_games("11x11x4", N_FOUR)
-        out = territory_run(games, [RefTerritory(hungry=HUNGRY_FOUR), R.RefScripted(R.HEADS)], LR.two_team_table(N_FOUR, 4, 1),
+        out = R.run(games, [RefTerritory(hungry=HUNGRY_FOUR), R.RefScripted(R.HEADS)], LR.two_team_table(N_FOUR, 4, 1),
                             SPAWN_SEED)
     else:                                         # a territory owner, a scripted owner and stub net 0
         assert name == "league-11x11x4"
         games, geo = SR.start_games("11x11x4", N_LEAGUE)
-        out = territory_run(games, [RefTerritory(), R.RefScripted(), LR.RefStub(0)], R.three_owner_table(N_LEAGUE), SPAWN_SEED)
+        out = R.run(games, [RefTerritory(), R.RefScripted(), LR.RefStub(0)], R.three_owner_table(N_LEAGUE), SPAWN_SEED)
     out["geometry"] = geo
     return out
