@@ -69,6 +69,7 @@ template <bool BF> __device__ __forceinline__ _Float16 hs_to16(float v)
 #else
 #define HS_SMEM (HS_SMEM_EPI > HS_SMEM_STAGE ? HS_SMEM_EPI : HS_SMEM_STAGE)
 #endif
+#define HS_ROWMAP (256 * 8)                              // the packed form's row map behind the block's LDS: 8 bytes per GEMM row (2 x 69 632 <= 160 KB per CU)
 #define HS_WS_ELEMS (9 * HS_C * HS_C * 2)                // f16 numbers in the split weight image; four floats follow it
 #define HS_RING 3
 #define HS_AHEAD 2
@@ -331,6 +332,24 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     const int ry_loB = RA + yaB - (ryB - 1), cx_loB = xaB - (rxB - 1), wsB = xbB - xaB + 1, npxB = nB > 0 ? (ybB - yaB + 1) * wsB : 0;
     const int byB0 = bboxB & 255, bxB0 = (bboxB >> 8) & 255, byB1 = (bboxB >> 16) & 255, bxB1 = bboxB >> 24;
     (void)nA; (void)RA; (void)ry_loB; (void)cx_loB; (void)npxB; (void)byB0; (void)bxB0; (void)byB1; (void)bxB1;
+    // PK: the epilogue's row map, once per block instead of once per lane: thread r writes the entry of GEMM row r behind the
+    // block's staging / exchange LDS (the chunk loop's barriers stand between this and the epilogue's reads) --
+    //   .x  the row's element offset in the tensors, its image included; -1 past the block's pixels
+    //   .y  where its shortcut value is: .x when the shortcut's producer computed the pixel (bounding box grown by grow_res), else
+    //       the pixel's offset in that producer's background image with bit 31 set; 0 past the block's pixels (read, never used)
+    if constexpr (PK) {
+        const int r_ = tid;
+        const bool sb_ = r_ >= nA;                         // row -> (segment, pixel) -> address in the segment's image
+        const int mm_ = sb_ ? r_ - nA : m0 + r_;
+        const int y_ = (int)(((float)mm_ + 0.5f) * invW), x_ = mm_ - y_ * Wr;
+        const int Y_ = (sb_ ? ryB : cy0) + y_, X_ = (sb_ ? rxB : cx0) + x_;
+        const bool in_ = r_ < nA + nB;
+        const int o_ = (((sb_ ? imgB : img) * p.Hd + Y_) * p.Wd + X_) * HS_C;
+        const bool stale_ = MODE == 2 && p.bg_res != nullptr &&
+                            (Y_ < (sb_ ? byB0 : by0) - p.grow_res || Y_ > (sb_ ? byB1 : by1) + p.grow_res ||
+                             X_ < (sb_ ? bxB0 : bx0) - p.grow_res || X_ > (sb_ ? bxB1 : bx1) + p.grow_res);
+        *(int2 *)(smem + HS_SMEM + 8 * r_) = make_int2(in_ ? o_ : -1, !in_ ? 0 : stale_ ? (int)(((unsigned)(Y_ * p.Wd + X_) * HS_C) | 0x80000000u) : o_);
+    }
     // items past the strip's last pixel repeat it (same value to the same LDS address): no predication, no branches
     if constexpr (PK) {
         const float invWsB = 1.0f / (float)wsB;
@@ -853,21 +872,19 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
     float4 rv[2][8];
     int off[2][8];
     bool res_stale[8];
+    int rsrc[8] = {};                                                    // PK: the rows' shortcut sources (the map's .y)
+    const float *resq = p.res + 4 * cq, *bgq = p.bg_res + 4 * cq;        // PK: this thread's channels in the shortcut tensor / its background image
+    (void)rsrc; (void)resq; (void)bgq;
     const bool sel_res = RECT && p.bg_res != nullptr;
 #define HS_ROWS(pass) (((pass) + 1 < NPASS ? 2 : NI - 2 * (NPASS - 1)) * 32)
 #define HS_EPI_PREP(pass)                 /* element offsets of this thread's rows (-1: past the block's pixels) + residual loads */ \
     {                                                                                           \
         _Pragma("unroll") for (int j = 0; j < HS_ROWS(pass) / 8; ++j) {                         \
             const int m_ = m0 + 64 * (pass) + rr0 + 8 * j;                                      \
-            if (PK) {                         /* row -> (segment, pixel) -> address in the segment's image */ \
-                const int r_ = 64 * (pass) + rr0 + 8 * j;                                       \
-                const bool sb_ = r_ >= nA;                                                      \
-                const int mm_ = sb_ ? r_ - nA : m_;                                             \
-                const int y_ = (int)(((float)mm_ + 0.5f) * invW), x_ = mm_ - y_ * Wr;           \
-                const int Y_ = (sb_ ? ryB : cy0) + y_, X_ = (sb_ ? rxB : cx0) + x_;             \
-                off[(pass) & 1][j] = r_ < nA + nB ? (((sb_ ? imgB : img) * p.Hd + Y_) * p.Wd + X_) * HS_C : -1; \
-                res_stale[j] = r_ < nA + nB && sel_res && (Y_ < (sb_ ? byB0 : by0) - p.grow_res || Y_ > (sb_ ? byB1 : by1) + p.grow_res || \
-                                           X_ < (sb_ ? bxB0 : bx0) - p.grow_res || X_ > (sb_ ? bxB1 : bx1) + p.grow_res); \
+            if (PK) {                         /* the row's entry of the block's map (written in the prologue): a broadcast read */ \
+                const int2 e_ = *(const int2 *)(smem + HS_SMEM + 8 * (64 * (pass) + rr0 + 8 * j)); \
+                off[(pass) & 1][j] = e_.x;                                                      \
+                rsrc[j] = e_.y;                                                                 \
             } else if (RECT) {                                                                  \
                 const int y_ = (int)(((float)m_ + 0.5f) * invW), x_ = m_ - y_ * Wr;             \
                 off[(pass) & 1][j] = m_ < m1 ? ((cy0 + y_) * p.Wd + cx0 + x_) * HS_C : -1;      \
@@ -881,11 +898,11 @@ __device__ __forceinline__ void hs_block(const ConvHsArgs &p, unsigned char *sme
                     const _Float16 *rb_ = (RECT && res_stale[j]) ? (const _Float16 *)p.bg_res + 4 * cq : (const _Float16 *)p.res + obase; \
                     const f16x4 r16_ = *(const f16x4 *)(rb_ + max(off[(pass) & 1][j], 0));      \
                     rv[(pass) & 1][j] = make_float4(hs_from16<BF>(r16_[0]), hs_from16<BF>(r16_[1]), hs_from16<BF>(r16_[2]), hs_from16<BF>(r16_[3])); \
+                } else if (PK) {              /* (the entry names the source and the offset in it: see the map) */ \
+                    rv[(pass) & 1][j] = *(const float4 *)((rsrc[j] < 0 ? bgq : resq) + (rsrc[j] & 0x7FFFFFFF)); \
                 } else {                                                                        \
-                    /* (PK: the row's offset carries its image, the background image is one canvas) */ \
-                    const int bgo_ = (PK && res_stale[j]) ? (64 * (pass) + rr0 + 8 * j >= nA ? imgB : img) * HWc * HS_C : 0; \
                     const float *rb_ = (RECT && res_stale[j]) ? p.bg_res + 4 * cq : p.res + obase; \
-                    rv[(pass) & 1][j] = *(const float4 *)(rb_ + (max(off[(pass) & 1][j], 0) - bgo_));    \
+                    rv[(pass) & 1][j] = *(const float4 *)(rb_ + max(off[(pass) & 1][j], 0));    \
                 }                                                                               \
             }                                                                                   \
         }                                                                                       \
@@ -1056,7 +1073,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_f16s_rect(ConvHsArgs p)
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_f16s_rectp(ConvHsArgs p)
 {
-    __shared__ __align__(16) unsigned char smem[HS_SMEM];
+    __shared__ __align__(16) unsigned char smem[HS_SMEM + HS_ROWMAP];                  // the block's row map sits behind the staging / exchange buffers
     const int nd = *p.n_desc;
     const uint4 dA = p.desc[2 * blockIdx.x], dB = p.desc[2 * blockIdx.x + 1];      // the grid never exceeds the array
     if (2 * (int)blockIdx.x >= nd) return;
