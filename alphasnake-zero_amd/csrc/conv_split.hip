@@ -136,6 +136,21 @@ struct ConvHsArgs {
     const unsigned char *res_mask;     // MODE 8: ReLU bits (one byte per quad of channels) the shortcut rows are taken through
 };
 
+// The kernels' MODE (an int template parameter; described at length above hs_block), named for the host code:
+enum HsMode : int {
+    HS_MODE_ARGS = 0,              // every option of the epilogue read from the arguments at run time
+    HS_MODE_RELU = 1,              // ReLU, no shortcut
+    HS_MODE_RES_RELU = 2,          // ReLU + shortcut
+    HS_MODE_HEAD = 3,              // ReLU + shortcut + the fused 1x1 head, no layer output
+    HS_MODE_STATS = 4,             // training forward: the bare convolution + its batch-norm sums (+ maxima where amax_part is given)
+    HS_MODE_IGRAD = 5,             // training input gradient (+ the shortcut's) + the layer below's backward sums, its ReLU from mask bytes
+    HS_MODE_STATS_AFF = 6,         // STATS whose input goes through relu(x * aff_scale + aff_shift) on its way in
+    HS_MODE_IGRAD_AFF = 7,         // IGRAD whose ReLU decision is recomputed from aff_scale / aff_shift; never a shortcut
+    HS_MODE_IGRAD_MRES = 8,        // IGRAD whose shortcut gradient is taken through res_mask's bits
+    HS_MODE_STATS_AFF_AMAX = 9,    // STATS_AFF + the per-channel maxima
+    HS_MODE_IGRAD_MRES_AFF = 10,   // IGRAD_MRES whose ReLU decision for the sums is recomputed like IGRAD_AFF's
+};
+
 #ifdef HS_STAMPS       // development build only (tools/conv_stamps.py): s_memtime at the phase boundaries of every block
 __device__ unsigned long long hs_stamp_buf[16384 * 8];
 #define HS_STAMP(k) if (tid == 0 && blockIdx.x < 16384) hs_stamp_buf[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memtime();
@@ -1393,20 +1408,37 @@ extern "C" int snk_conv3x3_prepare_weights_f16s_train_batch(const float *const *
     return 0;
 }
 
-static int conv_f16s_launch(const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
-                            const float *d_residual, float *d_out, const float *d_w1x1, float s1, float b1, float *d_h1,
-                            int n_images, int height, int width, int relu, bool split, void *stream, int io16 = 0,
-                            const float *d_center = nullptr, float *d_stat_part = nullptr, int *grid_out = nullptr, bool bf = false,
-                            const float *d_gy = nullptr, const unsigned char *d_gmask = nullptr, const float *d_ginv = nullptr,
-                            const float *d_aff_scale = nullptr, const float *d_aff_shift = nullptr, float *d_amax_part = nullptr,
-                            const unsigned char *d_res_mask = nullptr, bool mx = false)
+// ---- the host side ---------------------------------------------------------------------------------------------------------------
+// One launch as its entry point states it.  a: the ConvHsArgs members the entry point sets, by name (x, wS and the canvas come from
+// conv_form); the launchers fill in the weight image's tail and the block plan.  Nothing is deduced from which pointers are set:
+// the entry point names its MODE and frame, and conv_form_check refuses a form whose arguments contradict them.
+struct ConvForm {
+    const char *who;           // the entry point that was called, for the wording of a refusal
+    int mode;                  // HsMode
+    bool split;                // true: the split f16s form; false: one MFMA per product (single-pass f16 and the 16-bit towers)
+    int io16;                  // 0: float32 tensors; 1: 16-bit activations in, float32 out; 3: 16-bit in and out
+    bool bf, mx;               // 16-bit towers: bf16 instead of f16; MX-FP8 operands (with bf)
+    int n_images;
+    void *stream;
+    ConvHsArgs a;
+};
+
+static ConvForm conv_form(const char *who, int mode, const void *d_x, const void *d_wS, int n_images, int height, int width, void *stream)
 {
-    SNK_REQUIRE(n_images >= 0 && height >= 1 && width >= 3, "snk_conv3x3_bn_f16s: bad shape %d x %d x %d", n_images, height, width);
-    SNK_REQUIRE(d_out != d_x, "snk_conv3x3_bn_f16s: in-place convolution is not possible (blocks read their neighbours' input rows)");
-    SNK_REQUIRE(d_out != d_residual || d_res_mask, "snk_conv3x3_bn_f16s: the output may overwrite the shortcut in the masked-shortcut form only");
-    if (n_images == 0) return 0;
+    ConvForm f = {};
+    f.who = who; f.mode = mode; f.split = true; f.n_images = n_images; f.stream = stream;
+    f.a.x = (const float *)d_x; f.a.wS = (const f16x8 *)d_wS; f.a.Hd = height; f.a.Wd = width;
+    return f;
+}
+
+// the compile-time epilogue of a tower layer: ReLU without / with shortcut; anything else takes the generic one
+static int hs_tower_mode(int relu, const void *d_residual) { return !relu ? HS_MODE_ARGS : d_residual ? HS_MODE_RES_RELU : HS_MODE_RELU; }
+
+// The block plan of a full-form launch: n_blk blocks per image of at most tiles_max M tiles (tests/conv_plan_ref.py restates it).
+static int conv_f16s_plan(const char *who, int n_images, int height, int width, bool a16, int *n_blk_out, int *tiles_max_out)
+{
     const int P = width + 1, HW = height * width;
-    const bool a16 = (io16 & 1) != 0;                      // the 16-bit frame: LDS rows pitched in bytes, six staging items
+    // (a16: the 16-bit frame: LDS rows pitched in bytes, six staging items)
     const int nst_px = 64 * (a16 ? HS_NST16 : HS_NST);
     // GEMM rows = the image's pixels in row-major order, 32 per M tile; an image is cut into n_blk blocks of at most 8 M
     // tiles whose input rows (those of its pixels + one above and below) fit the LDS buffer and the staging items
@@ -1420,7 +1452,7 @@ static int conv_f16s_launch(const float *d_x, const void *d_wS, const float *d_s
                min(rows_out + 2, height) * width <= nst_px;
         if (fits || tiles_max == 1) break;
     }
-    SNK_REQUIRE(fits, "snk_conv3x3_bn_f16s: observation width %d not supported (max 80)", width);
+    SNK_REQUIRE(fits, "%s: observation width %d not supported (max 80)", who, width);
     // very small batches (measured: up to ~40 images at 21x21): cut the images finer so that the grid covers more of the
     // chip's block slots -- a block's duration, not the throughput, is what such a launch costs (16 states: 31 -> 14 us);
     // from ~48 images on the 7-tile blocks with their compile-time epilogues are faster again
@@ -1429,123 +1461,139 @@ static int conv_f16s_launch(const float *d_x, const void *d_wS, const float *d_s
         n_blk = min(T, max(n_blk, (512 + n_images - 1) / n_images));
         tiles_max = (T + n_blk - 1) / n_blk;
     }
-    const int tiles_base = T / n_blk, tiles_rem = T % n_blk;
-    SNK_REQUIRE((long)n_images * n_blk < (1l << 31) && (long)HW * HS_C < (1l << 31), "snk_conv3x3_bn_f16s: batch too large");
-    ConvHsArgs a = {d_x, (const f16x8 *)d_wS, (const float *)((const _Float16 *)d_wS + HS_WS_ELEMS), d_scale, d_shift,
-                    d_residual, d_out, d_w1x1, d_h1, s1, b1, height, width, n_blk, tiles_base, tiles_rem, relu, (n_images / 8) * 8,
-                    d_center, d_stat_part, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, d_gy, d_gmask, d_ginv,
-                    d_aff_scale, d_aff_shift, d_amax_part, d_res_mask};
-    const int n_mt = tiles_max, grid = n_images * n_blk;
-    hipStream_t st = (hipStream_t)stream;
-    if (grid_out) *grid_out = grid;
-// (split == false: the training step's single-pass f16 form -- the same frames with the hi halves only, SPLIT = false)
-#define HS_LAUNCH_TRAIN_NI(NI_, MODE_)                                                          \
-        if (split) k_conv3x3_f16s<NI_, MODE_><<<grid, 256, 0, st>>>(a);                         \
-        else k_conv3x3_f16s<NI_, MODE_, false><<<grid, 256, 0, st>>>(a);                        \
-        break;
-#define HS_LAUNCH_TRAIN(MODE_)                                                                   \
-        switch (n_mt) {                                                                         \
-        case 1: HS_LAUNCH_TRAIN_NI(1, MODE_)                                                    \
-        case 2: HS_LAUNCH_TRAIN_NI(2, MODE_)                                                    \
-        case 3: HS_LAUNCH_TRAIN_NI(3, MODE_)                                                    \
-        case 4: HS_LAUNCH_TRAIN_NI(4, MODE_)                                                    \
-        case 5: HS_LAUNCH_TRAIN_NI(5, MODE_)                                                    \
-        case 6: HS_LAUNCH_TRAIN_NI(6, MODE_)                                                    \
-        case 7: HS_LAUNCH_TRAIN_NI(7, MODE_)                                                    \
-        default: HS_LAUNCH_TRAIN_NI(8, MODE_)                                                   \
-        }                                                                                       \
-        SNK_CHECK_HIP(hipGetLastError());                                                       \
-        return 0;
-    SNK_REQUIRE(!(d_stat_part && a.g_y && d_aff_scale && d_residual && !d_res_mask),
-                "snk_conv3x3_f16s_igrad_stats_deferred: the layer below a block's second convolution has no shortcut gradient to add");
-    if (d_stat_part && a.g_y && d_res_mask && d_aff_scale) { HS_LAUNCH_TRAIN(10) }   // ... and the ReLU decision of the sums recomputed (deferred stem below)
-    if (d_stat_part && a.g_y && d_res_mask) { HS_LAUNCH_TRAIN(8) }     // input gradient + sums, the shortcut's gradient taken through ReLU bits
-    if (d_stat_part && a.g_y && d_aff_scale) { HS_LAUNCH_TRAIN(7) }    // ... of a layer whose ReLU decision is recomputed from its scale / shift
-    if (d_stat_part && d_aff_scale && d_amax_part) { HS_LAUNCH_TRAIN(9) }
-    if (d_stat_part && d_aff_scale) { HS_LAUNCH_TRAIN(6) }             // forward pass, the producer's batch norm + ReLU applied on the way in
-    if (d_stat_part && a.g_y) { HS_LAUNCH_TRAIN(5) }                   // the training step's input gradient + the previous layer's batch-norm backward sums
-    if (d_stat_part) { HS_LAUNCH_TRAIN(4) }                            // the training step's forward pass: bare convolution + batch-norm sums
-#undef HS_LAUNCH_TRAIN
-#undef HS_LAUNCH_TRAIN_NI
-    // the three epilogue shapes the net wrapper uses get compile-time versions at the 21x21 tile count; everything else
-    // takes the generic version
-    if (!split && io16) {        // f16 activations in HBM (io16: 1 = f16 in, f32 out; 3 = f16 in and out)
-#define HS_LAUNCH_IO4(NI_, MODE_)                                                               \
-        if (mx && io16 == 3) k_conv3x3_f16s<NI_, MODE_, false, 3, true, true><<<grid, 256, 0, st>>>(a); \
-        else if (mx) k_conv3x3_f16s<NI_, MODE_, false, 1, true, true><<<grid, 256, 0, st>>>(a); \
-        else if (bf && io16 == 3) k_conv3x3_f16s<NI_, MODE_, false, 3, true><<<grid, 256, 0, st>>>(a); \
-        else if (bf) k_conv3x3_f16s<NI_, MODE_, false, 1, true><<<grid, 256, 0, st>>>(a);       \
-        else if (io16 == 3) k_conv3x3_f16s<NI_, MODE_, false, 3><<<grid, 256, 0, st>>>(a);      \
-        else k_conv3x3_f16s<NI_, MODE_, false, 1><<<grid, 256, 0, st>>>(a);
-// the tower's two shapes (ReLU without / with shortcut) have compile-time epilogues; anything else takes the generic one
-#define HS_LAUNCH_IO(NI_)                                                                       \
-    case NI_:                                                                                   \
-        if (relu && !d_residual) { HS_LAUNCH_IO4(NI_, 1) }                                      \
-        else if (relu) { HS_LAUNCH_IO4(NI_, 2) }                                                \
-        else { HS_LAUNCH_IO4(NI_, 0) }                                                          \
-        break;
-        if (d_w1x1) {            // the tower's last layer with the head's 1x1 stage in its epilogue: no layer output
-            SNK_REQUIRE(io16 == 1 && relu && d_residual && !d_out && d_h1, "snk_conv3x3_bn_*_act16_head: the fused head closes a residual block");
-#define HS_LAUNCH_HEAD(NI_) case NI_: if (mx) k_conv3x3_f16s<NI_, 3, false, 1, true, true><<<grid, 256, 0, st>>>(a); \
-                                      else if (bf) k_conv3x3_f16s<NI_, 3, false, 1, true><<<grid, 256, 0, st>>>(a); \
-                                      else k_conv3x3_f16s<NI_, 3, false, 1><<<grid, 256, 0, st>>>(a); break;
-            switch (n_mt) {
-                HS_LAUNCH_HEAD(1) HS_LAUNCH_HEAD(2) HS_LAUNCH_HEAD(3) HS_LAUNCH_HEAD(4) HS_LAUNCH_HEAD(5) HS_LAUNCH_HEAD(6) HS_LAUNCH_HEAD(7)
-            default: if (mx) k_conv3x3_f16s<8, 3, false, 1, true, true><<<grid, 256, 0, st>>>(a);
-                     else if (bf) k_conv3x3_f16s<8, 3, false, 1, true><<<grid, 256, 0, st>>>(a);
-                     else k_conv3x3_f16s<8, 3, false, 1><<<grid, 256, 0, st>>>(a); break;
-            }
-#undef HS_LAUNCH_HEAD
-            SNK_CHECK_HIP(hipGetLastError());
-            return 0;
-        }
-        switch (n_mt) {
-            HS_LAUNCH_IO(1) HS_LAUNCH_IO(2) HS_LAUNCH_IO(3) HS_LAUNCH_IO(4) HS_LAUNCH_IO(5) HS_LAUNCH_IO(6) HS_LAUNCH_IO(7)
-        default:
-            if (relu && !d_residual) { HS_LAUNCH_IO4(8, 1) }
-            else if (relu) { HS_LAUNCH_IO4(8, 2) }
-            else { HS_LAUNCH_IO4(8, 0) }
-            break;
-        }
-#undef HS_LAUNCH_IO4
-#undef HS_LAUNCH_IO
-        SNK_CHECK_HIP(hipGetLastError());
-        return 0;
+    *n_blk_out = n_blk;
+    *tiles_max_out = tiles_max;
+    return 0;
+}
+
+// What a MODE needs of the arguments and excludes -- the cross-checks the launcher once made by the order in which it looked at pointers.
+static int conv_form_check(const ConvForm &f)
+{
+    const ConvHsArgs &a = f.a;
+    const bool aff = a.aff_scale && a.aff_shift, no_aff = !a.aff_scale && !a.aff_shift, igrad = a.g_y && a.g_inv;
+    SNK_REQUIRE(!(f.mode == HS_MODE_IGRAD_AFF && a.res), "%s: the layer below a block's second convolution has no shortcut gradient to add", f.who);
+    bool ok = false;
+    switch (f.mode) {
+    case HS_MODE_ARGS:           ok = true; break;
+    case HS_MODE_RELU:           ok = a.relu && !a.res && a.out && !a.w1x1; break;
+    case HS_MODE_RES_RELU:       ok = a.relu && a.res && a.out && !a.w1x1; break;
+    case HS_MODE_HEAD:           ok = a.relu && a.res && !a.out && a.w1x1 && a.h1; break;     // the fused head closes a residual block
+    case HS_MODE_STATS:          ok = !a.g_y && no_aff && !a.res_mask; break;
+    case HS_MODE_IGRAD:          ok = igrad && a.g_mask && no_aff && !a.res_mask; break;
+    case HS_MODE_STATS_AFF:      ok = !a.g_y && aff && !a.amax_part && !a.res_mask; break;
+    case HS_MODE_IGRAD_AFF:      ok = igrad && !a.g_mask && aff && !a.res_mask; break;
+    case HS_MODE_IGRAD_MRES:     ok = igrad && a.g_mask && no_aff && a.res && a.res_mask; break;
+    case HS_MODE_STATS_AFF_AMAX: ok = !a.g_y && aff && a.amax_part && !a.res_mask; break;
+    case HS_MODE_IGRAD_MRES_AFF: ok = igrad && !a.g_mask && aff && a.res && a.res_mask; break;
     }
-    if (!split) {
-        switch (n_mt) {
-        case 1: k_conv3x3_f16s<1, 0, false><<<grid, 256, 0, st>>>(a); break;
-        case 2: k_conv3x3_f16s<2, 0, false><<<grid, 256, 0, st>>>(a); break;
-        case 3: k_conv3x3_f16s<3, 0, false><<<grid, 256, 0, st>>>(a); break;
-        case 4: k_conv3x3_f16s<4, 0, false><<<grid, 256, 0, st>>>(a); break;
-        case 5: k_conv3x3_f16s<5, 0, false><<<grid, 256, 0, st>>>(a); break;
-        case 6: k_conv3x3_f16s<6, 0, false><<<grid, 256, 0, st>>>(a); break;
-        case 7: k_conv3x3_f16s<7, 0, false><<<grid, 256, 0, st>>>(a); break;
-        default: k_conv3x3_f16s<8, 0, false><<<grid, 256, 0, st>>>(a); break;
-        }
-        SNK_CHECK_HIP(hipGetLastError());
-        return 0;
-    }
-    const int mode = !relu ? 0 : (d_w1x1 ? (d_residual && !d_out ? 3 : 0) : (d_residual ? 2 : 1));
-#define HS_LAUNCH_MODES(NI_)                                                                    \
-    case NI_:                                                                                   \
-        if (mode == 1) k_conv3x3_f16s<NI_, 1><<<grid, 256, 0, st>>>(a);                         \
-        else if (mode == 2) k_conv3x3_f16s<NI_, 2><<<grid, 256, 0, st>>>(a);                    \
-        else if (mode == 3) k_conv3x3_f16s<NI_, 3><<<grid, 256, 0, st>>>(a);                    \
-        else k_conv3x3_f16s<NI_, 0><<<grid, 256, 0, st>>>(a);                                   \
-        break;
+    // the training forms are bare convolutions on float32 tensors that leave sums; the inference forms leave none
+    if (f.mode >= HS_MODE_STATS) ok = ok && a.stat_part && a.out && !a.w1x1 && f.io16 == 0 && !f.bf && !f.mx;
+    else ok = ok && !a.stat_part && !a.amax_part && !a.g_y && no_aff && !a.res_mask;
+    SNK_REQUIRE(ok, "%s: the arguments do not make MODE %d", f.who, f.mode);
+    SNK_REQUIRE((f.io16 == 0 || ((f.io16 == 1 || f.io16 == 3) && !f.split)) && (f.io16 != 0 || !f.bf) && (!f.mx || f.bf),
+                "%s: no frame split %d, io16 %d, bf %d, mx %d", f.who, f.split, f.io16, f.bf, f.mx);
+    return 0;
+}
+
+// The NI switch, once: the kernel compiled for n_mt M tiles per block of the frame <MODE, SPLIT, IO16, BF, MX>.
+template <int MODE, bool SPLIT, int IO16, bool BF, bool MX>
+static void hs_launch(const ConvHsArgs &a, int n_mt, int grid, hipStream_t st)
+{
     switch (n_mt) {
-        HS_LAUNCH_MODES(1) HS_LAUNCH_MODES(2) HS_LAUNCH_MODES(3) HS_LAUNCH_MODES(4)
-        HS_LAUNCH_MODES(5) HS_LAUNCH_MODES(6) HS_LAUNCH_MODES(7)
-    default:
-        if (mode == 1) k_conv3x3_f16s<8, 1><<<grid, 256, 0, st>>>(a);
-        else if (mode == 2) k_conv3x3_f16s<8, 2><<<grid, 256, 0, st>>>(a);
-        else if (mode == 3) k_conv3x3_f16s<8, 3><<<grid, 256, 0, st>>>(a);
-        else k_conv3x3_f16s<8, 0><<<grid, 256, 0, st>>>(a);
-        break;
+    case 1: k_conv3x3_f16s<1, MODE, SPLIT, IO16, BF, MX><<<grid, 256, 0, st>>>(a); break;
+    case 2: k_conv3x3_f16s<2, MODE, SPLIT, IO16, BF, MX><<<grid, 256, 0, st>>>(a); break;
+    case 3: k_conv3x3_f16s<3, MODE, SPLIT, IO16, BF, MX><<<grid, 256, 0, st>>>(a); break;
+    case 4: k_conv3x3_f16s<4, MODE, SPLIT, IO16, BF, MX><<<grid, 256, 0, st>>>(a); break;
+    case 5: k_conv3x3_f16s<5, MODE, SPLIT, IO16, BF, MX><<<grid, 256, 0, st>>>(a); break;
+    case 6: k_conv3x3_f16s<6, MODE, SPLIT, IO16, BF, MX><<<grid, 256, 0, st>>>(a); break;
+    case 7: k_conv3x3_f16s<7, MODE, SPLIT, IO16, BF, MX><<<grid, 256, 0, st>>>(a); break;
+    default: k_conv3x3_f16s<8, MODE, SPLIT, IO16, BF, MX><<<grid, 256, 0, st>>>(a); break;
     }
-#undef HS_LAUNCH_MODES
+}
+
+// the training forms: float32 tensors, the split form or the single-pass f16 form (the same frames with the hi halves only)
+template <int MODE> static void hs_launch_train(const ConvForm &f, const ConvHsArgs &a, int n_mt, int grid)
+{
+    if (f.split) hs_launch<MODE, true, 0, false, false>(a, n_mt, grid, (hipStream_t)f.stream);
+    else hs_launch<MODE, false, 0, false, false>(a, n_mt, grid, (hipStream_t)f.stream);
+}
+
+// the 16-bit towers: f16, bf16 or MX-FP8 operands (IO16: 1 = 16-bit in, float32 out; 3 = 16-bit in and out)
+template <int MODE, int IO16> static void hs_launch_a16(const ConvForm &f, const ConvHsArgs &a, int n_mt, int grid)
+{
+    if (f.mx) hs_launch<MODE, false, IO16, true, true>(a, n_mt, grid, (hipStream_t)f.stream);
+    else if (f.bf) hs_launch<MODE, false, IO16, true, false>(a, n_mt, grid, (hipStream_t)f.stream);
+    else hs_launch<MODE, false, IO16, false, false>(a, n_mt, grid, (hipStream_t)f.stream);
+}
+
+// The one place that says which <MODE, SPLIT, IO16, BF, MX> are built; false: this form has no kernel.
+static bool hs_dispatch(const ConvForm &f, const ConvHsArgs &a, int n_mt, int grid)
+{
+    hipStream_t st = (hipStream_t)f.stream;
+    if (f.mode >= HS_MODE_STATS) {
+        switch (f.mode) {
+        case HS_MODE_STATS:          hs_launch_train<HS_MODE_STATS>(f, a, n_mt, grid); return true;
+        case HS_MODE_IGRAD:          hs_launch_train<HS_MODE_IGRAD>(f, a, n_mt, grid); return true;
+        case HS_MODE_STATS_AFF:      hs_launch_train<HS_MODE_STATS_AFF>(f, a, n_mt, grid); return true;
+        case HS_MODE_IGRAD_AFF:      hs_launch_train<HS_MODE_IGRAD_AFF>(f, a, n_mt, grid); return true;
+        case HS_MODE_IGRAD_MRES:     hs_launch_train<HS_MODE_IGRAD_MRES>(f, a, n_mt, grid); return true;
+        case HS_MODE_STATS_AFF_AMAX: hs_launch_train<HS_MODE_STATS_AFF_AMAX>(f, a, n_mt, grid); return true;
+        case HS_MODE_IGRAD_MRES_AFF: hs_launch_train<HS_MODE_IGRAD_MRES_AFF>(f, a, n_mt, grid); return true;
+        }
+        return false;
+    }
+    if (f.io16 == 3) {           // a tower layer whose reader is another layer
+        switch (f.mode) {
+        case HS_MODE_ARGS:     hs_launch_a16<HS_MODE_ARGS, 3>(f, a, n_mt, grid); return true;
+        case HS_MODE_RELU:     hs_launch_a16<HS_MODE_RELU, 3>(f, a, n_mt, grid); return true;
+        case HS_MODE_RES_RELU: hs_launch_a16<HS_MODE_RES_RELU, 3>(f, a, n_mt, grid); return true;
+        }
+        return false;
+    }
+    if (f.io16 == 1) {           // the layer the head reads, or the one that carries the head's 1x1 stage in its epilogue
+        switch (f.mode) {
+        case HS_MODE_ARGS:     hs_launch_a16<HS_MODE_ARGS, 1>(f, a, n_mt, grid); return true;
+        case HS_MODE_RELU:     hs_launch_a16<HS_MODE_RELU, 1>(f, a, n_mt, grid); return true;
+        case HS_MODE_RES_RELU: hs_launch_a16<HS_MODE_RES_RELU, 1>(f, a, n_mt, grid); return true;
+        case HS_MODE_HEAD:     hs_launch_a16<HS_MODE_HEAD, 1>(f, a, n_mt, grid); return true;
+        }
+        return false;
+    }
+    if (!f.split) {              // single-pass f16 on float32 tensors: the generic epilogue only
+        if (f.mode != HS_MODE_ARGS) return false;
+        hs_launch<HS_MODE_ARGS, false, 0, false, false>(a, n_mt, grid, st);
+        return true;
+    }
+    switch (f.mode) {            // the float32 tower
+    case HS_MODE_ARGS:     hs_launch<HS_MODE_ARGS, true, 0, false, false>(a, n_mt, grid, st); return true;
+    case HS_MODE_RELU:     hs_launch<HS_MODE_RELU, true, 0, false, false>(a, n_mt, grid, st); return true;
+    case HS_MODE_RES_RELU: hs_launch<HS_MODE_RES_RELU, true, 0, false, false>(a, n_mt, grid, st); return true;
+    case HS_MODE_HEAD:     hs_launch<HS_MODE_HEAD, true, 0, false, false>(a, n_mt, grid, st); return true;
+    }
+    return false;
+}
+
+// The full form: every image cut into blocks by conv_f16s_plan.  grid_out: the blocks launched (the training forms fold that many rows).
+static int conv_f16s_launch(const ConvForm &f, int *grid_out = nullptr)
+{
+    const int n_images = f.n_images, height = f.a.Hd, width = f.a.Wd;
+    SNK_REQUIRE(n_images >= 0 && height >= 1 && width >= 3, "%s: bad shape %d x %d x %d", f.who, n_images, height, width);
+    SNK_REQUIRE(f.a.out != f.a.x, "%s: in-place convolution is not possible (blocks read their neighbours' input rows)", f.who);
+    SNK_REQUIRE(f.a.out != f.a.res || f.a.res_mask, "%s: the output may overwrite the shortcut in the masked-shortcut form only", f.who);
+    if (n_images == 0) return 0;
+    int n_blk = 0, tiles_max = 0;
+    const int rc = conv_f16s_plan(f.who, n_images, height, width, (f.io16 & 1) != 0, &n_blk, &tiles_max);
+    if (rc) return rc;
+    SNK_REQUIRE((long)n_images * n_blk < (1l << 31) && (long)height * width * HS_C < (1l << 31), "%s: batch too large", f.who);
+    if (conv_form_check(f)) return -1;
+    ConvHsArgs a = f.a;
+    a.wscale_inv = (const float *)((const _Float16 *)a.wS + HS_WS_ELEMS);
+    const int T = (height * width + 31) / 32, grid = n_images * n_blk;
+    a.n_blk = n_blk; a.tiles_base = T / n_blk; a.tiles_rem = T % n_blk;
+    a.n_img_grouped = (n_images / 8) * 8;
+    SNK_REQUIRE(hs_dispatch(f, a, tiles_max, grid), "%s: no kernel is built for MODE %d, split %d, io16 %d", f.who, f.mode, f.split, f.io16);
     SNK_CHECK_HIP(hipGetLastError());
+    if (grid_out) *grid_out = grid;
     return 0;
 }
 
@@ -2018,35 +2066,58 @@ extern "C" int snk_conv_rect_plan_pack_host(const unsigned *h_bbox, int n_images
     return 0;
 }
 
-// who: the entry point that was called, for the wording of a refusal
-static int conv_f16s_rect_launch(const char *who, const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
-                                 const float *d_residual, float *d_out, const void *d_desc, const int *d_count,
-                                 const float *d_bg_in, int grow_in, const float *d_bg_res, int grow_res, const float *d_bg_out,
-                                 int n_images, int height, int width, bool act16, void *stream, bool bf = false, bool mx = false)
+// the frames the sub-rectangle kernels are built in: the float32 tower (split) and the three 16-bit towers (16-bit in and out)
+template <int MODE> static void hs_launch_rect(const ConvForm &f, const ConvHsArgs &a, bool pack, int grid)
 {
-    SNK_REQUIRE(grow_in >= 0 && grow_in < 128 && grow_res >= 0 && grow_res < 128, "%s: grow_in %d, grow_res %d", who, grow_in, grow_res);
-    SNK_REQUIRE(d_x && d_wS && d_scale && d_shift && d_out && d_desc && d_count, "%s: NULL argument", who);
-    SNK_REQUIRE(d_out != d_x, "%s: in-place convolution is not possible", who);
-    const long mb = rect_max_blocks(n_images, height, width, act16);
-    SNK_REQUIRE(mb >= 0 && mb < (1l << 31) && (long)height * width * HS_C < (1l << 31), "%s: bad shape %d x %d x %d", who,
-                n_images, height, width);
+    hipStream_t st = (hipStream_t)f.stream;
+    if (pack) k_conv3x3_f16s_rectp<MODE><<<grid, 256, 0, st>>>(a);
+    else if (f.mx) k_conv3x3_f16s_rect<MODE, false, 3, true, true><<<grid, 256, 0, st>>>(a);
+    else if (f.bf) k_conv3x3_f16s_rect<MODE, false, 3, true, false><<<grid, 256, 0, st>>>(a);
+    else if (f.io16) k_conv3x3_f16s_rect<MODE, false, 3, false, false><<<grid, 256, 0, st>>>(a);
+    else k_conv3x3_f16s_rect<MODE, true, 0, false, false><<<grid, 256, 0, st>>>(a);
+}
+
+// The sub-rectangle forms: one block per descriptor of a.desc -- snk_conv_rect_plan's, or (pack) snk_conv_rect_plan_pack's.
+static int conv_f16s_rect_launch(const ConvForm &f, bool pack = false)
+{
+    const char *who = f.who;
+    const int n_images = f.n_images, height = f.a.Hd, width = f.a.Wd;
+    SNK_REQUIRE(f.a.grow_in >= 0 && f.a.grow_in < 128 && f.a.grow_res >= 0 && f.a.grow_res < 128, "%s: grow_in %d, grow_res %d", who,
+                f.a.grow_in, f.a.grow_res);
+    SNK_REQUIRE(f.a.x && f.a.wS && f.a.scale && f.a.shift && f.a.out && f.a.desc && f.a.n_desc, "%s: NULL argument", who);
+    SNK_REQUIRE(f.a.out != f.a.x, "%s: in-place convolution is not possible", who);
+    // grid: the most blocks the plan can have written; (packed: a row's offset into the tensors carries its image: the whole
+    // batch must stay below 2^31 elements)
+    const long mb = pack ? rect_pack_max_desc(n_images, height, width) : rect_max_blocks(n_images, height, width, f.io16 != 0);
+    SNK_REQUIRE(mb >= 0 && mb < (1l << 31) && (long)(pack ? n_images : 1) * height * width * HS_C < (1l << 31), "%s: bad shape %d x %d x %d",
+                who, n_images, height, width);
     if (n_images == 0) return 0;
-    ConvHsArgs a = {d_x, (const f16x8 *)d_wS, (const float *)((const _Float16 *)d_wS + HS_WS_ELEMS), d_scale, d_shift,
-                    d_residual, d_out, nullptr, nullptr, 0.f, 0.f, height, width, 1, 0, 0, 1, 0, nullptr, nullptr,
-                    (const uint4 *)d_desc, d_count, d_bg_out, d_bg_in, d_residual ? d_bg_res : nullptr, grow_in, grow_res, nullptr, nullptr, nullptr};
-    if (act16 && mx) {
-        if (d_residual) k_conv3x3_f16s_rect<2, false, 3, true, true><<<(int)mb, 256, 0, (hipStream_t)stream>>>(a);
-        else k_conv3x3_f16s_rect<1, false, 3, true, true><<<(int)mb, 256, 0, (hipStream_t)stream>>>(a);
-    } else if (act16 && bf) {
-        if (d_residual) k_conv3x3_f16s_rect<2, false, 3, true><<<(int)mb, 256, 0, (hipStream_t)stream>>>(a);
-        else k_conv3x3_f16s_rect<1, false, 3, true><<<(int)mb, 256, 0, (hipStream_t)stream>>>(a);
-    } else if (act16) {
-        if (d_residual) k_conv3x3_f16s_rect<2, false, 3><<<(int)mb, 256, 0, (hipStream_t)stream>>>(a);
-        else k_conv3x3_f16s_rect<1, false, 3><<<(int)mb, 256, 0, (hipStream_t)stream>>>(a);
-    } else if (d_residual) k_conv3x3_f16s_rect<2><<<(int)mb, 256, 0, (hipStream_t)stream>>>(a);
-    else k_conv3x3_f16s_rect<1><<<(int)mb, 256, 0, (hipStream_t)stream>>>(a);
+    SNK_REQUIRE(f.mode == (f.a.res ? HS_MODE_RES_RELU : HS_MODE_RELU) && (f.io16 ? f.io16 == 3 && !f.split && !pack : f.split && !f.bf) &&
+                (!f.mx || f.bf), "%s: no sub-rectangle kernel is built for MODE %d, split %d, io16 %d", who, f.mode, f.split, f.io16);
+    ConvHsArgs a = f.a;
+    a.wscale_inv = (const float *)((const _Float16 *)a.wS + HS_WS_ELEMS);
+    a.n_blk = 1; a.relu = 1;
+    if (!a.res) a.bg_res = nullptr;
+    const int grid = (int)(pack ? mb / 2 : mb);
+    if (f.mode == HS_MODE_RES_RELU) hs_launch_rect<HS_MODE_RES_RELU>(f, a, pack, grid);
+    else hs_launch_rect<HS_MODE_RELU>(f, a, pack, grid);
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+// the argument list the five sub-rectangle entry points share, by name
+static ConvForm conv_rect_form(const char *who, const void *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
+                               const void *d_residual, void *d_out, const void *d_desc, const int *d_count, const void *d_bg_in,
+                               int grow_in, const void *d_bg_res, int grow_res, const void *d_bg_out, int n_images, int height,
+                               int width, void *stream)
+{
+    ConvForm f = conv_form(who, d_residual ? HS_MODE_RES_RELU : HS_MODE_RELU, d_x, d_wS, n_images, height, width, stream);
+    f.a.scale = d_scale; f.a.shift = d_shift; f.a.res = (const float *)d_residual; f.a.out = (float *)d_out;
+    f.a.desc = (const uint4 *)d_desc; f.a.n_desc = d_count;
+    f.a.bg_in = (const float *)d_bg_in; f.a.grow_in = grow_in;
+    f.a.bg_res = (const float *)d_bg_res; f.a.grow_res = grow_res;
+    f.a.bg_out = (const float *)d_bg_out;
+    return f;
 }
 
 extern "C" int snk_conv3x3_bn_f16s_rect(const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
@@ -2054,8 +2125,8 @@ extern "C" int snk_conv3x3_bn_f16s_rect(const float *d_x, const void *d_wS, cons
                                         const float *d_bg_in, int grow_in, const float *d_bg_res, int grow_res,
                                         const float *d_bg_out, int n_images, int height, int width, void *stream)
 {
-    return conv_f16s_rect_launch("snk_conv3x3_bn_f16s_rect", d_x, d_wS, d_scale, d_shift, d_residual, d_out, d_desc, d_count, d_bg_in,
-                                 grow_in, d_bg_res, grow_res, d_bg_out, n_images, height, width, false, stream);
+    return conv_f16s_rect_launch(conv_rect_form("snk_conv3x3_bn_f16s_rect", d_x, d_wS, d_scale, d_shift, d_residual, d_out, d_desc, d_count,
+                                                d_bg_in, grow_in, d_bg_res, grow_res, d_bg_out, n_images, height, width, stream));
 }
 
 // snk_conv3x3_bn_f16s_rect on the packed plan's descriptors (snk_conv_rect_plan_pack)
@@ -2064,22 +2135,13 @@ extern "C" int snk_conv3x3_bn_f16s_rect_pack(const float *d_x, const void *d_wS,
                                              const float *d_bg_in, int grow_in, const float *d_bg_res, int grow_res,
                                              const float *d_bg_out, int n_images, int height, int width, void *stream)
 {
-    SNK_REQUIRE(grow_in >= 0 && grow_in < 128 && grow_res >= 0 && grow_res < 128, "snk_conv3x3_bn_f16s_rect_pack: grow_in %d, grow_res %d", grow_in, grow_res);
-    SNK_REQUIRE(d_x && d_wS && d_scale && d_shift && d_out && d_desc && d_count, "snk_conv3x3_bn_f16s_rect_pack: NULL argument");
-    SNK_REQUIRE(d_out != d_x, "snk_conv3x3_bn_f16s_rect_pack: in-place convolution is not possible");
-    const long md = rect_pack_max_desc(n_images, height, width);
-    // (a row's offset into the tensors carries its image: the whole batch must stay below 2^31 elements)
-    SNK_REQUIRE(md >= 0 && md < (1l << 31) && (long)n_images * height * width * HS_C < (1l << 31), "snk_conv3x3_bn_f16s_rect_pack: bad shape %d x %d x %d",
-                n_images, height, width);
-    if (n_images == 0) return 0;
-    ConvHsArgs a = {d_x, (const f16x8 *)d_wS, (const float *)((const _Float16 *)d_wS + HS_WS_ELEMS), d_scale, d_shift,
-                    d_residual, d_out, nullptr, nullptr, 0.f, 0.f, height, width, 1, 0, 0, 1, 0, nullptr, nullptr,
-                    (const uint4 *)d_desc, d_count, d_bg_out, d_bg_in, d_residual ? d_bg_res : nullptr, grow_in, grow_res, nullptr, nullptr, nullptr};
-    if (d_residual) k_conv3x3_f16s_rectp<2><<<(int)(md / 2), 256, 0, (hipStream_t)stream>>>(a);
-    else k_conv3x3_f16s_rectp<1><<<(int)(md / 2), 256, 0, (hipStream_t)stream>>>(a);
-    SNK_CHECK_HIP(hipGetLastError());
-    return 0;
+    return conv_f16s_rect_launch(conv_rect_form("snk_conv3x3_bn_f16s_rect_pack", d_x, d_wS, d_scale, d_shift, d_residual, d_out, d_desc,
+                                                d_count, d_bg_in, grow_in, d_bg_res, grow_res, d_bg_out, n_images, height, width, stream),
+                                 true);
 }
+
+// the frame of the 16-bit towers' sub-rectangle layers: 16-bit activations in and out
+static ConvForm conv_rect_form16(ConvForm f, bool bf, bool mx) { f.split = false; f.io16 = 3; f.bf = bf; f.mx = mx; return f; }
 
 // the sub-rectangle form of snk_conv3x3_bn_f16_act16 (f16 activations in and out, relu = 1; the background images are f16
 // [height][width][128])
@@ -2088,9 +2150,9 @@ extern "C" int snk_conv3x3_bn_f16_act16_rect(const void *d_x16, const void *d_wS
                                              const void *d_bg_in16, int grow_in, const void *d_bg_res16, int grow_res,
                                              const void *d_bg_out16, int n_images, int height, int width, void *stream)
 {
-    return conv_f16s_rect_launch("snk_conv3x3_bn_f16_act16_rect", (const float *)d_x16, d_wS, d_scale, d_shift,
-                                 (const float *)d_residual16, (float *)d_out16, d_desc, d_count, (const float *)d_bg_in16, grow_in,
-                                 (const float *)d_bg_res16, grow_res, (const float *)d_bg_out16, n_images, height, width, true, stream);
+    return conv_f16s_rect_launch(conv_rect_form16(conv_rect_form("snk_conv3x3_bn_f16_act16_rect", d_x16, d_wS, d_scale, d_shift, d_residual16,
+                                                                 d_out16, d_desc, d_count, d_bg_in16, grow_in, d_bg_res16, grow_res, d_bg_out16,
+                                                                 n_images, height, width, stream), false, false));
 }
 
 // the same for the bf16 tower (bf16 activations in and out, bf16 background images, weights = snk_conv3x3_prepare_weights_bf16)
@@ -2099,36 +2161,60 @@ extern "C" int snk_conv3x3_bn_bf16_act16_rect(const void *d_x16, const void *d_w
                                               const void *d_bg_in16, int grow_in, const void *d_bg_res16, int grow_res,
                                               const void *d_bg_out16, int n_images, int height, int width, void *stream)
 {
-    return conv_f16s_rect_launch("snk_conv3x3_bn_bf16_act16_rect", (const float *)d_x16, d_wS, d_scale, d_shift,
-                                 (const float *)d_residual16, (float *)d_out16, d_desc, d_count, (const float *)d_bg_in16, grow_in,
-                                 (const float *)d_bg_res16, grow_res, (const float *)d_bg_out16, n_images, height, width, true, stream, true);
+    return conv_f16s_rect_launch(conv_rect_form16(conv_rect_form("snk_conv3x3_bn_bf16_act16_rect", d_x16, d_wS, d_scale, d_shift, d_residual16,
+                                                                 d_out16, d_desc, d_count, d_bg_in16, grow_in, d_bg_res16, grow_res, d_bg_out16,
+                                                                 n_images, height, width, stream), true, false));
 }
+
+// the argument list the inference entry points of the full form share, by name (d_out: NULL where only the fused head's output is wanted)
+static ConvForm conv_bn_form(const char *who, int mode, const void *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
+                             const void *d_residual, void *d_out, int relu, int n_images, int height, int width, void *stream)
+{
+    ConvForm f = conv_form(who, mode, d_x, d_wS, n_images, height, width, stream);
+    f.a.scale = d_scale; f.a.shift = d_shift; f.a.res = (const float *)d_residual; f.a.out = (float *)d_out; f.a.relu = relu;
+    return f;
+}
+
+// the head's 1x1 stage in the layer's epilogue
+static void conv_form_head(ConvForm &f, const float *d_w1x1, float bn_scale, float bn_shift, float *d_h1)
+{
+    f.a.w1x1 = d_w1x1; f.a.s1 = bn_scale; f.a.b1 = bn_shift; f.a.h1 = d_h1;
+}
+
+// the frame of the 16-bit towers' full layers: 16-bit activations in; out16: 16-bit out as well
+static void conv_form_a16(ConvForm &f, bool out16, bool bf, bool mx) { f.split = false; f.io16 = out16 ? 3 : 1; f.bf = bf; f.mx = mx; }
 
 extern "C" int snk_conv3x3_bn_f16s(const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
                                    const float *d_residual, float *d_out, int n_images, int height, int width, int relu,
                                    void *stream)
 {
     SNK_REQUIRE(d_x && d_wS && d_scale && d_shift && d_out, "snk_conv3x3_bn_f16s: NULL argument");
-    return conv_f16s_launch(d_x, d_wS, d_scale, d_shift, d_residual, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width,
-                            relu, true, stream);
+    return conv_f16s_launch(conv_bn_form("snk_conv3x3_bn_f16s", hs_tower_mode(relu, d_residual), d_x, d_wS, d_scale, d_shift, d_residual,
+                                         d_out, relu, n_images, height, width, stream));
 }
 
+// (single-pass f16 on float32 tensors: the generic epilogue is the only one built)
 extern "C" int snk_conv3x3_bn_f16(const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
                                   const float *d_residual, float *d_out, int n_images, int height, int width, int relu,
                                   void *stream)
 {
     SNK_REQUIRE(d_x && d_wS && d_scale && d_shift && d_out, "snk_conv3x3_bn_f16: NULL argument");
-    return conv_f16s_launch(d_x, d_wS, d_scale, d_shift, d_residual, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width,
-                            relu, false, stream);
+    ConvForm f = conv_bn_form("snk_conv3x3_bn_f16", HS_MODE_ARGS, d_x, d_wS, d_scale, d_shift, d_residual, d_out, relu, n_images, height,
+                              width, stream);
+    f.split = false;
+    return conv_f16s_launch(f);
 }
 
+// (the compile-time epilogue where the layer closes a residual block and writes no output of its own; the generic one otherwise)
 extern "C" int snk_conv3x3_bn_f16s_head(const float *d_x, const void *d_wS, const float *d_scale, const float *d_shift,
                                         const float *d_residual, float *d_out, const float *d_w1x1, float bn_scale,
                                         float bn_shift, float *d_h1, int n_images, int height, int width, void *stream)
 {
     SNK_REQUIRE(d_x && d_wS && d_scale && d_shift && d_w1x1 && d_h1, "snk_conv3x3_bn_f16s_head: NULL argument");
-    return conv_f16s_launch(d_x, d_wS, d_scale, d_shift, d_residual, d_out, d_w1x1, bn_scale, bn_shift, d_h1, n_images, height,
-                            width, 1, true, stream);
+    ConvForm f = conv_bn_form("snk_conv3x3_bn_f16s_head", d_residual && !d_out ? HS_MODE_HEAD : HS_MODE_ARGS, d_x, d_wS, d_scale, d_shift,
+                              d_residual, d_out, 1, n_images, height, width, stream);
+    conv_form_head(f, d_w1x1, bn_scale, bn_shift, d_h1);
+    return conv_f16s_launch(f);
 }
 
 // The training step's forward convolution: d_out = conv3x3_same(d_x, w) (no batch norm, no ReLU) and, from the same values on
@@ -2164,15 +2250,33 @@ __global__ __launch_bounds__(256) void k_amax_fold128(const float *__restrict__ 
     }
 }
 
-static int conv_stats(bool split, const float *d_x, const void *d_wS, float *d_out, const float *d_center, float *d_partials,
-                      double *d_sums, int n_images, int height, int width, void *stream)
+// what the training entry points share, by name: bare convolutions on float32 tensors (d_center: the centre of the sums, or the
+// mean of the layer below for the input-gradient forms); split = false: the single-pass f16 form
+static ConvForm conv_train_form(const char *who, int mode, bool split, const float *d_x, const void *d_wS, const float *d_residual,
+                                float *d_out, const float *d_center, int n_images, int height, int width, void *stream)
 {
-    SNK_REQUIRE(d_x && d_wS && d_out && d_partials && d_sums && n_images > 0, "snk_conv3x3_%s_stats: bad argument", split ? "f16s" : "f16");
+    ConvForm f = conv_form(who, mode, d_x, d_wS, n_images, height, width, stream);
+    f.split = split;
+    f.a.res = d_residual; f.a.out = d_out; f.a.center = d_center;
+    return f;
+}
+
+// The launch of a training form, the fold of its blocks' sums into d_sums and, where d_amax is given, of their maxima into d_amax.
+static int conv_train(ConvForm f, float *d_partials, double *d_sums, float *d_amax = nullptr)
+{
+    // the launch's grid is known only inside: the maxima sit behind the largest sums + fold scratch the buffer is sized for
+    const long T = ((long)f.a.Hd * f.a.Wd + 31) / 32;
+    f.a.stat_part = d_partials;
+    f.a.amax_part = d_amax ? d_partials + (long)f.n_images * T * 256 + TF_SCRATCH_FLOATS(256) : nullptr;
     int grid = 0;
-    const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, nullptr, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
-                                    split, stream, 0, d_center, d_partials, &grid);
+    const int rc = conv_f16s_launch(f, &grid);
     if (rc) return rc;
-    tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
+    tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)f.stream);
+    if (d_amax) {
+        float *stage = d_partials + (long)f.n_images * T * 384 + TF_SCRATCH_FLOATS(256);
+        k_amax_fold128<<<HS_AMAX_STAGE, 256, 0, (hipStream_t)f.stream>>>(f.a.amax_part, grid, stage);
+        k_amax_fold128<<<1, 256, 0, (hipStream_t)f.stream>>>(stage, HS_AMAX_STAGE, d_amax);
+    }
     SNK_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -2180,7 +2284,9 @@ static int conv_stats(bool split, const float *d_x, const void *d_wS, float *d_o
 extern "C" int snk_conv3x3_f16s_stats(const float *d_x, const void *d_wS, float *d_out, const float *d_center, float *d_partials,
                                       double *d_sums, int n_images, int height, int width, void *stream)
 {
-    return conv_stats(true, d_x, d_wS, d_out, d_center, d_partials, d_sums, n_images, height, width, stream);
+    SNK_REQUIRE(d_x && d_wS && d_out && d_partials && d_sums && n_images > 0, "snk_conv3x3_f16s_stats: bad argument");
+    return conv_train(conv_train_form("snk_conv3x3_f16s_stats", HS_MODE_STATS, true, d_x, d_wS, nullptr, d_out, d_center, n_images, height,
+                                      width, stream), d_partials, d_sums);
 }
 
 // ---- the training step's single-pass f16 mode (TrainStep(conv="f16"), SNK_TRAIN_CONV=f16) -------------------------------------------
@@ -2194,7 +2300,9 @@ extern "C" int snk_conv3x3_f16s_stats(const float *d_x, const void *d_wS, float 
 extern "C" int snk_conv3x3_f16_stats(const float *d_x, const void *d_wS, float *d_out, const float *d_center, float *d_partials,
                                      double *d_sums, int n_images, int height, int width, void *stream)
 {
-    return conv_stats(false, d_x, d_wS, d_out, d_center, d_partials, d_sums, n_images, height, width, stream);
+    SNK_REQUIRE(d_x && d_wS && d_out && d_partials && d_sums && n_images > 0, "snk_conv3x3_f16_stats: bad argument");
+    return conv_train(conv_train_form("snk_conv3x3_f16_stats", HS_MODE_STATS, false, d_x, d_wS, nullptr, d_out, d_center, n_images, height,
+                                      width, stream), d_partials, d_sums);
 }
 
 // The same with the two options of the deferred batch norm (snake_engine/train_step.py: the activation between the two convolutions
@@ -2204,44 +2312,33 @@ extern "C" int snk_conv3x3_f16_stats(const float *d_x, const void *d_wS, float *
 //     would have written; the input scale in d_wS's tail must cover that range (snk_bn_train_finalize_range);
 //   d_amax (or NULL; with either input form): 128 floats, the largest |out - center| per channel -- what snk_bn_train_finalize_range turns into the
 //     range of this layer's own batch norm + ReLU output without a pass over it.
-static int conv_stats_deferred(bool split, const float *d_x, const void *d_wS, float *d_out, const float *d_center,
-                               const float *d_in_scale, const float *d_in_shift, float *d_amax, float *d_partials,
-                               double *d_sums, int n_images, int height, int width, void *stream)
+static int hs_stats_mode(const float *d_in_scale, const float *d_amax)
 {
-    SNK_REQUIRE(d_x && d_wS && d_out && d_partials && d_sums && n_images > 0 && !d_in_scale == !d_in_shift,
-                "snk_conv3x3_%s_stats_deferred: bad argument", split ? "f16s" : "f16");
-    // the launch's grid is known only inside: the maxima sit behind the largest sums + fold scratch the buffer is sized for
-    const long T = ((long)height * width + 31) / 32;
-    float *amax_part = d_amax ? d_partials + (long)n_images * T * 256 + TF_SCRATCH_FLOATS(256) : nullptr;
-    int grid = 0;
-    const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, nullptr, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
-                                    split, stream, 0, d_center, d_partials, &grid, false, nullptr, nullptr, nullptr, d_in_scale, d_in_shift,
-                                    amax_part);
-    if (rc) return rc;
-    tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
-    if (d_amax) {
-        float *stage = d_partials + (long)n_images * T * 384 + TF_SCRATCH_FLOATS(256);
-        k_amax_fold128<<<HS_AMAX_STAGE, 256, 0, (hipStream_t)stream>>>(amax_part, grid, stage);
-        k_amax_fold128<<<1, 256, 0, (hipStream_t)stream>>>(stage, HS_AMAX_STAGE, d_amax);
-    }
-    SNK_CHECK_HIP(hipGetLastError());
-    return 0;
+    return !d_in_scale ? HS_MODE_STATS : d_amax ? HS_MODE_STATS_AFF_AMAX : HS_MODE_STATS_AFF;
 }
 
 extern "C" int snk_conv3x3_f16s_stats_deferred(const float *d_x, const void *d_wS, float *d_out, const float *d_center,
                                                const float *d_in_scale, const float *d_in_shift, float *d_amax, float *d_partials,
                                                double *d_sums, int n_images, int height, int width, void *stream)
 {
-    return conv_stats_deferred(true, d_x, d_wS, d_out, d_center, d_in_scale, d_in_shift, d_amax, d_partials, d_sums, n_images, height,
-                               width, stream);
+    SNK_REQUIRE(d_x && d_wS && d_out && d_partials && d_sums && n_images > 0 && !d_in_scale == !d_in_shift,
+                "snk_conv3x3_f16s_stats_deferred: bad argument");
+    ConvForm f = conv_train_form("snk_conv3x3_f16s_stats_deferred", hs_stats_mode(d_in_scale, d_amax), true, d_x, d_wS, nullptr, d_out,
+                                 d_center, n_images, height, width, stream);
+    f.a.aff_scale = d_in_scale; f.a.aff_shift = d_in_shift;
+    return conv_train(f, d_partials, d_sums, d_amax);
 }
 
 extern "C" int snk_conv3x3_f16_stats_deferred(const float *d_x, const void *d_wS, float *d_out, const float *d_center,
                                               const float *d_in_scale, const float *d_in_shift, float *d_amax, float *d_partials,
                                               double *d_sums, int n_images, int height, int width, void *stream)
 {
-    return conv_stats_deferred(false, d_x, d_wS, d_out, d_center, d_in_scale, d_in_shift, d_amax, d_partials, d_sums, n_images, height,
-                               width, stream);
+    SNK_REQUIRE(d_x && d_wS && d_out && d_partials && d_sums && n_images > 0 && !d_in_scale == !d_in_shift,
+                "snk_conv3x3_f16_stats_deferred: bad argument");
+    ConvForm f = conv_train_form("snk_conv3x3_f16_stats_deferred", hs_stats_mode(d_in_scale, d_amax), false, d_x, d_wS, nullptr, d_out,
+                                 d_center, n_images, height, width, stream);
+    f.a.aff_scale = d_in_scale; f.a.aff_shift = d_in_shift;
+    return conv_train(f, d_partials, d_sums, d_amax);
 }
 
 // reduced precision with f16 activations in HBM (BASELINE configs[4]): d_x16 / d_residual16 are f16 [n][H][W][128]; the output
@@ -2252,8 +2349,10 @@ extern "C" int snk_conv3x3_bn_f16_act16(const void *d_x16, const void *d_wS, con
                                         int relu, void *stream)
 {
     SNK_REQUIRE(d_x16 && d_wS && d_scale && d_shift && d_out, "snk_conv3x3_bn_f16_act16: NULL argument");
-    return conv_f16s_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, (float *)d_out, nullptr, 0.f,
-                            0.f, nullptr, n_images, height, width, relu, false, stream, out_f16 ? 3 : 1);
+    ConvForm f = conv_bn_form("snk_conv3x3_bn_f16_act16", hs_tower_mode(relu, d_residual16), d_x16, d_wS, d_scale, d_shift, d_residual16,
+                              d_out, relu, n_images, height, width, stream);
+    conv_form_a16(f, out_f16 != 0, false, false);
+    return conv_f16s_launch(f);
 }
 
 // BASELINE configs[4] as it is worded, "bf16 MFMA conv": bf16 activations in HBM (d_x16 / d_residual16: bf16 [n][H][W][128]; the
@@ -2265,8 +2364,10 @@ extern "C" int snk_conv3x3_bn_bf16_act16(const void *d_x16, const void *d_wS, co
                                          int relu, void *stream)
 {
     SNK_REQUIRE(d_x16 && d_wS && d_scale && d_shift && d_out, "snk_conv3x3_bn_bf16_act16: NULL argument");
-    return conv_f16s_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, (float *)d_out, nullptr, 0.f,
-                            0.f, nullptr, n_images, height, width, relu, false, stream, out_bf16 ? 3 : 1, nullptr, nullptr, nullptr, true);
+    ConvForm f = conv_bn_form("snk_conv3x3_bn_bf16_act16", hs_tower_mode(relu, d_residual16), d_x16, d_wS, d_scale, d_shift, d_residual16,
+                              d_out, relu, n_images, height, width, stream);
+    conv_form_a16(f, out_bf16 != 0, true, false);
+    return conv_f16s_launch(f);
 }
 
 // The last layer of the towers with 16-bit activations with the head's 1x1 stage in its epilogue (alpha_nnet.py:46-50), as
@@ -2278,8 +2379,11 @@ extern "C" int snk_conv3x3_bn_f16_act16_head(const void *d_x16, const void *d_wS
                                              float *d_h1, int n_images, int height, int width, void *stream)
 {
     SNK_REQUIRE(d_x16 && d_wS && d_scale && d_shift && d_residual16 && d_w1x1 && d_h1, "snk_conv3x3_bn_f16_act16_head: NULL argument");
-    return conv_f16s_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, nullptr, d_w1x1, bn_scale,
-                            bn_shift, d_h1, n_images, height, width, 1, false, stream, 1);
+    ConvForm f = conv_bn_form("snk_conv3x3_bn_f16_act16_head", HS_MODE_HEAD, d_x16, d_wS, d_scale, d_shift, d_residual16, nullptr, 1,
+                              n_images, height, width, stream);
+    conv_form_head(f, d_w1x1, bn_scale, bn_shift, d_h1);
+    conv_form_a16(f, false, false, false);
+    return conv_f16s_launch(f);
 }
 
 extern "C" int snk_conv3x3_bn_bf16_act16_head(const void *d_x16, const void *d_wS, const float *d_scale, const float *d_shift,
@@ -2287,8 +2391,11 @@ extern "C" int snk_conv3x3_bn_bf16_act16_head(const void *d_x16, const void *d_w
                                               float *d_h1, int n_images, int height, int width, void *stream)
 {
     SNK_REQUIRE(d_x16 && d_wS && d_scale && d_shift && d_residual16 && d_w1x1 && d_h1, "snk_conv3x3_bn_bf16_act16_head: NULL argument");
-    return conv_f16s_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, nullptr, d_w1x1, bn_scale,
-                            bn_shift, d_h1, n_images, height, width, 1, false, stream, 1, nullptr, nullptr, nullptr, true);
+    ConvForm f = conv_bn_form("snk_conv3x3_bn_bf16_act16_head", HS_MODE_HEAD, d_x16, d_wS, d_scale, d_shift, d_residual16, nullptr, 1,
+                              n_images, height, width, stream);
+    conv_form_head(f, d_w1x1, bn_scale, bn_shift, d_h1);
+    conv_form_a16(f, false, true, false);
+    return conv_f16s_launch(f);
 }
 
 // The mxfp8 tower (SNK_CONV_ALGO=mxfp8): the bf16 tower's arguments, activations and epilogue; the MFMA operands are MX-FP8 (the
@@ -2300,9 +2407,10 @@ extern "C" int snk_conv3x3_bn_mxfp8_act16(const void *d_x16, const void *d_wS, c
 {
     SNK_REQUIRE(d_x16 && d_wS && d_scale && d_shift && d_out, "snk_conv3x3_bn_mxfp8_act16: NULL argument");
     SNK_REQUIRE(n_images > 0, "snk_conv3x3_bn_mxfp8_act16: %d images", n_images);
-    return conv_f16s_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, (float *)d_out, nullptr, 0.f,
-                            0.f, nullptr, n_images, height, width, relu, false, stream, out_bf16 ? 3 : 1, nullptr, nullptr, nullptr, true,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true);
+    ConvForm f = conv_bn_form("snk_conv3x3_bn_mxfp8_act16", hs_tower_mode(relu, d_residual16), d_x16, d_wS, d_scale, d_shift, d_residual16,
+                              d_out, relu, n_images, height, width, stream);
+    conv_form_a16(f, out_bf16 != 0, true, true);
+    return conv_f16s_launch(f);
 }
 
 extern "C" int snk_conv3x3_bn_mxfp8_act16_rect(const void *d_x16, const void *d_wS, const float *d_scale, const float *d_shift,
@@ -2311,9 +2419,9 @@ extern "C" int snk_conv3x3_bn_mxfp8_act16_rect(const void *d_x16, const void *d_
                                                const void *d_bg_out16, int n_images, int height, int width, void *stream)
 {
     SNK_REQUIRE(n_images > 0, "snk_conv3x3_bn_mxfp8_act16_rect: %d images", n_images);
-    return conv_f16s_rect_launch("snk_conv3x3_bn_mxfp8_act16_rect", (const float *)d_x16, d_wS, d_scale, d_shift,
-                                 (const float *)d_residual16, (float *)d_out16, d_desc, d_count, (const float *)d_bg_in16, grow_in,
-                                 (const float *)d_bg_res16, grow_res, (const float *)d_bg_out16, n_images, height, width, true, stream, true, true);
+    return conv_f16s_rect_launch(conv_rect_form16(conv_rect_form("snk_conv3x3_bn_mxfp8_act16_rect", d_x16, d_wS, d_scale, d_shift, d_residual16,
+                                                                 d_out16, d_desc, d_count, d_bg_in16, grow_in, d_bg_res16, grow_res, d_bg_out16,
+                                                                 n_images, height, width, stream), true, true));
 }
 
 extern "C" int snk_conv3x3_bn_mxfp8_act16_head(const void *d_x16, const void *d_wS, const float *d_scale, const float *d_shift,
@@ -2322,9 +2430,11 @@ extern "C" int snk_conv3x3_bn_mxfp8_act16_head(const void *d_x16, const void *d_
 {
     SNK_REQUIRE(d_x16 && d_wS && d_scale && d_shift && d_residual16 && d_w1x1 && d_h1, "snk_conv3x3_bn_mxfp8_act16_head: NULL argument");
     SNK_REQUIRE(n_images > 0, "snk_conv3x3_bn_mxfp8_act16_head: %d images", n_images);
-    return conv_f16s_launch((const float *)d_x16, d_wS, d_scale, d_shift, (const float *)d_residual16, nullptr, d_w1x1, bn_scale,
-                            bn_shift, d_h1, n_images, height, width, 1, false, stream, 1, nullptr, nullptr, nullptr, true,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true);
+    ConvForm f = conv_bn_form("snk_conv3x3_bn_mxfp8_act16_head", HS_MODE_HEAD, d_x16, d_wS, d_scale, d_shift, d_residual16, nullptr, 1,
+                              n_images, height, width, stream);
+    conv_form_head(f, d_w1x1, bn_scale, bn_shift, d_h1);
+    conv_form_a16(f, false, true, true);
+    return conv_f16s_launch(f);
 }
 
 // The training step's INPUT-GRADIENT convolution with the next batch-norm backward's sums in its epilogue: d_out = conv3x3_same(d_x,
@@ -2332,61 +2442,43 @@ extern "C" int snk_conv3x3_bn_mxfp8_act16_head(const void *d_x16, const void *d_
 // on their way out d_sums[0..127] = sum(g), d_sums[128..255] = sum(g * (y - mean) * inv) with g = d_out where that layer's ReLU bit
 // is set (d_mask: one byte per quad of channels, as snk_bn_train_apply writes them; d_y: its pre-batch-norm output) -- what
 // snk_bn_train_grad_sums_f64 computes from d_out in a pass of its own.  d_partials: snk_conv3x3_stats_partials floats.
-static int conv_igrad_stats(bool split, const float *d_x, const void *d_wS, const float *d_residual, float *d_out, const float *d_y,
-                            const uint8_t *d_mask, const float *d_mean, const float *d_inv, float *d_partials, double *d_sums,
-                            int n_images, int height, int width, void *stream)
-{
-    SNK_REQUIRE(d_x && d_wS && d_out && d_y && d_mask && d_mean && d_inv && d_partials && d_sums && n_images > 0,
-                "snk_conv3x3_%s_igrad_stats: bad argument", split ? "f16s" : "f16");
-    int grid = 0;
-    const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, d_residual, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
-                                    split, stream, 0, d_mean, d_partials, &grid, false, d_y, d_mask, d_inv);
-    if (rc) return rc;
-    tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
-    SNK_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
 extern "C" int snk_conv3x3_f16s_igrad_stats(const float *d_x, const void *d_wS, const float *d_residual, float *d_out,
                                             const float *d_y, const uint8_t *d_mask, const float *d_mean, const float *d_inv, float *d_partials,
                                             double *d_sums, int n_images, int height, int width, void *stream)
 {
-    return conv_igrad_stats(true, d_x, d_wS, d_residual, d_out, d_y, d_mask, d_mean, d_inv, d_partials, d_sums, n_images, height,
-                            width, stream);
+    SNK_REQUIRE(d_x && d_wS && d_out && d_y && d_mask && d_mean && d_inv && d_partials && d_sums && n_images > 0,
+                "snk_conv3x3_f16s_igrad_stats: bad argument");
+    ConvForm f = conv_train_form("snk_conv3x3_f16s_igrad_stats", HS_MODE_IGRAD, true, d_x, d_wS, d_residual, d_out, d_mean, n_images, height,
+                                 width, stream);
+    f.a.g_y = d_y; f.a.g_mask = d_mask; f.a.g_inv = d_inv;
+    return conv_train(f, d_partials, d_sums);
 }
 
 extern "C" int snk_conv3x3_f16_igrad_stats(const float *d_x, const void *d_wS, const float *d_residual, float *d_out,
                                            const float *d_y, const uint8_t *d_mask, const float *d_mean, const float *d_inv, float *d_partials,
                                            double *d_sums, int n_images, int height, int width, void *stream)
 {
-    return conv_igrad_stats(false, d_x, d_wS, d_residual, d_out, d_y, d_mask, d_mean, d_inv, d_partials, d_sums, n_images, height,
-                            width, stream);
+    SNK_REQUIRE(d_x && d_wS && d_out && d_y && d_mask && d_mean && d_inv && d_partials && d_sums && n_images > 0,
+                "snk_conv3x3_f16_igrad_stats: bad argument");
+    ConvForm f = conv_train_form("snk_conv3x3_f16_igrad_stats", HS_MODE_IGRAD, false, d_x, d_wS, d_residual, d_out, d_mean, n_images, height,
+                                 width, stream);
+    f.a.g_y = d_y; f.a.g_mask = d_mask; f.a.g_inv = d_inv;
+    return conv_train(f, d_partials, d_sums);
 }
 
 // The same for a layer below whose batch norm + ReLU output was never written (deferred): its ReLU decision is
 // d_y * d_scale[c] + d_shift[c] > 0 -- the sign of what snk_bn_train_apply would have written -- instead of mask bytes.
-static int conv_igrad_stats_deferred(bool split, const float *d_x, const void *d_wS, const float *d_residual, float *d_out,
-                                     const float *d_y, const float *d_scale, const float *d_shift, const float *d_mean,
-                                     const float *d_inv, float *d_partials, double *d_sums, int n_images, int height, int width, void *stream)
-{
-    SNK_REQUIRE(d_x && d_wS && d_out && d_y && d_scale && d_shift && d_mean && d_inv && d_partials && d_sums && n_images > 0,
-                "snk_conv3x3_%s_igrad_stats_deferred: bad argument", split ? "f16s" : "f16");
-    int grid = 0;
-    const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, d_residual, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
-                                    split, stream, 0, d_mean, d_partials, &grid, false, d_y, nullptr, d_inv, d_scale, d_shift);
-    if (rc) return rc;
-    tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
-    SNK_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
 extern "C" int snk_conv3x3_f16s_igrad_stats_deferred(const float *d_x, const void *d_wS, const float *d_residual, float *d_out,
                                                      const float *d_y, const float *d_scale, const float *d_shift,
                                                      const float *d_mean, const float *d_inv, float *d_partials, double *d_sums, int n_images,
                                                      int height, int width, void *stream)
 {
-    return conv_igrad_stats_deferred(true, d_x, d_wS, d_residual, d_out, d_y, d_scale, d_shift, d_mean, d_inv, d_partials, d_sums,
-                                     n_images, height, width, stream);
+    SNK_REQUIRE(d_x && d_wS && d_out && d_y && d_scale && d_shift && d_mean && d_inv && d_partials && d_sums && n_images > 0,
+                "snk_conv3x3_f16s_igrad_stats_deferred: bad argument");
+    ConvForm f = conv_train_form("snk_conv3x3_f16s_igrad_stats_deferred", HS_MODE_IGRAD_AFF, true, d_x, d_wS, d_residual, d_out, d_mean,
+                                 n_images, height, width, stream);
+    f.a.g_y = d_y; f.a.g_inv = d_inv; f.a.aff_scale = d_scale; f.a.aff_shift = d_shift;
+    return conv_train(f, d_partials, d_sums);
 }
 
 extern "C" int snk_conv3x3_f16_igrad_stats_deferred(const float *d_x, const void *d_wS, const float *d_residual, float *d_out,
@@ -2394,37 +2486,28 @@ extern "C" int snk_conv3x3_f16_igrad_stats_deferred(const float *d_x, const void
                                                     const float *d_inv, float *d_partials, double *d_sums, int n_images, int height,
                                                     int width, void *stream)
 {
-    return conv_igrad_stats_deferred(false, d_x, d_wS, d_residual, d_out, d_y, d_scale, d_shift, d_mean, d_inv, d_partials, d_sums,
-                                     n_images, height, width, stream);
+    SNK_REQUIRE(d_x && d_wS && d_out && d_y && d_scale && d_shift && d_mean && d_inv && d_partials && d_sums && n_images > 0,
+                "snk_conv3x3_f16_igrad_stats_deferred: bad argument");
+    ConvForm f = conv_train_form("snk_conv3x3_f16_igrad_stats_deferred", HS_MODE_IGRAD_AFF, false, d_x, d_wS, d_residual, d_out, d_mean,
+                                 n_images, height, width, stream);
+    f.a.g_y = d_y; f.a.g_inv = d_inv; f.a.aff_scale = d_scale; f.a.aff_shift = d_shift;
+    return conv_train(f, d_partials, d_sums);
 }
 
 // snk_conv3x3_f16s_igrad_stats whose shortcut gradient is d_residual WHERE d_residual_mask's bit is set: d_residual = the gradient
 // at the residual block's output (before that output's ReLU), d_residual_mask = that output's ReLU bits (snk_bn_train_apply's
 // bytes) -- the masked copy snk_bn_train_grad_apply(d_g) writes is not needed.  d_out may be d_residual (in place).
-static int conv_igrad_stats_masked_res(bool split, const float *d_x, const void *d_wS, const float *d_residual,
-                                       const uint8_t *d_residual_mask, float *d_out, const float *d_y, const uint8_t *d_mask, const float *d_mean,
-                                       const float *d_inv, float *d_partials, double *d_sums, int n_images, int height, int width,
-                                       void *stream)
-{
-    SNK_REQUIRE(d_x && d_wS && d_residual && d_residual_mask && d_out && d_y && d_mask && d_mean && d_inv && d_partials && d_sums &&
-                n_images > 0, "snk_conv3x3_%s_igrad_stats_masked_res: bad argument", split ? "f16s" : "f16");
-    int grid = 0;
-    const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, d_residual, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
-                                    split, stream, 0, d_mean, d_partials, &grid, false, d_y, d_mask, d_inv, nullptr, nullptr, nullptr,
-                                    d_residual_mask);
-    if (rc) return rc;
-    tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
-    SNK_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
 extern "C" int snk_conv3x3_f16s_igrad_stats_masked_res(const float *d_x, const void *d_wS, const float *d_residual,
                                                        const uint8_t *d_residual_mask, float *d_out, const float *d_y, const uint8_t *d_mask,
                                                        const float *d_mean, const float *d_inv, float *d_partials, double *d_sums,
                                                        int n_images, int height, int width, void *stream)
 {
-    return conv_igrad_stats_masked_res(true, d_x, d_wS, d_residual, d_residual_mask, d_out, d_y, d_mask, d_mean, d_inv, d_partials,
-                                       d_sums, n_images, height, width, stream);
+    SNK_REQUIRE(d_x && d_wS && d_residual && d_residual_mask && d_out && d_y && d_mask && d_mean && d_inv && d_partials && d_sums &&
+                n_images > 0, "snk_conv3x3_f16s_igrad_stats_masked_res: bad argument");
+    ConvForm f = conv_train_form("snk_conv3x3_f16s_igrad_stats_masked_res", HS_MODE_IGRAD_MRES, true, d_x, d_wS, d_residual, d_out, d_mean,
+                                 n_images, height, width, stream);
+    f.a.g_y = d_y; f.a.g_mask = d_mask; f.a.g_inv = d_inv; f.a.res_mask = d_residual_mask;
+    return conv_train(f, d_partials, d_sums);
 }
 
 extern "C" int snk_conv3x3_f16_igrad_stats_masked_res(const float *d_x, const void *d_wS, const float *d_residual,
@@ -2432,37 +2515,28 @@ extern "C" int snk_conv3x3_f16_igrad_stats_masked_res(const float *d_x, const vo
                                                       const float *d_mean, const float *d_inv, float *d_partials, double *d_sums,
                                                       int n_images, int height, int width, void *stream)
 {
-    return conv_igrad_stats_masked_res(false, d_x, d_wS, d_residual, d_residual_mask, d_out, d_y, d_mask, d_mean, d_inv, d_partials,
-                                       d_sums, n_images, height, width, stream);
+    SNK_REQUIRE(d_x && d_wS && d_residual && d_residual_mask && d_out && d_y && d_mask && d_mean && d_inv && d_partials && d_sums &&
+                n_images > 0, "snk_conv3x3_f16_igrad_stats_masked_res: bad argument");
+    ConvForm f = conv_train_form("snk_conv3x3_f16_igrad_stats_masked_res", HS_MODE_IGRAD_MRES, false, d_x, d_wS, d_residual, d_out, d_mean,
+                                 n_images, height, width, stream);
+    f.a.g_y = d_y; f.a.g_mask = d_mask; f.a.g_inv = d_inv; f.a.res_mask = d_residual_mask;
+    return conv_train(f, d_partials, d_sums);
 }
 
 // snk_conv3x3_f16s_igrad_stats_masked_res for a layer below whose batch norm + ReLU output was never written (the deferred stem):
 // the ReLU decision of the SUMS is d_y * d_scale[c] + d_shift[c] > 0 instead of mask bytes
-static int conv_igrad_stats_masked_res_deferred(bool split, const float *d_x, const void *d_wS, const float *d_residual,
-                                                const uint8_t *d_residual_mask, float *d_out, const float *d_y, const float *d_scale,
-                                                const float *d_shift, const float *d_mean, const float *d_inv, float *d_partials,
-                                                double *d_sums, int n_images, int height, int width, void *stream)
-{
-    SNK_REQUIRE(d_x && d_wS && d_residual && d_residual_mask && d_out && d_y && d_scale && d_shift && d_mean && d_inv && d_partials &&
-                d_sums && n_images > 0, "snk_conv3x3_%s_igrad_stats_masked_res_deferred: bad argument", split ? "f16s" : "f16");
-    int grid = 0;
-    const int rc = conv_f16s_launch(d_x, d_wS, nullptr, nullptr, d_residual, d_out, nullptr, 0.f, 0.f, nullptr, n_images, height, width, 0,
-                                    split, stream, 0, d_mean, d_partials, &grid, false, d_y, nullptr, d_inv, d_scale, d_shift, nullptr,
-                                    d_residual_mask);
-    if (rc) return rc;
-    tf_fold<double>(d_partials, grid, 256, 256, 1.0, d_sums, (double *)(d_partials + (long)grid * 256), (hipStream_t)stream);
-    SNK_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
 extern "C" int snk_conv3x3_f16s_igrad_stats_masked_res_deferred(const float *d_x, const void *d_wS, const float *d_residual,
                                                                 const uint8_t *d_residual_mask, float *d_out, const float *d_y,
                                                                 const float *d_scale, const float *d_shift, const float *d_mean,
                                                                 const float *d_inv, float *d_partials, double *d_sums, int n_images,
                                                                 int height, int width, void *stream)
 {
-    return conv_igrad_stats_masked_res_deferred(true, d_x, d_wS, d_residual, d_residual_mask, d_out, d_y, d_scale, d_shift, d_mean,
-                                                d_inv, d_partials, d_sums, n_images, height, width, stream);
+    SNK_REQUIRE(d_x && d_wS && d_residual && d_residual_mask && d_out && d_y && d_scale && d_shift && d_mean && d_inv && d_partials &&
+                d_sums && n_images > 0, "snk_conv3x3_f16s_igrad_stats_masked_res_deferred: bad argument");
+    ConvForm f = conv_train_form("snk_conv3x3_f16s_igrad_stats_masked_res_deferred", HS_MODE_IGRAD_MRES_AFF, true, d_x, d_wS, d_residual,
+                                 d_out, d_mean, n_images, height, width, stream);
+    f.a.g_y = d_y; f.a.g_inv = d_inv; f.a.aff_scale = d_scale; f.a.aff_shift = d_shift; f.a.res_mask = d_residual_mask;
+    return conv_train(f, d_partials, d_sums);
 }
 
 extern "C" int snk_conv3x3_f16_igrad_stats_masked_res_deferred(const float *d_x, const void *d_wS, const float *d_residual,
@@ -2471,6 +2545,10 @@ extern "C" int snk_conv3x3_f16_igrad_stats_masked_res_deferred(const float *d_x,
                                                                const float *d_inv, float *d_partials, double *d_sums, int n_images, int height,
                                                                int width, void *stream)
 {
-    return conv_igrad_stats_masked_res_deferred(false, d_x, d_wS, d_residual, d_residual_mask, d_out, d_y, d_scale, d_shift, d_mean,
-                                                d_inv, d_partials, d_sums, n_images, height, width, stream);
+    SNK_REQUIRE(d_x && d_wS && d_residual && d_residual_mask && d_out && d_y && d_scale && d_shift && d_mean && d_inv && d_partials &&
+                d_sums && n_images > 0, "snk_conv3x3_f16_igrad_stats_masked_res_deferred: bad argument");
+    ConvForm f = conv_train_form("snk_conv3x3_f16_igrad_stats_masked_res_deferred", HS_MODE_IGRAD_MRES_AFF, false, d_x, d_wS, d_residual,
+                                 d_out, d_mean, n_images, height, width, stream);
+    f.a.g_y = d_y; f.a.g_inv = d_inv; f.a.aff_scale = d_scale; f.a.aff_shift = d_shift; f.a.res_mask = d_residual_mask;
+    return conv_train(f, d_partials, d_sums);
 }

@@ -9,6 +9,7 @@ Weight list order (= Keras ``model.get_weights()`` order of the reference graph)
 import ctypes as C
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -121,6 +122,39 @@ def rect_layer_count(h, w, n_layers, threshold=0.93):
     return count
 
 
+# What a SNK_CONV_ALGO value means, in one place.  The entry points are named here and bound to the library once in QNet.__init__:
+#   prepare, takes_scale   the weight-image entry; True: it takes the layer's activation scale (conv_x_scale)
+#   wbuf                   0: the image is a row of QNet._wimg; 16 / 9: a float32 buffer of its own of that many 128 x 128 matrices
+#   unit_scale             conv_x_scale is forced to 1 (16-bit activations are staged as they are)
+#   guard                  the net's guard word is installed in every image (a launch that clamps reports to it)
+#   act                    dtype of the tower's activations in HBM (None: float32)
+#   stem, stem_rect, layer, layer_rect, layer_rect_pack, head      the full / sub-rectangle / packed / fused-head launch forms
+#   plan, max_blocks       the sub-rectangle plan of this tower's block frame
+#   fuse_head, head_env    the last layer carries the head's 1x1 stage; SNK_HEAD_FUSE=0 may switch that off
+_TOWER_ENTRIES = ("prepare", "stem", "stem_rect", "layer", "layer_rect", "layer_rect_pack", "head", "plan", "max_blocks")
+_Tower = namedtuple("_Tower", _TOWER_ENTRIES + ("takes_scale", "wbuf", "unit_scale", "guard", "act", "fuse_head", "head_env"),
+                    defaults=(None,) * 7 + (False, 0, False, False, None, False, False))
+_RECT16 = dict(plan="snk_conv_rect_plan_act16", max_blocks="snk_conv_rect_max_blocks_act16", unit_scale=True, fuse_head=True, head_env=True)
+TOWERS = {
+    "f16s": _Tower("snk_conv3x3_prepare_weights_f16s", "snk_stem_conv_bn_relu_f32", "snk_stem_conv_bn_relu_f32_rect",
+                   "snk_conv3x3_bn_f16s", "snk_conv3x3_bn_f16s_rect", "snk_conv3x3_bn_f16s_rect_pack", "snk_conv3x3_bn_f16s_head",
+                   plan="snk_conv_rect_plan", max_blocks="snk_conv_rect_max_blocks", takes_scale=True, guard=True, fuse_head=True),
+    "f16": _Tower("snk_conv3x3_prepare_weights_f16s", "snk_stem_conv_bn_relu_f32", layer="snk_conv3x3_bn_f16", takes_scale=True, guard=True),
+    "winograd": _Tower("snk_conv3x3_prepare_weights_winograd", "snk_stem_conv_bn_relu_f32", layer="snk_conv3x3_bn_f32_winograd", wbuf=16),
+    "direct": _Tower("snk_conv3x3_prepare_weights", "snk_stem_conv_bn_relu_f32", layer="snk_conv3x3_bn_f32", wbuf=9),
+    "f16a": _Tower("snk_conv3x3_prepare_weights_f16_act16", "snk_stem_conv_bn_relu_f16out", "snk_stem_conv_bn_relu_f16out_rect",
+                   "snk_conv3x3_bn_f16_act16", "snk_conv3x3_bn_f16_act16_rect", head="snk_conv3x3_bn_f16_act16_head",
+                   guard=True, act=torch.float16, **_RECT16),
+    "bf16": _Tower("snk_conv3x3_prepare_weights_bf16", "snk_stem_conv_bn_relu_bf16out", "snk_stem_conv_bn_relu_bf16out_rect",
+                   "snk_conv3x3_bn_bf16_act16", "snk_conv3x3_bn_bf16_act16_rect", head="snk_conv3x3_bn_bf16_act16_head",
+                   act=torch.bfloat16, **_RECT16),
+    # the bf16 tower's stem and activations; the layers' MFMA operands are MX-FP8, the weights quantized once by the prepare entry
+    "mxfp8": _Tower("snk_conv3x3_prepare_weights_mxfp8", "snk_stem_conv_bn_relu_bf16out", "snk_stem_conv_bn_relu_bf16out_rect",
+                    "snk_conv3x3_bn_mxfp8_act16", "snk_conv3x3_bn_mxfp8_act16_rect", head="snk_conv3x3_bn_mxfp8_act16_head",
+                    act=torch.bfloat16, **_RECT16),
+}
+
+
 class QNet:
     def __init__(self, weights, input_shape, device=None, max_chunk=4096):
         if not torch.cuda.is_available():
@@ -142,12 +176,14 @@ class QNet:
         # activations is HBM-bound); "bf16": the same block body on bf16 -- bf16 activations in HBM, bf16 weights,
         # v_mfma_f32_32x32x16_bf16: BASELINE configs[4]'s "bf16 MFMA conv" as it is worded; "mxfp8": the bf16 tower with MX-FP8
         # MFMA operands (bf16 activations in HBM, quantized per 32-channel block on their way into LDS; v_mfma_scale_f32_32x32x64_f8f6f4)
-        if self.conv_algo not in ("f16s", "winograd", "direct", "bf16", "f16", "f16a", "mxfp8"):
+        if self.conv_algo not in TOWERS:
             raise EngineError(f"SNK_CONV_ALGO={self.conv_algo!r}: expected f16s, winograd, direct, f16, f16a, bf16 or mxfp8")
+        t = TOWERS[self.conv_algo]
+        self._algo_tower = t._replace(**{f: getattr(self.L, getattr(t, f)) for f in _TOWER_ENTRIES if getattr(t, f)})
         # sub-rectangle form of the first tower layers (snk_conv3x3_bn_f16s_rect): SNK_CONV_RECT=0 switches it off,
         # SNK_CONV_RECT_LAYERS=n fixes the number of layers that use it
-        self.rect = self.conv_algo in ("f16s", "f16a", "bf16", "mxfp8") and os.environ.get("SNK_CONV_RECT", "1") != "0"
-        self.act16 = {"f16a": torch.float16, "bf16": torch.bfloat16, "mxfp8": torch.bfloat16}.get(self.conv_algo)      # 16-bit activations in HBM
+        self.rect = t.layer_rect is not None and os.environ.get("SNK_CONV_RECT", "1") != "0"
+        self.act16 = t.act                                   # 16-bit activations in HBM
         self.background = BACKGROUND_PIXEL
         self.guard_trips = 0         # batches forward_guarded evaluated again after a clamp
         self.rect_tiles = None       # set to [] to collect every chunk's (images, per-layer GEMM tiles) device tensors
@@ -181,36 +217,21 @@ class QNet:
         # the split-f16 weight images of all layers are rows of ONE buffer, so that the layers' range flags (a word in each
         # image's tail) come to the host with one strided copy (range_flags)
         self._wimg = None
-        if self.conv_algo in ("f16s", "f16", "f16a", "bf16", "mxfp8") and self.blocks:
+        # (a net without tower layers has no 16-bit activations: the stem's float32 output goes to the head)
+        tw = self.tower = self._algo_tower if self.blocks else self._algo_tower._replace(act=None, stem=self.L.snk_stem_conv_bn_relu_f32)
+        if tw.wbuf == 0 and self.blocks:
             self._wimg = torch.empty((2 * self.blocks, F16S_WEIGHT_BYTES), dtype=torch.uint8, device=dev)
             self._flags_host = torch.empty((2 * self.blocks,), dtype=torch.int32).pin_memory()
             if self._guard is None:      # ONE device word every layer of this net reports a clamp to, and its pinned host mirror
                 self._guard = (torch.zeros((1,), dtype=torch.int32, device=dev), torch.zeros((1,), dtype=torch.int32).pin_memory())
         for i in range(2 * self.blocks):
             base = 5 + 5 * i
-            if self.conv_algo == "bf16":
+            if tw.unit_scale:
                 self.conv_x_scale[i] = 1.0
-                wT = self._wimg[i]
-                check(self.L.snk_conv3x3_prepare_weights_bf16(t[base].contiguous().data_ptr(), wT.data_ptr(), st))
-            elif self.conv_algo == "mxfp8":                  # codes + block scales from the float32 kernel, quantized once here
-                self.conv_x_scale[i] = 1.0
-                wT = self._wimg[i]
-                check(self.L.snk_conv3x3_prepare_weights_mxfp8(t[base].contiguous().data_ptr(), wT.data_ptr(), st))
-            elif self.conv_algo == "f16a":
-                self.conv_x_scale[i] = 1.0                   # f16 activations are staged as they are
-                wT = self._wimg[i]
-                check(self.L.snk_conv3x3_prepare_weights_f16_act16(t[base].contiguous().data_ptr(), wT.data_ptr(), st))
-            elif self.conv_algo in ("f16s", "f16"):
-                wT = self._wimg[i]
-                check(self.L.snk_conv3x3_prepare_weights_f16s(t[base].contiguous().data_ptr(), wT.data_ptr(),
-                                                              self.conv_x_scale[i], st))
-            elif self.conv_algo == "winograd":
-                wT = torch.empty(16 * 128 * 128, dtype=torch.float32, device=dev)
-                check(self.L.snk_conv3x3_prepare_weights_winograd(t[base].contiguous().data_ptr(), wT.data_ptr(), st))
-            else:
-                wT = torch.empty(9 * 128 * 128, dtype=torch.float32, device=dev)
-                check(self.L.snk_conv3x3_prepare_weights(t[base].contiguous().data_ptr(), wT.data_ptr(), st))
-            if self._wimg is not None and self.conv_algo not in ("bf16", "mxfp8"):
+            wT = self._wimg[i] if tw.wbuf == 0 else torch.empty(tw.wbuf * 128 * 128, dtype=torch.float32, device=dev)
+            scale = (self.conv_x_scale[i],) if tw.takes_scale else ()
+            check(tw.prepare(t[base].contiguous().data_ptr(), wT.data_ptr(), *scale, st))
+            if tw.guard:
                 check(self.L.snk_conv3x3_f16s_set_guard_word(wT.data_ptr(), self._guard[0].data_ptr(), st))
             sc, sh = fold(*t[base + 1:base + 5])
             self.conv_wT.append(wT); self.conv_sc.append(sc); self.conv_sh.append(sh)
@@ -294,7 +315,7 @@ class QNet:
         batch-norm heuristic chose (activation_scales) wherever the measured maximum would come within 2^4 of the f16
         limit: a net whose moving statistics do not describe its activations (freshly trained, loaded from a checkpoint)
         gets scales from data instead.  Returns the activation report."""
-        if self.conv_algo not in ("f16s", "f16"):
+        if not self.tower.takes_scale:
             self.calibrated = True              # nothing to fit: callers must not come back with observations every turn
             return []
         rep = self.activation_report(planes)
@@ -318,7 +339,7 @@ class QNet:
     @property
     def guard_ptr(self):
         """address of the net's device guard word (0: this net has no range to watch): the gate of the rollout tick's kernels"""
-        return self._guard[0].data_ptr() if self._guard is not None and self.conv_algo in ("f16s", "f16", "f16a") else 0
+        return self._guard[0].data_ptr() if self._guard is not None and self.tower.guard else 0
 
     def guard_post(self):
         """after a forward: copy the guard word to its pinned host mirror, asynchronously -- `guard_tripped` is valid once the
@@ -391,114 +412,56 @@ class QNet:
             main.wait_stream(sd)
         return out
 
-    def _fn16(self):
-        """(stem, stem on rectangles, layer, layer on rectangles) of the tower with 16-bit activations"""
-        L = self.L
-        if self.conv_algo == "bf16":
-            return (L.snk_stem_conv_bn_relu_bf16out, L.snk_stem_conv_bn_relu_bf16out_rect, L.snk_conv3x3_bn_bf16_act16,
-                    L.snk_conv3x3_bn_bf16_act16_rect, L.snk_conv3x3_bn_bf16_act16_head)
-        if self.conv_algo == "mxfp8":          # the bf16 tower's stem (bf16 activations); its layers with MX-FP8 MFMA operands
-            return (L.snk_stem_conv_bn_relu_bf16out, L.snk_stem_conv_bn_relu_bf16out_rect, L.snk_conv3x3_bn_mxfp8_act16,
-                    L.snk_conv3x3_bn_mxfp8_act16_rect, L.snk_conv3x3_bn_mxfp8_act16_head)
-        return (L.snk_stem_conv_bn_relu_f16out, L.snk_stem_conv_bn_relu_f16out_rect, L.snk_conv3x3_bn_f16_act16,
-                L.snk_conv3x3_bn_f16_act16_rect, L.snk_conv3x3_bn_f16_act16_head)
-
-    def _forward_chunk_f16a(self, planes, mask, out, s0, m, k):
-        """the tower with f16 / bf16 activations in HBM: stem -> 16 bit, every layer 16 -> 16 bit, the last one 16 bit -> float32"""
-        st = torch.cuda.current_stream().cuda_stream
-        L, h, w = self.L, self.h, self.w
-        stem16, stem16_rect, conv16, conv16_rect, conv16_head = self._fn16()
-        # the last layer's epilogue does the head's 1x1 stage (its float32 output -- twice the bytes of any other activation of
-        # this tower -- never goes to HBM); SNK_HEAD_FUSE=0: the separate head kernel on the layer's float32 output
-        fused_head = self._head_fits() and os.environ.get("SNK_HEAD_FUSE", "1") != "0"
+    def _chunk_buffers(self, m, k, fused_head):
+        """[a, b, c, last] of stream slot k: three activation buffers of the tower's dtype and, for a tower with 16-bit
+        activations whose head is not fused, the float32 buffer its last layer writes (None otherwise)"""
+        if self.tower.act is None:
+            return [*self._workspace(m, k), None]
         key = ("a16", k)
         if self._ws is None:
             self._ws = {}
         if key not in self._ws or self._ws[key][0].shape[0] < m or (self._ws[key][3] is None) != fused_head:
-            bufs = [torch.empty((m, h, w, 128), dtype=self.act16, device=self.device) for _ in range(3)]
-            bufs.append(None if fused_head else torch.empty((m, h, w, 128), dtype=torch.float32, device=self.device))
+            bufs = [torch.empty((m, self.h, self.w, 128), dtype=self.tower.act, device=self.device) for _ in range(3)]
+            bufs.append(None if fused_head else torch.empty((m, self.h, self.w, 128), dtype=torch.float32, device=self.device))
             self._ws[key] = bufs
-        bufs = self._ws[key]
-        a, b, c, last = bufs
+        return self._ws[key]
+
+    def _forward_chunk(self, planes, mask, out, s0, m, k):
+        """stem, tower, head of one chunk on the current stream.  A tower with 16-bit activations: stem -> 16 bit, every layer
+        16 -> 16 bit, the last one 16 bit -> float32."""
+        if self.clock_probe is not None:          # bench.py: a one-wavefront clock sample beside this chunk's kernels
+            self.clock_probe.launch()
+        st = torch.cuda.current_stream().cuda_stream
+        L, h, w, t = self.L, self.h, self.w, self.tower
+        # the last layer's epilogue does the head's 1x1 stage (snk_head_dense_f32 keeps 16 states' h1 in 64 KB of LDS; the 16-bit
+        # towers' float32 last output -- twice the bytes of any other activation of theirs -- never goes to HBM); for those towers
+        # SNK_HEAD_FUSE=0 selects the separate head kernel on the layer's float32 output
+        fused_head = t.fuse_head and self.blocks > 0 and self._head_fits() and \
+            not (t.head_env and os.environ.get("SNK_HEAD_FUSE", "1") == "0")
+        a, b, c, last = self._chunk_buffers(m, k, fused_head)
         x = planes[s0:s0 + m]
         plan = self._rect_plan(x, m, k, st) if self._use_rect(m) else None
-        if plan is not None and self.n_rect >= 2:
-            check(stem16_rect(x.data_ptr(), self.stem_w.data_ptr(), self.stem_sc.data_ptr(),
+        if plan is not None and self.n_rect >= 2:         # both readers of the stem's output (layer 0, layer 1's shortcut) are sub-rectangle layers
+            check(t.stem_rect(x.data_ptr(), self.stem_w.data_ptr(), self.stem_sc.data_ptr(),
                               self.stem_sh.data_ptr(), a.data_ptr(), plan[3].data_ptr(), 1, m, h, w, st))
         else:
-            check(stem16(x.data_ptr(), self.stem_w.data_ptr(), self.stem_sc.data_ptr(),
+            check(t.stem(x.data_ptr(), self.stem_w.data_ptr(), self.stem_sc.data_ptr(),
                          self.stem_sh.data_ptr(), a.data_ptr(), m, h, w, st))
         cur, t1, t2 = a, b, c
-        tm = self.conv_timing
-
-        def conv(i, xin, res, dst, out_f16):
-            if tm is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(torch.cuda.current_stream())
-            if dst is None:                                # the last layer with the fused head: dst_h1 instead of a layer output
-                check(conv16_head(xin.data_ptr(), self.conv_wT[i].data_ptr(), self.conv_sc[i].data_ptr(), self.conv_sh[i].data_ptr(),
-                                  res.data_ptr(), self.head_w.data_ptr(), self.head_s, self.head_b, h1.data_ptr(), m, h, w, st))
-            elif plan is not None and i < self.n_rect:     # a sub-rectangle layer is never the last one: f16 output
-                check(conv16_rect(xin.data_ptr(), self.conv_wT[i].data_ptr(), self.conv_sc[i].data_ptr(),
-                                  self.conv_sh[i].data_ptr(), None if res is None else res.data_ptr(),
-                                  dst.data_ptr(), *self._rect_args(i, plan, res), m, h, w, st))
-            else:
-                check(conv16(xin.data_ptr(), self.conv_wT[i].data_ptr(), self.conv_sc[i].data_ptr(),
-                             self.conv_sh[i].data_ptr(), None if res is None else res.data_ptr(),
-                             dst.data_ptr(), int(out_f16), m, h, w, 1, st))
-            if tm is not None:
-                e1.record(torch.cuda.current_stream())
-                tm.append((e0, e1, 2.0 * m * h * w * 9 * 128 * 128))
         h1 = self._h1_workspace(m, k) if fused_head else None
         for blk in range(self.blocks):
-            conv(2 * blk, cur, None, t1, True)
-            if blk == self.blocks - 1:
-                conv(2 * blk + 1, t1, cur, last, False)
+            self._conv(2 * blk, cur, None, t1, m, st, plan=plan)
+            if blk == self.blocks - 1 and (fused_head or last is not None):      # no layer output, or a float32 one of its own
+                self._conv(2 * blk + 1, t1, cur, None if fused_head else last, m, st, h1=h1, plan=plan)
+                cur = last
             else:
-                conv(2 * blk + 1, t1, cur, t2, True)
+                self._conv(2 * blk + 1, t1, cur, t2, m, st, plan=plan)
                 cur, t2 = t2, cur
         mk = None if mask is None else mask[s0:s0 + m]
         if fused_head:
             check(L.snk_head_dense_f32(h1.data_ptr(), self.fc1_w.data_ptr(), self.fc1_b.data_ptr(), self.fc2_w.data_ptr(),
                                        self.fc2_b.data_ptr(), 0 if mk is None else mk.data_ptr(), out[s0:s0 + m].data_ptr(), m, h, w, st))
             return
-        check(L.snk_head_f32(last.data_ptr(), self.head_w.data_ptr(), self.head_s, self.head_b,
-                             self.fc1_w.data_ptr(), self.fc1_b.data_ptr(), self.fc2_w.data_ptr(), self.fc2_b.data_ptr(),
-                             0 if mk is None else mk.data_ptr(), out[s0:s0 + m].data_ptr(), m, h, w, st))
-
-    def _forward_chunk(self, planes, mask, out, s0, m, k):
-        if self.clock_probe is not None:          # bench.py: a one-wavefront clock sample beside this chunk's kernels
-            self.clock_probe.launch()
-        if self.act16 is not None and self.blocks > 0:
-            return self._forward_chunk_f16a(planes, mask, out, s0, m, k)
-        st = torch.cuda.current_stream().cuda_stream
-        L, h, w = self.L, self.h, self.w
-        a, b, c = self._workspace(m, k)
-        x = planes[s0:s0 + m]
-        plan = self._rect_plan(x, m, k, st) if self._use_rect(m) else None
-        if plan is not None and self.n_rect >= 2:         # both readers of the stem's output (layer 0, layer 1's shortcut) are sub-rectangle layers
-            check(L.snk_stem_conv_bn_relu_f32_rect(x.data_ptr(), self.stem_w.data_ptr(), self.stem_sc.data_ptr(),
-                                                   self.stem_sh.data_ptr(), a.data_ptr(), plan[3].data_ptr(), 1, m, h, w, st))
-        else:
-            check(L.snk_stem_conv_bn_relu_f32(x.data_ptr(), self.stem_w.data_ptr(), self.stem_sc.data_ptr(),
-                                              self.stem_sh.data_ptr(), a.data_ptr(), m, h, w, st))
-        cur, t1, t2 = a, b, c
-        # the last layer's epilogue also does the head's 1x1 stage (snk_head_dense_f32 keeps 16 states' h1 in 64 KB of LDS)
-        fused_head = self.conv_algo == "f16s" and self.blocks > 0 and self._head_fits()
-        for blk in range(self.blocks):
-            i0, i1 = 2 * blk, 2 * blk + 1
-            self._conv(i0, cur, None, t1, m, st, plan=plan)
-            if fused_head and blk == self.blocks - 1:
-                h1 = self._h1_workspace(m, k)
-                self._conv(i1, t1, cur, None, m, st, h1=h1)
-                mk = None if mask is None else mask[s0:s0 + m]
-                check(L.snk_head_dense_f32(h1.data_ptr(), self.fc1_w.data_ptr(), self.fc1_b.data_ptr(), self.fc2_w.data_ptr(),
-                                           self.fc2_b.data_ptr(), 0 if mk is None else mk.data_ptr(), out[s0:s0 + m].data_ptr(),
-                                           m, h, w, st))
-                return
-            self._conv(i1, t1, cur, t2, m, st, plan=plan)
-            cur, t2 = t2, cur
-        mk = None if mask is None else mask[s0:s0 + m]
         check(L.snk_head_f32(cur.data_ptr(), self.head_w.data_ptr(), self.head_s, self.head_b,
                              self.fc1_w.data_ptr(), self.fc1_b.data_ptr(), self.fc2_w.data_ptr(), self.fc2_b.data_ptr(),
                              0 if mk is None else mk.data_ptr(), out[s0:s0 + m].data_ptr(), m, h, w, st))
@@ -521,31 +484,21 @@ class QNet:
         scale change."""
         if self._bg is None:
             m, st = 1, torch.cuda.current_stream().cuda_stream
-            a16 = self.act16 is not None
-            dt = self.act16 if a16 else torch.float32
+            dt = self.tower.act or torch.float32
             blank = torch.tensor(self.background, dtype=torch.float32, device=self.device).repeat(1, self.h, self.w, 1).contiguous()
             bufs = [torch.empty((1, self.h, self.w, 128), dtype=dt, device=self.device) for _ in range(3)]
-            stem = self._fn16()[0] if a16 else self.L.snk_stem_conv_bn_relu_f32
-            check(stem(blank.data_ptr(), self.stem_w.data_ptr(), self.stem_sc.data_ptr(), self.stem_sh.data_ptr(),
-                       bufs[0].data_ptr(), m, self.h, self.w, st))
+            check(self.tower.stem(blank.data_ptr(), self.stem_w.data_ptr(), self.stem_sc.data_ptr(), self.stem_sh.data_ptr(),
+                                  bufs[0].data_ptr(), m, self.h, self.w, st))
             bg = torch.empty((1 + self.n_rect, self.h, self.w, 128), dtype=dt, device=self.device)
             bg[0].copy_(bufs[0][0])
             cur, t1, t2 = bufs
             tm, self.conv_timing = self.conv_timing, None
-
-            def conv(i, x, res, out):
-                if a16:
-                    check(self._fn16()[2](x.data_ptr(), self.conv_wT[i].data_ptr(), self.conv_sc[i].data_ptr(),
-                                          self.conv_sh[i].data_ptr(), None if res is None else res.data_ptr(),
-                                          out.data_ptr(), 1, m, self.h, self.w, 1, st))
-                else:
-                    self._conv(i, x, res, out, m, st)
             for i in range(self.n_rect):
                 if i % 2 == 0:
-                    conv(i, cur, None, t1)
+                    self._conv(i, cur, None, t1, m, st)
                     bg[1 + i].copy_(t1[0])
                 else:
-                    conv(i, t1, cur, t2)
+                    self._conv(i, t1, cur, t2, m, st)
                     bg[1 + i].copy_(t2[0])
                     cur, t2 = t2, cur
             self.conv_timing = tm
@@ -565,14 +518,14 @@ class QNet:
     def _rect_plan(self, x, m, k, st):
         """descriptors of this chunk's sub-rectangle layers: (descriptor tensor [n_rect][max_blocks][4], counts [n_rect][2])"""
         bg = self.backgrounds()
-        a16 = self.act16 is not None          # the 16-bit towers cut rectangles for their own block frame
+        t = self.tower                        # (the 16-bit towers cut rectangles for their own block frame)
         # the float32-accurate tower packs the rows of same-shaped rectangles into shared GEMM tiles (SNK_CONV_RECT_PACK=0: every
         # rectangle pads its own last tile); the descriptor array then holds two 16-byte entries per block
-        pack = not a16 and self.rect_pack and m * self.h * self.w * 128 < 2 ** 31
+        pack = t.layer_rect_pack is not None and self.rect_pack and m * self.h * self.w * 128 < 2 ** 31
         mb = int(self.L.snk_conv_rect_pack_max_desc(m, self.h, self.w)) if pack else -1
         if mb < 0:
             pack = False
-            mb = int((self.L.snk_conv_rect_max_blocks_act16 if a16 else self.L.snk_conv_rect_max_blocks)(m, self.h, self.w))
+            mb = int(t.max_blocks(m, self.h, self.w))
         if mb < 0:
             raise EngineError(f"sub-rectangle convolution: shape {m} x {self.h} x {self.w} not supported")
         key = ("rect", k)
@@ -597,39 +550,30 @@ class QNet:
             check(self.L.snk_conv_rect_plan_pack(x.data_ptr(), b0, b1, b2, m, self.h, self.w, self.n_rect, grow, bbox.data_ptr(),
                                                  desc_m.data_ptr(), counts.data_ptr(), order.data_ptr(), st))
             return desc_m, counts, bg, bbox, True
-        check((self.L.snk_conv_rect_plan_act16 if a16 else self.L.snk_conv_rect_plan)(
-            x.data_ptr(), b0, b1, b2, m, self.h, self.w, self.n_rect, grow, bbox.data_ptr(), desc_m.data_ptr(), counts.data_ptr(), st))
+        check(t.plan(x.data_ptr(), b0, b1, b2, m, self.h, self.w, self.n_rect, grow, bbox.data_ptr(), desc_m.data_ptr(),
+                     counts.data_ptr(), st))
         return desc_m, counts, bg, bbox, False
 
     def _conv(self, i, x, res, out, m, st, h1=None, plan=None):
-        tm = self.conv_timing
+        """One launch of tower layer i in one of its three forms: on the plan's sub-rectangles (a layer below n_rect when a plan is
+        given), with the head's 1x1 stage in its epilogue (h1 given; out may be None), or in full.  A tower with 16-bit
+        activations writes 16 bits unless `out` is a float32 buffer."""
+        t, tm = self.tower, self.conv_timing
         if tm is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(torch.cuda.current_stream())
+        lead = (x.data_ptr(), self.conv_wT[i].data_ptr(), self.conv_sc[i].data_ptr(), self.conv_sh[i].data_ptr(),
+                None if res is None else res.data_ptr())
         if plan is not None and i < self.n_rect and h1 is None:
-            conv_rect = self.L.snk_conv3x3_bn_f16s_rect_pack if plan[4] else self.L.snk_conv3x3_bn_f16s_rect
-            check(conv_rect(x.data_ptr(), self.conv_wT[i].data_ptr(), self.conv_sc[i].data_ptr(),
-                            self.conv_sh[i].data_ptr(), None if res is None else res.data_ptr(),
-                            out.data_ptr(), *self._rect_args(i, plan, res), m, self.h, self.w, st))
-            if tm is not None:
-                e1.record(torch.cuda.current_stream())
-                tm.append((e0, e1, 2.0 * m * self.h * self.w * 9 * 128 * 128))
-            return
-        if h1 is not None:
-            check(self.L.snk_conv3x3_bn_f16s_head(x.data_ptr(), self.conv_wT[i].data_ptr(), self.conv_sc[i].data_ptr(),
-                                                  self.conv_sh[i].data_ptr(), None if res is None else res.data_ptr(),
-                                                  None if out is None else out.data_ptr(), self.head_w.data_ptr(),
-                                                  self.head_s, self.head_b, h1.data_ptr(), m, self.h, self.w, st))
-            if tm is not None:
-                e1.record(torch.cuda.current_stream())
-                tm.append((e0, e1, 2.0 * m * self.h * self.w * 9 * 128 * 128))
-            return
-        fn = {"winograd": self.L.snk_conv3x3_bn_f32_winograd,
-              "f16s": self.L.snk_conv3x3_bn_f16s, "f16": self.L.snk_conv3x3_bn_f16}.get(
-            self.conv_algo, self.L.snk_conv3x3_bn_f32)
-        check(fn(x.data_ptr(), self.conv_wT[i].data_ptr(), self.conv_sc[i].data_ptr(),
-                 self.conv_sh[i].data_ptr(), None if res is None else res.data_ptr(),
-                 out.data_ptr(), m, self.h, self.w, 1, st))
+            conv_rect = t.layer_rect_pack if plan[4] else t.layer_rect
+            check(conv_rect(*lead, out.data_ptr(), *self._rect_args(i, plan, res), m, self.h, self.w, st))
+        elif h1 is not None:
+            # (the float32 tower's entry can write the layer's output as well; the 16-bit towers' entries have no such argument)
+            dst = () if t.act is not None else (None if out is None else out.data_ptr(),)
+            check(t.head(*lead, *dst, self.head_w.data_ptr(), self.head_s, self.head_b, h1.data_ptr(), m, self.h, self.w, st))
+        else:
+            out16 = () if t.act is None else (int(out.dtype == t.act),)
+            check(t.layer(*lead, out.data_ptr(), *out16, m, self.h, self.w, 1, st))
         if tm is not None:
             e1.record(torch.cuda.current_stream())
             tm.append((e0, e1, 2.0 * m * self.h * self.w * 9 * 128 * 128))

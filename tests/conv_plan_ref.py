@@ -1,4 +1,4 @@
-"""Plain-Python restatement of the planning loop of conv_f16s_launch (csrc/conv_split.hip): how one host routine cuts the images of
+"""Plain-Python restatement of conv_f16s_plan, the planning loop of conv_f16s_launch (csrc/conv_split.hip): how one host routine cuts the images of
 every tower convolution -- inference and training -- into blocks of M tiles.
 
     plan(n, H, W, a16) -> Plan(n_blk, tiles_base, tiles_rem, NI)
@@ -15,7 +15,7 @@ every tower convolution -- inference and training -- into blocks of M tiles.
 What this catches, and what it does not: the loop below was written from the C++ by hand and the constants are read from the source
 with a regular expression.  tests/test_conv_tiles_cpu.py asserts the plans of the shapes tests/test_conv_tiles_gpu.py runs, so a
 CHANGED CONSTANT (HS_NPB, HS_NST, HS_NST16, HS_BUF16, HS_LDP, HS_GAP16_FULL, the SNK_CONV_FINE_MAX default) that moves one of those
-shapes to another kernel body fails there instead of silently leaving a body untested.  A REWRITTEN LOOP in conv_f16s_launch is not
+shapes to another kernel body fails there instead of silently leaving a body untested.  A REWRITTEN LOOP in conv_f16s_plan is not
 seen: this file would go on stating the old one.  Whoever changes the loop changes this restatement with it.
 """
 import os

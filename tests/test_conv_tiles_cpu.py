@@ -1,4 +1,4 @@
-"""The block plans of the shapes tests/test_conv_tiles_gpu.py runs, from the restatement of conv_f16s_launch's planning loop in
+"""The block plans of the shapes tests/test_conv_tiles_gpu.py runs, from the restatement of conv_f16s_plan, conv_f16s_launch's planning loop in
 tests/conv_plan_ref.py: the GPU tests are named for kernel bodies (k_conv3x3_f16s<NI, MODE, ...> run with ntile tiles), and these
 assertions keep them on those bodies when a frame constant of csrc/conv_split.hip changes.
 

@@ -1,6 +1,6 @@
 """The tower convolution's batched block frames against float64.
 
-Every tower layer goes through conv_f16s_launch (csrc/conv_split.hip), which cuts an image into blocks of up to 8 M tiles and runs
+Every tower layer goes through conv_f16s_launch (csrc/conv_split.hip), which cuts an image (conv_f16s_plan) into blocks of up to 8 M tiles and runs
 k_conv3x3_f16s<NI, MODE, ...>; a batch of at most 40 images is re-cut into one-tile blocks, and that is where every other layer-level
 comparison of the suite lands (tests/test_conv_tiles_cpu.py asserts it).  Here the batch is n = 41 -- the smallest one above the
 re-cut, and 41 = 5 x 8 + 1 leaves one image behind the XCD groups of 8 -- at the shapes whose plans tests/test_conv_tiles_cpu.py
